@@ -8,6 +8,10 @@ steps, aggregated over all ranks (weak scaling: every rank codes its own `--imag
 
 One definition of "MB/s" everywhere in the line: JPEG bytes / (seconds to encode them + seconds to decode them again).
 
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = one timed step); `--full` adds every other
+figure and check (oracle parity and exact round trip, latency, end to end, mixed, skewed, extras, CPU baseline).
+`--dump-outputs DIR` writes what the last timed step computed as .npy files (dump_resident_outputs).
+
 `--gpus N` without a torchrun environment starts the N ranks itself (one process per GPU, RCCL); under
 `python -m torch.distributed.run` the ranks are the launcher's.  `mixed` (BASELINE.json configs[3]) is the strong-scaling
 companion: ONE mixed 1080p / 4K corpus dealt to the ranks by JPEG bytes (shard.shard_indices), host memory to host memory."""
@@ -242,6 +246,69 @@ def pipeline_figure(codec, jpgs, label, verify=False, threads=0, repeats=3):
             "parity": "every file restored bit-exact", "_cs": cs, "_ds": ds}
 
 
+def dump_resident_outputs(L, g, out_dir, imgs, order, dec_descs, d_streams, offs, lens, status, seed=1234):
+    """`--dump-outputs DIR`: what the last timed step handed back, as .npy files that two builds can be compared by (the inputs are
+    seeded, so the same arguments give the same arrays).  The encoder's streams are whole in their lengths and CRC-32s, and sampled
+    at fixed fractions of every stream; the decoder's coefficient frames are whole in the CRC-32 of every distinct image's planes,
+    and sampled as seeded (image, component, block) picks over all images.  Integers are stored exactly (float64 for 32-bit values,
+    float32 for bytes and int16 coefficients); about 25 MB at the default size, at most ~40 MB at any size."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    nseg, nimg = len(lens), len(order)
+    rng = np.random.default_rng(seed)
+    per = max(1, min(512, (4 << 20) // max(1, nseg)))              # <= 4 Mi sampled stream bytes (16 MB)
+    frac = np.sort(rng.random(per))
+    crc = np.zeros(nseg, dtype=np.float64)
+    sample = np.zeros((nseg, per), dtype=np.float32)
+    buf = C.create_string_buffer(max(1, max(lens) if nseg else 1))
+    for i in range(nseg):
+        n = lens[i]
+        if n == 0:
+            continue
+        assert L.lep_gpu_memcpy_d2h(g, buf, d_streams + offs[i], n) == 0
+        b = np.frombuffer(buf, dtype=np.uint8, count=n)
+        crc[i] = zlib.crc32(b)
+        sample[i] = b[(frac * n).astype(np.int64)]
+    np.save(os.path.join(out_dir, "encode_stream_lengths.npy"), np.asarray(lens, dtype=np.float64))
+    np.save(os.path.join(out_dir, "encode_stream_crc32.npy"), crc)
+    np.save(os.path.join(out_dir, "encode_stream_bytes_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "decode_status.npy"), np.asarray(status, dtype=np.float64))
+    # decoded planes: every distinct image whole (as CRC-32s; the frames themselves are tens of GB), ...
+    ndist = len(set(order))
+    maxc = max(imgs[u].desc.ncomp for u in order)
+    fcrc = np.full((ndist, maxc), -1.0)
+    seen = {}
+    for k, u in enumerate(order):
+        if u in seen:
+            continue
+        seen[u] = k
+        d = imgs[u].desc
+        for c in range(d.ncomp):
+            n = d.nblocks(c) * 128
+            fb = C.create_string_buffer(n)
+            assert L.lep_gpu_memcpy_d2h(g, fb, dec_descs[k].blocks[c], n) == 0
+            fcrc[len(seen) - 1, c] = zlib.crc32(fb.raw)
+    np.save(os.path.join(out_dir, "decode_frame_crc32.npy"), fcrc)
+    # ... and seeded blocks of all of them, the replicas included (<= 32 Ki blocks of 64 coefficients: 8 MB)
+    picks = min(32768, sum(imgs[u].desc.total_blocks() for u in order))
+    pi, pc, pb = rng.integers(0, nimg, picks), rng.random(picks), rng.random(picks)
+    coef = np.zeros((picks, 64), dtype=np.float32)
+    blk = (C.c_int16 * 64)()
+    for j in range(picks):
+        k = int(pi[j])
+        d = imgs[order[k]].desc
+        c = min(int(pc[j] * d.ncomp), d.ncomp - 1)
+        b = min(int(pb[j] * d.nblocks(c)), d.nblocks(c) - 1)
+        assert L.lep_gpu_memcpy_d2h(g, blk, dec_descs[k].blocks[c] + 128 * b, 128) == 0
+        coef[j] = np.frombuffer(blk, dtype=np.int16)
+    np.save(os.path.join(out_dir, "decode_coefficients_sample.npy"), coef)
+    log("[bench] outputs of the last step written to %s: %d streams (%d sampled bytes each), %d distinct frames, %d sampled blocks"
+        % (out_dir, nseg, per, ndist, picks))
+
+
 class HipDevice:
     """the MI355X behind the C ABI (lepton_amd/liblepton_mi355x.so): device-resident encode / decode steps and the
     host-memory pipeline.  tests/bench_stub.py offers the same three methods without a GPU (LEP_BENCH_DEVICE=stub) so that
@@ -303,10 +370,12 @@ class HipDevice:
             self.L.lep_gpu_trim(self.g)
         return pipeline_figure(self.codec, jpgs, label, verify=verify, threads=self.host_threads)
 
-    def resident(self, uniq, images, steps, warmup, barrier, check_parity=True, with_latency=False, latency_sizes=(1, 8, 64), latency_repeats=3, whole_file=True):
+    def resident(self, uniq, images, steps, warmup, barrier, check_parity=True, with_latency=False, latency_sizes=(1, 8, 64), latency_repeats=3, whole_file=True,
+                 verify=True, dump_dir=None):
         """`images` 4K frames (the `uniq` distinct ones replicated device-to-device) and their streams resident in HBM;
         `warmup` + `steps` encode + decode launches; returns counters, kernel times (HIP events on the launch stream) and the
-        parity verdict (every segment's exit code, decode(encode(x)) == x, streams == oracle for every distinct image)."""
+        parity verdict (every segment's exit code; with `verify` also decode(encode(x)) == x, and with `check_parity` streams ==
+        oracle, for every distinct image).  `dump_dir`: the last step's outputs are written there (dump_resident_outputs)."""
         from lepton_amd import abi
         from lepton_amd.codec import JpegImage
 
@@ -319,12 +388,14 @@ class HipDevice:
         nimg = len(order)
         allocs = []
         try:
-            return self._resident(L, g, codec, uniq, imgs, plans, order, nuniq, jpeg_bytes, nimg, allocs, steps, warmup, barrier, check_parity, with_latency, latency_sizes, latency_repeats, whole_file)
+            return self._resident(L, g, codec, uniq, imgs, plans, order, nuniq, jpeg_bytes, nimg, allocs, steps, warmup, barrier, check_parity, with_latency, latency_sizes, latency_repeats, whole_file,
+                                  verify=verify, dump_dir=dump_dir)
         finally:
             for a in allocs:   # the resident frames are no longer needed (or could not all be had); what follows wants the memory
                 L.lep_gpu_free(g, a)
 
-    def _resident(self, L, g, codec, uniq, imgs, plans, order, nuniq, jpeg_bytes, nimg, allocs, steps, warmup, barrier, check_parity, with_latency, latency_sizes=(1, 8, 64), latency_repeats=3, whole_file=True):
+    def _resident(self, L, g, codec, uniq, imgs, plans, order, nuniq, jpeg_bytes, nimg, allocs, steps, warmup, barrier, check_parity, with_latency, latency_sizes=(1, 8, 64), latency_repeats=3, whole_file=True,
+                  verify=True, dump_dir=None):
         from lepton_amd import abi
 
         def dmalloc(n):
@@ -413,18 +484,21 @@ class HipDevice:
         L.lep_gpu_memcpy_d2h(g, lens, d_len, 4 * nseg)
         assert not any(status), "segment exit codes: %s" % sorted(set(status))
         stream_bytes = sum(lens)
+        if dump_dir:
+            dump_resident_outputs(L, g, dump_dir, imgs, order, dec_descs, d_streams, offs, lens, status)
         import hashlib
         nchk = min(nimg, nuniq)
-        for k in range(nchk):
+        parity = "segment exit codes only (--full checks the exact round trip and the streams against the oracle)"
+        for k in range(nchk if verify else 0):
             d = imgs[order[k]].desc
             for c in range(d.ncomp):
                 n = d.nblocks(c) * 128
                 buf = C.create_string_buffer(n)
                 L.lep_gpu_memcpy_d2h(g, buf, dec_descs[k].blocks[c], n)
                 assert hashlib.md5(buf.raw).digest() == hashlib.md5(C.string_at(d.blocks[c], n)).digest(), "decode(encode(x)) != x"
-        parity = "exact round trip(all %d distinct images)" % nchk
+            parity = "exact round trip(all %d distinct images)" % nchk
         bins_per_image = None
-        if check_parity:
+        if check_parity and verify:
             try:
                 import oracle_binding as ob
                 from concurrent.futures import ThreadPoolExecutor
@@ -583,7 +657,16 @@ def main():
     ap.add_argument("--mixed-images", type=int, default=-1, help="size of the mixed 1080p / 4K corpus of the strong-scaling figure (0 = skip; default: 10000 -- BASELINE.json configs[3] -- from 8 ranks on, 1024 below)")
     ap.add_argument("--mixed-distinct", type=int, default=-1, help="distinct files in the mixed corpus (default: as many as the ranks' host CPUs generate in about a minute: all of them at 8 ranks x 16+ CPUs, 32 on a small host)")
     ap.add_argument("--mixed-shapes", default="1920x1080,3840x2160", help="the two image sizes of the mixed corpus (tests use small ones)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: parity with the oracle and the exact round trip checked, latency table, end to end, "
+                         "mixed corpus, skewed corpus, extras, CPU baseline (the --no-* options above trim this run); without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, seeded samples "
+                         "of the larger arrays, well under 64 MB in all; rank 0 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:   # started by hand: be the launcher
         sys.exit(spawn_ranks(args.gpus))
@@ -604,8 +687,14 @@ def main():
         else:
             torch.cuda.set_device(local_rank)
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    if rank == 0 and not stub:
-        ge.build()
+    if not stub:
+        # the library build() made, as it is: the benchmark compiles nothing and writes nothing into the tree (which may be
+        # read-only to it); a missing library or one built from other sources is an error here, before anything is measured
+        if not os.path.exists(ge.LIB) and not os.environ.get("LEP_LIB_PATH"):
+            raise RuntimeError("%s is missing: run __graft_entry__.build() first" % ge.LIB)
+        ok, said = ge.library_matches_sources()
+        if not ok and not os.environ.get("LEP_LIB_PATH"):
+            raise RuntimeError("the loaded library (%s) was not built from the sources beside it (src %s): run __graft_entry__.build()" % (said, ge.source_sha16()))
     if dist:
         dist.barrier()
     if stub:
@@ -627,9 +716,11 @@ def main():
     t0 = time.perf_counter()
     nuniq = max(1, min(args.unique, args.images))
     seeds = shard.weak_seeds(nuniq, rank, 20001)
-    uniq = corpus.make_corpus(nuniq, args.width, args.height, seeds[0])
+    # (one generating process per CPU this rank may use: the box's CPU count can be many times that)
+    uniq = corpus.make_corpus(nuniq, args.width, args.height, seeds[0], workers=min(nuniq, max(1, usable_cpus() // max(1, world)), 32))
     log("[rank %d] corpus: %d unique %dx%d JPEGs in %.1fs" % (rank, nuniq, args.width, args.height, time.perf_counter() - t0))
-    res = dev.resident(uniq, args.images, args.steps, args.warmup, barrier, with_latency=(world == 1 and not args.no_extras))
+    res = dev.resident(uniq, args.images, args.steps, args.warmup, barrier, check_parity=args.full, with_latency=(args.full and world == 1 and not args.no_extras),
+                       verify=args.full, dump_dir=(args.dump_outputs if rank == 0 else None))
     names, parity, latency, bins_per_image = res["names"], res["parity"], res["latency"], res["bins_per_image"]
     log("[rank %d] resident steps done (%.1fs)" % (rank, time.perf_counter() - t0))
 
@@ -638,7 +729,7 @@ def main():
     mixed_local = {"mixed_bytes": 0.0, "mixed_files": 0.0, "mixed_c_s_max": 0.0, "mixed_d_s_max": 0.0, "mixed_generated": 0.0}
     mixed_err = None
     mixed_runs = {}
-    mixed_n = args.mixed_images if args.mixed_images >= 0 else (10000 if world >= 8 else 1024)
+    mixed_n = 0 if not args.full else args.mixed_images if args.mixed_images >= 0 else (10000 if world >= 8 else 1024)
     cpus_per_rank = max(1, usable_cpus() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", world))))
     # a 4K file takes a core ~1.5 s to synthesise, a 1080p one ~0.4 s: what a rank's cores make in about a minute
     mixed_distinct = args.mixed_distinct if args.mixed_distinct > 0 else (mixed_n if cpus_per_rank * world * 60 >= mixed_n else 32)
@@ -666,7 +757,7 @@ def main():
     # the mirror image).  Every rank runs it on its own files; rank 0 reports the aggregate.
     e2e = None
     e2e_local = {"e2e_bytes": 0.0, "e2e_c_s_max": 0.0, "e2e_d_s_max": 0.0}
-    if not args.no_end_to_end:
+    if args.full and not args.no_end_to_end:
         try:
             n_e2e = args.e2e_images if world == 1 else min(args.e2e_images, 1024)
             e2e = dev.pipeline([uniq[i % nuniq] for i in range(n_e2e)],
@@ -680,7 +771,8 @@ def main():
              "ranks": 1}
     local.update(e2e_local)
     local.update(mixed_local)
-    agg = shard.aggregate(local, backend_device=("cuda:%d" % local_rank) if (dist and not stub) else None)
+    # (one process: the counters are the line's as they are -- shard.aggregate would import torch for nothing)
+    agg = shard.aggregate(local, backend_device=("cuda:%d" % local_rank) if (dist and not stub) else None) if dist else {k: float(v) for k, v in local.items()}
     # per rank, for reading a multi-GPU run without a second visit: the host side of each rank (threads, CPUs, pinned staging, NUMA
     # placement) next to what it took of the wall clock -- the same counters the sums / maxima above were made of
     mine_rec = dict(dev.footprint(), **dev.identity(), world_size_seen=(dist.get_world_size() if dist else 1),
@@ -790,7 +882,7 @@ def main():
                 "note": "JPEG Huffman decode / re-encode on the GPU, host only splits files and writes containers; lep bytes == reference for the fixtures (tests)"})
     if latency:
         out["latency"] = latency
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # The companion headline: the SAME device-resident step over a photograph-like corpus (detail
         # growing from top to bottom: thread segments of equal compressed size then differ several-fold in blocks) -- the
         # replicated, evenly cut corpus above flatters the schedule
@@ -831,7 +923,7 @@ def main():
         except Exception as e:
             extras["reference_benchmark_file"] = {"error": repr(e)[:300]}
         out["extra"] = extras
-    if world == 1 and not args.no_cpu_baseline and not stub:
+    if args.full and world == 1 and not args.no_cpu_baseline and not stub:
         cb = cpu_baseline(uniq)
         if cb:
             try:   # the same file through the reference binary, for the `lepton -benchmark` row

@@ -26,7 +26,7 @@ if [ "${PMC_FIRST:-0}" = 1 ]; then   # the bench line then quotes the table of i
   pmc_passes; cp $OUT/pmc_traffic.json profiles/pmc_traffic.json
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  timeout 1500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$? ($(( $(date +%s)-t0 )) s)"
+  timeout 1500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$? ($(( $(date +%s)-t0 )) s)"
   ARGS="--steps 3 --warmup 1 --no-extras --no-end-to-end --no-cpu-baseline --mixed-images 0"
   timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o b --output-format csv -- python bench.py $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err; echo "rocprof rc=$? ($(( $(date +%s)-t0 )) s)"
   for f in $(find $OUT/prof -name "*kernel_stats.csv"); do cp $f $OUT/rocprofv3_kernel_stats.csv; done

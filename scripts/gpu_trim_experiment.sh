@@ -10,8 +10,8 @@ for V in 1; do
   LEP_VMM=$V timeout 600 python scripts/trim_cliff.py > $OUT/trim_vmm$V.json 2> $OUT/trim_vmm$V.err; echo "trim vmm=$V rc=$? ($(( $(date +%s)-t0 )) s)"; cat $OUT/trim_vmm$V.json
 done
 B="python bench.py --steps 2 --warmup 1 --unique 16 --no-extras --no-end-to-end --no-cpu-baseline --mixed-images 0"
-timeout 1500 python bench.py --trim-between-phases --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_trim.json 2> $OUT/bench_trim.err; echo "bench with trims rc=$? ($(( $(date +%s)-t0 )) s)"
-timeout 1500 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_notrim.json 2> $OUT/bench_notrim.err; echo "bench without rc=$? ($(( $(date +%s)-t0 )) s)"
+timeout 1500 python bench.py --full --trim-between-phases --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_trim.json 2> $OUT/bench_trim.err; echo "bench with trims rc=$? ($(( $(date +%s)-t0 )) s)"
+timeout 1500 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_notrim.json 2> $OUT/bench_notrim.err; echo "bench without rc=$? ($(( $(date +%s)-t0 )) s)"
 python - <<PY
 import json
 for n in ("trim", "notrim"):

@@ -30,14 +30,19 @@ class StubDevice:
         # (a made-up PCI address per rank: the plumbing that carries it is what the CPU suite exercises)
         return {"pci_domain": 0, "pci_bus": 0x10 + self.local_rank, "pci_device": 0, "pci_function": 0, "xgmi_hive_hi": 0, "xgmi_hive_lo": 0x1234}
 
-    def resident(self, uniq, images, steps, warmup, barrier, check_parity=True, with_latency=False):
+    def resident(self, uniq, images, steps, warmup, barrier, check_parity=True, with_latency=False, verify=True, dump_dir=None):
         nb = sum(len(uniq[i % len(uniq)]) for i in range(images))
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
             time.sleep(nb / 50e6)
         barrier()
-        self._note("resident", images=images, bytes=nb)
+        self._note("resident", images=images, bytes=nb, steps=steps, warmup=warmup, verify=verify, check_parity=check_parity, with_latency=with_latency)
+        if dump_dir:   # (nothing was coded: the bytes of the files it was handed stand in for outputs)
+            import numpy as np
+
+            os.makedirs(dump_dir, exist_ok=True)
+            np.save(os.path.join(dump_dir, "stub_image_bytes.npy"), np.array([len(uniq[i % len(uniq)]) for i in range(images)], dtype=np.float64))
         return {"jpeg_bytes": nb, "images": images, "segments": images, "blocks": nb // 16, "stream_bytes": nb * 3 // 4,
                 "elapsed": time.perf_counter() - t0, "enc_ms": steps * nb / 50e6 * 400, "dec_ms": steps * nb / 50e6 * 600,
                 "names": {"encode": "stub_encode", "decode": "stub_decode"}, "parity": "stub: nothing was coded",

@@ -10,14 +10,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(tmp_path, extra, env_extra=None):
+def run_bench(tmp_path, extra, env_extra=None, full=True):
+    """full: the mixed corpus and the end-to-end figure these tests look at are measured with --full only"""
     log = str(tmp_path / "stub")
     env = dict(os.environ, LEP_BENCH_DEVICE="stub", LEP_BENCH_STUB_LOG=log, PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env.update(env_extra or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--images", "6", "--unique", "2", "--width", "160",
-           "--height", "120", "--mixed-images", "12", "--mixed-shapes", "96x64,320x240", "--e2e-images", "4", "--no-extras", "--no-cpu-baseline"] + extra
+           "--height", "120", "--mixed-images", "12", "--mixed-shapes", "96x64,320x240", "--e2e-images", "4", "--no-extras", "--no-cpu-baseline"] + (["--full"] if full else []) + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -60,6 +61,28 @@ def test_one_rank_runs_the_same_corpus_alone(tmp_path):
     assert out["n_gpus"] == 1 and out["mixed"]["files"] == 12 and out["mixed"]["n_gpus"] == 1
     assert len(out["per_rank"]) == 1 and out["per_rank"][0]["mixed_files"] == 12
     assert [n["rank"] for n in notes if n["what"] == "resident"] == [0]
+
+
+def test_a_plain_run_times_its_steps_and_nothing_else(tmp_path):
+    """without --full a run sets up, warms up, times --steps steps, writes the outputs --dump-outputs asks for and prints the line:
+    no mixed corpus, no end to end, no round-trip or oracle check, no latency table"""
+    dump = tmp_path / "outputs"
+    out, notes = run_bench(tmp_path, ["--steps", "5", "--warmup", "2", "--dump-outputs", str(dump)], full=False)
+    assert out["n_gpus"] == 1 and out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out) and out["unit"] == "MB/s" and out["higher_is_better"] is True
+    assert not {"mixed", "end_to_end", "latency", "value_skewed", "extra", "cpu_baseline"} & set(out)
+    res = [n for n in notes if n["what"] == "resident"]
+    assert len(res) == 1 and res[0]["steps"] == 5 and res[0]["warmup"] == 2
+    assert not (res[0]["verify"] or res[0]["check_parity"] or res[0]["with_latency"])
+    assert not [n for n in notes if n["what"] == "pipeline"]
+    import numpy as np
+
+    a = np.load(dump / "stub_image_bytes.npy")
+    assert a.dtype == np.float64 and a.shape == (6,)
+    (tmp_path / "full").mkdir()
+    out_full, notes_full = run_bench(tmp_path / "full", ["--steps", "5"], full=True)
+    assert "mixed" in out_full and "end_to_end" in out_full
+    assert [n["verify"] for n in notes_full if n["what"] == "resident"] == [True]
 
 
 def test_under_torchrun_the_ranks_are_the_launcher_s(tmp_path):

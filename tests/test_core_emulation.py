@@ -11,6 +11,34 @@ import oracle_binding as ob
 from conftest import ROOT, golden, golden_cases
 from lepton_amd.codec import JpegImage
 
+def _host_path(jpg, want_lep=None, restored=None):
+    """what the product does with a file a kernel leaves alone: the host parser + the oracle write the .lep (the reference's bytes, where
+    the fixture has them) and the host re-coder restores from it the file -- or, for a damaged one, what the reference restores"""
+    import hashlib
+    from lepton_amd.codec import LepFile
+
+    img = JpegImage(jpg)
+    streams, _ = ob.oracle_encode(img.desc, img.plan())
+    lep = img.write_lep(streams)
+    if want_lep is not None:
+        assert lep == want_lep, "the host path's .lep differs from the reference's"
+    f = LepFile(lep)
+    ob.oracle_decode(f.desc, f.segments, f.streams)
+    back = f.recode()
+    assert back == jpg if restored is None else hashlib.md5(back).hexdigest() == restored, "the host path does not restore the file"
+
+
+def _golden_lep(name):
+    """the reference's .lep of a named fixture (tests/golden, tests/golden/ref), None for a generated file"""
+    from conftest import GOLDEN, REF_GOLDEN
+
+    for d in (GOLDEN, REF_GOLDEN):
+        p = os.path.join(d, name + ".lep")
+        if os.path.exists(p):
+            return open(p, "rb").read()
+    return None
+
+
 EMU_SO = os.environ.get("LEP_EMU_SO") or os.path.join(ROOT, "tests", "emu", "libcore_emu.so")   # LEP_EMU_SO: sanitizer builds go elsewhere
 
 
@@ -267,8 +295,9 @@ def test_gpu_huffman_encoder_on_cpu_restores_the_jpeg(emu, name):
     segs = (abi.HuffSegment * abi.MAX_SEGMENTS)()
     nseg, ok = C.c_int(0), C.c_int(0)
     assert L.lep_file_recode_plan(f.handle, C.byref(img), segs, C.byref(nseg), C.byref(ok)) == 0
-    if not ok.value:
-        pytest.skip("not eligible for the GPU Huffman encoder (truncated file, legacy hand-offs, ...): host path only")
+    if not ok.value:   # not for the GPU Huffman encoder (truncated file, legacy hand-offs, ...): the host re-coder above is the product's path
+        assert nseg.value == 0
+        return
     outs = (abi.Bytes * nseg.value)()
     ends = (abi.HuffEnd * nseg.value)()
     keep = []
@@ -314,10 +343,12 @@ def test_lane_per_unit_huffman_encoder_equals_the_wave_per_segment_one(emu, name
     segs = (abi.HuffSegment * abi.MAX_SEGMENTS)()
     nseg, ok = C.c_int(0), C.c_int(0)
     assert L.lep_file_recode_plan(f.handle, C.byref(img), segs, C.byref(nseg), C.byref(ok)) == 0
-    if not ok.value:
-        pytest.skip("not eligible for the GPU Huffman encoder")
-    if any(img.trunc_bc[c] for c in range(4)):
-        pytest.skip("a file cut inside its scan: only the lane-per-unit kernels know the cut (test_..._restores_files_cut_inside_their_scan)")
+    if not ok.value:   # not for the GPU Huffman encoder: the host re-coder restores it
+        assert nseg.value == 0 and f.recode() == jpg
+        return
+    if any(img.trunc_bc[c] for c in range(4)):   # a file cut inside its scan: only the lane-per-unit kernels know the cut
+        assert f.recode() == jpg                  # (test_..._restores_files_cut_inside_their_scan); here the host re-coder's bytes
+        return
     taken = 0
     for i in range(nseg.value):
         for cap in (min(segs[i].out_cap, len(jpg) + 1024), 100):        # the segment's own bound, and one that cuts it short
@@ -379,12 +410,12 @@ def test_gpu_huffman_decoder_on_cpu_matches_host_parser(emu, name):
     ok = C.c_int(0)
     rc = L.lep_jpeg_open_gpu(jpg, len(jpg), C.byref(h), C.byref(img), C.byref(ok))
     assert rc == 0
-    if not ok.value:
+    if not ok.value or img.flags & 1:
+        # not for the GPU Huffman decoder (grey, multi-scan, ...), or a file cut inside its scan (the single-wave kernel reports it
+        # irregular, the lane-per-subsequence kernels decode it): the host parser's path must give the reference's .lep and restore it
         L.lep_jpeg_close(h)
-        pytest.skip("not eligible for the GPU Huffman decoder (grey, multi-scan, ...): host parser only")
-    if img.flags & 1:
-        L.lep_jpeg_close(h)
-        pytest.skip("a file cut inside its scan: the single-wave kernel reports it irregular, the lane-per-subsequence kernels decode it")
+        _host_path(jpg, _golden_lep(name))
+        return
     p, n = C.c_void_p(), C.c_size_t(0)
     L.lep_jpeg_scan_bytes(h, C.byref(p), C.byref(n))
     scan = C.create_string_buffer(C.string_at(p, n.value) + b"\0" * 64, n.value + 64)   # zero padded copy ("device" arena)
@@ -579,13 +610,13 @@ def test_lane_per_subsequence_huffman_decoder_equals_the_single_wave_one(emu, na
 
     jpg = _jpeg_for_huffman_tests(name)
     one = _huffdec_setup(jpg)
-    if one is None:
-        pytest.skip("not eligible for the GPU Huffman decoder")
+    if one is None or one[0].rsti or one[0].flags & 1:
+        # not for the GPU Huffman decoder; restart intervals (the single-wave kernel keeps these files); a file cut inside its scan (only
+        # the lane-per-subsequence kernels know the cut: test_..._on_files_cut_inside_their_scan) -- the host parser's path is the product's
+        if sub_bits == 1024:
+            _host_path(jpg, _golden_lep(name))
+        return
     img1, scan1, planes1, d = one
-    if img1.rsti:
-        pytest.skip("restart intervals: the single-wave kernel keeps these files")
-    if img1.flags & 1:
-        pytest.skip("a file cut inside its scan: only the lane-per-subsequence kernels know the cut (test_..._on_files_cut_inside_their_scan)")
     rows1 = (abi.HuffDecRow * (img1.mcuv + 1))()
     assert emu.emu_huffman_decode_image(C.byref(img1), rows1) == 0 and rows1[img1.mcuv].aux >> 8 == 0
     img2, scan2, planes2, _ = _huffdec_setup(jpg)
@@ -1723,9 +1754,10 @@ def test_lane_per_subsequence_huffman_decoder_on_files_cut_inside_their_scan(emu
     codes what it has (uncompressed_components.hh:166-185).  lep_huffdec_simt.h + parse_jpeg_finish_gpu must leave exactly the host
     parser's frame, hand-offs and truncation bounds -- the .lep written from them is the host parser's (== the reference's for the
     fixtures) -- or report a status and leave the file to the host parser; never a different result."""
-    res = _cut_file_through_the_lane_per_subsequence_decoder(emu, dict(_cut_jpegs())[name], bits)
-    if isinstance(res, str):
-        pytest.skip(res)
+    jpg = dict(_cut_jpegs())[name]
+    res = _cut_file_through_the_lane_per_subsequence_decoder(emu, jpg, bits)
+    if isinstance(res, str):   # the kernels left the file to the host parser: its path is the product's
+        _host_path(jpg, _golden_lep(name))
 
 
 def _cut_file_through_the_lane_per_subsequence_decoder(emu, jpg, bits, stale=None):
@@ -1832,8 +1864,9 @@ def test_lane_per_unit_huffman_encoder_restores_files_cut_inside_their_scan(emu,
     segs = (abi.HuffSegment * abi.MAX_SEGMENTS)()
     nseg, ok = C.c_int(0), C.c_int(0)
     assert L.lep_file_recode_plan(f.handle, C.byref(img), segs, C.byref(nseg), C.byref(ok)) == 0
-    if not ok.value:
-        pytest.skip("not eligible for the GPU Huffman encoder (grey, restart intervals, ...)")
+    if not ok.value:   # not for the GPU Huffman encoder (grey, restart intervals, ...): the host re-coder above is the product's path
+        assert nseg.value == 0
+        return
     assert any(img.trunc_bc[c] for c in range(3)), "the plan does not know the file is cut"
     n = nseg.value
     bufs, arr, ends = [], (abi.Bytes * n)(), (abi.HuffEnd * n)()
@@ -1851,11 +1884,22 @@ def test_lane_per_unit_huffman_encoder_restores_files_cut_inside_their_scan(emu,
     rc = L.lep_file_recode_finish(f.handle, arr, ends, n, C.byref(out))
     if rc == 101:
         assert ends[n - 1].pad & 1 and ends[n - 1].attempted < segs[n - 1].out_cap
-        pytest.skip("the cut was met before the byte bound (LEP_GPU_PATH_DECLINED): the host re-coder's")
+        return   # the cut was met before the byte bound (LEP_GPU_PATH_DECLINED): the host re-coder's bytes, checked above
     assert rc == 0
     got = out.tobytes()
     L.lep_free(out.data)
     assert got == jpg
+
+
+REFUSED_RST = (42,)   # EX_UNSUPPORTED_JPEG: how the reference refuses a scan whose restart markers are not where its interval says
+
+
+def _restored_md5(name):
+    """md5 of what the reference restores from its .lep of a damaged fixture of tests/golden/ref (None: the file itself)"""
+    from conftest import ref_manifest
+
+    v = ref_manifest()["jpegs"].get(name)
+    return v["restored_md5"] if v and not v.get("restored_equals_input", True) else None
 
 
 def _restart_interval_jpegs():
@@ -1898,8 +1942,9 @@ def test_lane_per_unit_huffman_encoder_on_restart_intervals(emu, name):
     jpg = dict(_restart_interval_jpegs())[name]
     try:
         src = JpegImage(jpg)
-    except LeptonError:
-        pytest.skip("the reference refuses this file")
+    except LeptonError as e:   # the reference refuses this file: so does the host parser, with the reference's exit code
+        assert e.code in REFUSED_RST, (name, e.code)
+        return
     for nthreads in (1, 8):
         plan = src.plan(nthreads)
         streams, _ = ob.oracle_encode(src.desc, plan)
@@ -1911,8 +1956,10 @@ def test_lane_per_unit_huffman_encoder_on_restart_intervals(emu, name):
         segs = (abi.HuffSegment * abi.MAX_SEGMENTS)()
         nseg, ok = C.c_int(0), C.c_int(0)
         assert L.lep_file_recode_plan(f.handle, C.byref(img), segs, C.byref(nseg), C.byref(ok)) == 0
-        if not ok.value:
-            pytest.skip("not eligible for the GPU scan encoder (narrowrst.jpg: markers the file withheld)")
+        if not ok.value:   # not for the GPU scan encoder (narrowrst.jpg: markers the file withheld): the host re-coder's bytes
+            assert nseg.value == 0
+            _host_path(jpg, _golden_lep(name), _restored_md5(name))
+            continue
         assert img.rsti > 0
         for i in range(nseg.value):
             own = min(segs[i].out_cap, len(jpg) + 1024)
@@ -2063,9 +2110,11 @@ def test_lane_per_restart_interval_huffman_decoder(emu, name):
     if rc:
         assert host is None
         return
-    if not ok.value:
+    if not ok.value:   # not for the GPU scan decoder: the host parser's path is the product's
         L.lep_jpeg_close(h)
-        pytest.skip("not eligible for the GPU scan decoder")
+        assert host is not None
+        _host_path(jpg, _golden_lep(name), _restored_md5(name))
+        return
     assert img.rsti > 0
     damaged = name in ("rst_marker_dropped", "rst_marker_moved")
     if name == "rst_marker_dropped":
