@@ -225,14 +225,21 @@ int lep_gpu_huffman_decode_device(lep_gpu *g, const lep_huffdec_image *images, i
 /* The same for PROGRESSIVE files (replaces the progressive branches of decode_jpeg's scan loop, src/lepton/jpgcoder.cc:2975-3260,
  * with decode_dc_prg_*, decode_ac_prg_fs / _sa, decode_eobrun_sa, skip_eobrun :4968-5335, :5462-5500): one wavefront per
  * (image, scan) whose 64 lanes decode the codes that would start at the next 64 bits while the scalar unit hops from code to
- * code (lep_huffprogdec_win.h; scans with restart intervals: uniform vector code, lep_huffprogdec.h).  A refinement scan must see what the earlier scans of its band wrote, so every descriptor carries a
+ * code (lep_huffprogdec_win.h; scans with restart intervals: one wavefront per piece of consecutive intervals where the descriptor carries
+ * LEP_HUFFDEC_RST_TABLE, lep_huffprogdec_rst.h -- uniform vector code otherwise, lep_huffprogdec.h).  A refinement scan must see what the earlier scans of its band wrote, so every descriptor carries a
  * dependency `level`.  Up to 16384 scans go out as ONE launch, ordered by level, in which a scan waits -- MCU row by MCU row,
  * on a progress word the scans in front of it publish -- for the scans of its file (same frame pointers) whose component and
  * band meet its own: a file then takes as long as its longest scan instead of the sum over its levels.  Larger calls (or
  * LEP_HUFFPROG_PIPELINE=0) launch level after level on the stream.  Each scan writes its coefficients into the
  * zero-filled frame t.blocks, the first scan of a file also one record per MCU row at d_rows + t.rows_off, and every scan a
  * final record {bits consumed, last DC, pad bits | status << 8} at d_rows + result_off; a non-zero status anywhere sends the
- * whole file to the host parser.  lep_jpeg_open_gpu_progressive fills the descriptors. */
+ * whole file to the host parser.  lep_jpeg_open_gpu_progressive fills the descriptors.
+ * LEP_HUFFDEC_RST_TABLE in t.flags is the contract the sequential side has: a caller that passes a descriptor with the flag HAS PUT the
+ * scan's marker positions (lep_jpeg_scan_restarts_of: uint32 offsets into this scan's un-stuffed bytes) behind the scan's slot, at
+ * t.scan + LEP_HUFFPROGDEC_SCAN_ROOM(t.scan_len); a caller that has not put them there CLEARS the flag, and the scan goes to
+ * lep_huffprogdec.h.  The scans of a file with at least one such scan are launched level after level (none of them waits on a
+ * progress word); LEP_HUFFPROGDEC_RST=0 sends them to lep_huffprogdec.h whatever the flag says. */
+#define LEP_HUFFPROGDEC_SCAN_ROOM(scan_len) ((((size_t)(scan_len)) + 80 + 15) & ~(size_t)15)   /* a progressive scan's slot: bytes + zero padding, 16-byte multiple */
 typedef struct lep_huffprogdec_scan {
     lep_huffdec_image t;                 /* scan = this scan's bytes; lut[0..1] DC tables 0 / 1, lut[2] the scan's AC table */
     int32_t cmpc, cmp[4];
@@ -316,6 +323,10 @@ int lep_jpeg_scan_bytes(const lep_jpeg *j, const uint8_t **data, size_t *len);
 /* The restart markers of a file lep_jpeg_open_gpu flagged LEP_HUFFDEC_RST_TABLE: the offset in the un-stuffed scan bytes at which
  * each stood.  The caller puts them, as uint32, at scan + LEP_HUFFDEC_SCAN_ROOM(scan_len) on the device. */
 int lep_jpeg_scan_restarts(const lep_jpeg *j, const uint32_t **pos, size_t *count);
+/* The same for scan `scan_index` of the file (0 = the first; what lep_jpeg_open_gpu_progressive's descriptors are indexed by): offsets
+ * relative to THAT scan's first un-stuffed byte.  For a scan flagged LEP_HUFFDEC_RST_TABLE there are (units - 1) / rsti of them, units =
+ * MCUs of an interleaved scan, the component's nch x ncv blocks of a one-component scan. */
+int lep_jpeg_scan_restarts_of(const lep_jpeg *j, int scan_index, const uint32_t **pos, size_t *count);
 int lep_jpeg_finish_gpu(lep_jpeg *j, const lep_huffdec_row *rows);
 void lep_jpeg_close(lep_jpeg *j);
 int lep_jpeg_describe(const lep_jpeg *j, lep_image_desc *desc);          /* host pointers into j */

@@ -216,6 +216,8 @@ def lib():
         L.lep_gpu_huffman_progressive_encode_device.argtypes = [vp, P(HuffProgImage), C.c_int, P(HuffProgScan), C.c_int, vp, vp, vp, vp]
         L.lep_jpeg_open_gpu_progressive.argtypes = [vp, P(HuffProgDecScan), C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.lep_jpeg_finish_gpu_progressive.argtypes = [vp, P(HuffProgDecScan), C.c_int, P(HuffDecRow)]
+        if hasattr(L, "lep_jpeg_scan_restarts_of"):   # (absent from an older build named by LEP_LIB_PATH, which flags no progressive scan either)
+            L.lep_jpeg_scan_restarts_of.argtypes = [vp, C.c_int, P(P(C.c_uint32)), P(C.c_size_t)]   # marker positions of scan i (LEP_HUFFDEC_RST_TABLE)
         L.lep_gpu_huffman_progressive_decode_device.argtypes = [vp, P(HuffProgDecScan), C.c_int, vp, vp]
         L.lep_jpeg_plan_progressive_check.argtypes = [vp, C.c_size_t, P(HuffProgImage), P(HuffProgScan), P(C.c_uint32), P(C.c_uint32), C.c_int, P(C.c_int), P(C.c_int)]
         L.lep_file_consumed.argtypes = [vp]
@@ -246,6 +248,6 @@ EXPORTS = [
     "lep_serve_start", "lep_serve_get_stats", "lep_serve_stop", "lep_zlib0_wrap", "lep_jpeg_open_slice", "lep_compress_slice", "lep_jpeg_open_embedded", "lep_compress_embedded", "lep_gpu_use_arena", "lep_gpu_expect_company", "lep_gpu_settle_uploads", "lep_batch_plan", "lep_jpeg_set_encode_options", "lep_gpu_huffman_decode_simt_device",
     "lep_jpeg_check_restores", "lep_jpeg_gpu_scan_wait_timeouts", "lep_batch_debug_poison", "lep_jpeg_plan_handoffs", "lep_file_consumed", "lep_chained_file_follows", "lep_file_open_next",
     "lep_file_recode_plan_progressive", "lep_file_recode_finish_progressive", "lep_gpu_huffman_progressive_encode_device",
-    "lep_jpeg_open_gpu_progressive", "lep_jpeg_finish_gpu_progressive", "lep_gpu_huffman_progressive_decode_device",
+    "lep_jpeg_open_gpu_progressive", "lep_jpeg_finish_gpu_progressive", "lep_jpeg_scan_restarts_of", "lep_gpu_huffman_progressive_decode_device",
     "lep_jpeg_plan_progressive_check", "lep_gpu_last_stage_ms", "lep_jpeg_set_container_version", "lep_container_can_write_version", "lep_jpeg_plan_scan_check", "lep_jpeg_scan_file_range",
 ]

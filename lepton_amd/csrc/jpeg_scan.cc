@@ -328,6 +328,8 @@ static int split_file(const uint8_t* d, size_t n, JpegFile* jf) {
                 if (tmp == 0x00) { crst = 0; jf->scan.push_back(0xFF); }
                 else if (tmp == 0xD0 + (cpos & 7)) {
                     if (scnc == 0) jf->rst_pos.push_back((uint32_t)jf->scan.size());
+                    if (jf->scan_rst_pos.size() < jf->scan_start.size()) jf->scan_rst_pos.resize(jf->scan_start.size());
+                    jf->scan_rst_pos.back().push_back((uint32_t)jf->scan.size() - jf->scan_start.back());
                     ++cpos; ++crst;
                     if (jf->rst_cnt.size() <= (size_t)scnc) jf->rst_cnt.resize(scnc + 1, 0);
                     ++jf->rst_cnt[scnc];
@@ -1012,6 +1014,19 @@ int parse_jpeg_prepare_gpu_progressive(JpegFile* jf, std::vector<ProgScanDecodeP
             if (shares && e.from <= sc.to && sc.from <= e.to) level = std::max(level, e.level + 1);
         }
         sc.level = level;
+        // restart intervals: when the scan holds exactly the markers its length asks for -- one behind every rsti units (MCUs of an
+        // interleaved scan, the component's nch x ncv blocks otherwise) but the last run -- their positions travel behind the scan's slot
+        // and the scan is decoded interval by interval (lep_huffprogdec_rst.h); otherwise lep_huffprogdec.h walks it as the reference does
+        if (jf->rsti > 0) {
+            const Component& q = jf->comp[sc.cmp[0]];
+            const uint64_t units = sc.cmpc > 1 ? (uint64_t)jf->mcuc : (uint64_t)q.nch * (uint64_t)q.ncv;
+            const size_t want = units ? (size_t)((units - 1) / (uint64_t)jf->rsti) : 0;
+            static const std::vector<uint32_t> none;
+            const std::vector<uint32_t>& pos = k < jf->scan_rst_pos.size() ? jf->scan_rst_pos[k] : none;
+            bool ok = want > 0 && pos.size() == want && k < jf->rst_cnt.size() && jf->rst_cnt[k] == want && (k >= jf->rst_err.size() || jf->rst_err[k] == 0);
+            for (size_t i = 0; ok && i < want; ++i) ok = pos[i] <= t.scan_len && (i == 0 || pos[i] >= pos[i - 1]);
+            if (ok) t.flags |= kScanRstTable;
+        }
         sc.want_rows = k == 0 ? 1 : 0;
         t.rows_off = 0;
         sc.result_off = (uint64_t)(nrows + 1) + k;

@@ -188,6 +188,12 @@ int lep_jpeg_scan_restarts(const lep_jpeg* j, const uint32_t** pos, size_t* coun
     *pos = j->jf.rst_pos.data(); *count = j->jf.rst_pos.size();
     return 0;
 }
+int lep_jpeg_scan_restarts_of(const lep_jpeg* j, int scan_index, const uint32_t** pos, size_t* count) {
+    *pos = nullptr; *count = 0;
+    if (scan_index < 0 || (size_t)scan_index >= j->jf.scan_start.size()) return LEP_ASSERTION_FAILURE;
+    if ((size_t)scan_index < j->jf.scan_rst_pos.size()) { *pos = j->jf.scan_rst_pos[(size_t)scan_index].data(); *count = j->jf.scan_rst_pos[(size_t)scan_index].size(); }
+    return 0;
+}
 int lep_jpeg_finish_gpu(lep_jpeg* j, const lep_huffdec_row* rows) {
     return lep::parse_jpeg_finish_gpu(&j->jf, reinterpret_cast<const lep::ScanDecodeRow*>(rows)) ? LEP_UNSUPPORTED_JPEG : 0;
 }

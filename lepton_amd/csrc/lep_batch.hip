@@ -553,7 +553,15 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
         std::vector<std::vector<size_t>> pscan_off(nl);   // progressive: every scan in its own aligned, zero-padded slot
         int nprog = 0;
         for (int k = 0; k < nl; ++k) if (on_prog[k]) {
-            for (const lep_huffprogdec_scan& sc : pscans[k]) { pscan_off[k].push_back(scan_total); scan_total += ((size_t)sc.t.scan_len + 80 + 15) & ~(size_t)15; }
+            for (size_t q = 0; q < pscans[k].size(); ++q) {
+                const lep_huffprogdec_scan& sc = pscans[k][q];
+                pscan_off[k].push_back(scan_total); scan_total += LEP_HUFFPROGDEC_SCAN_ROOM(sc.t.scan_len);
+                if (sc.t.flags & LEP_HUFFDEC_RST_TABLE) {   // the restart positions behind the scan's slot (lep_huffprogdec_rst.h)
+                    const uint32_t* rp = nullptr; size_t rn = 0;
+                    lep_jpeg_scan_restarts_of(parsed[c->live[k]], (int)q, &rp, &rn);
+                    scan_total += (rn * 4 + 15) & ~(size_t)15;
+                }
+            }
             row_off[k] = rows_total; rows_total += (size_t)prow_need[k];
             ++nprog;
         }
@@ -585,9 +593,14 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                 lep_jpeg_scan_bytes(parsed[c->live[k]], &p, &len);
                 if (on_prog[k]) {
                     for (size_t q = 0; q < pscans[k].size(); ++q) {
-                        const size_t off = (size_t)(uintptr_t)pscans[k][q].t.scan, n = pscans[k][q].t.scan_len, room = ((n + 80 + 15) & ~(size_t)15);
+                        const size_t off = (size_t)(uintptr_t)pscans[k][q].t.scan, n = pscans[k][q].t.scan_len, room = LEP_HUFFPROGDEC_SCAN_ROOM(n);
                         memcpy(s->h_scan + pscan_off[k][q], p + off, n);
                         memset(s->h_scan + pscan_off[k][q] + n, 0, room - n);
+                        if (pscans[k][q].t.flags & LEP_HUFFDEC_RST_TABLE) {
+                            const uint32_t* rp = nullptr; size_t rn = 0;
+                            lep_jpeg_scan_restarts_of(parsed[c->live[k]], (int)q, &rp, &rn);
+                            memcpy(s->h_scan + pscan_off[k][q] + room, rp, rn * 4);
+                        }
                     }
                     for (size_t q = 0; q < praw_off[k].size(); ++q)
                         memcpy(s->h_scan + praw_off[k][q], jpgs[c->live[k]].data + pchk[k].first[q], pchk[k].len[q]);
@@ -678,6 +691,34 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                 }
                 if (!again.empty()) {
                     if (int rc = lep_gpu_huffman_decode_device(g, again.data(), (int)again.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc;
+                    HIPOK(hipMemcpyAsync(rows.data(), s->d_rows, rows_total * sizeof(lep_huffdec_row), hipMemcpyDeviceToHost, s_huff));
+                    HIPOK(hipStreamSynchronize(s_huff));
+                }
+            }
+            // A progressive file in which a scan decoded interval by interval (lep_huffprogdec_rst.h) ended with a status gets a second chance
+            // with the older forms before the host parser is bothered, its frame wiped first: an interval of a damaged file that does not end
+            // at its marker is something the reference, which never looks at where the markers stood, may still decode.
+            {
+                std::vector<lep_huffprogdec_scan> again;
+                for (int k = 0; k < nl; ++k) if (on_prog[k]) {
+                    bool bad = false;
+                    for (size_t q = 0; q < pscans[k].size(); ++q) {
+                        const lep_huffprogdec_scan& sc = plaunch[pfirst_desc[k] + q];
+                        bad = bad || ((sc.t.flags & LEP_HUFFDEC_RST_TABLE) && (rows[sc.result_off].aux >> 8) != 0);
+                    }
+                    if (!bad) continue;
+                    size_t fb = 0;
+                    const lep_huffprogdec_scan& f = plaunch[pfirst_desc[k]];
+                    for (int cc = 0; cc < f.t.ncomp; ++cc) fb += (size_t)f.t.bch[cc] * f.bcv[cc] * 128;
+                    HIPOK(hipMemsetAsync(s->d_frames + c->frame_off[k], 0, fb, s_huff));
+                    for (size_t q = 0; q < pscans[k].size(); ++q) {
+                        lep_huffprogdec_scan& sc = plaunch[pfirst_desc[k] + q];
+                        sc.t.flags &= ~LEP_HUFFDEC_RST_TABLE;      // (the contract of the flag: cleared, the scan goes to lep_huffprogdec.h)
+                        again.push_back(sc);
+                    }
+                }
+                if (!again.empty()) {
+                    if (int rc = lep_gpu_huffman_progressive_decode_device(g, again.data(), (int)again.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc;
                     HIPOK(hipMemcpyAsync(rows.data(), s->d_rows, rows_total * sizeof(lep_huffdec_row), hipMemcpyDeviceToHost, s_huff));
                     HIPOK(hipStreamSynchronize(s_huff));
                 }

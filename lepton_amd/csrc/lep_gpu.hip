@@ -29,6 +29,7 @@
 #include "lep_huffprog_simt.h"
 #include "lep_huffprogdec.h"
 #include "lep_huffprogdec_win.h"
+#include "lep_huffprogdec_rst.h"
 
 using namespace lepdev;
 
@@ -405,6 +406,30 @@ __global__ __launch_bounds__(64, 2) void lep_huffprogdec_win_pipelined_kernel(co
     if (sc->pad & lephuff::kProgDecWin) { lephuff::ProgWinWave w; w.run_scan_win<true>(sc, &ws, rows, deps + k, progress, k); }
     else { lephuff::ProgDecWave w; w.run_scan<true>(sc, &sh, rows, deps + k, progress, k); }
 }
+// scans with restart intervals whose marker positions lie behind their slot (lep_huffprogdec_rst.h): one wavefront per PIECE -- a run of
+// consecutive intervals -- of the scans of one dependency level; then one wavefront per scan makes its final record of what the pieces left.
+// (The window form's registers and LDS: 8 KB of tables and ring per wavefront.  Unlike that form's launches these are thousands of
+// wavefronts per file: four to a SIMD.)
+__global__ __launch_bounds__(64, 4) void lep_huffprogdec_rst_kernel(const lephuff::ProgDecScan* __restrict__ scans, const lephuff::ProgRstScan* __restrict__ plans, int nscan,
+                                                                   lephuff::ProgRstOut* outs, lephuff::HuffDecRow* rows) {
+    __shared__ lephuff::ProgWinShared ws;
+    // the piece's scan: the last one of the launch whose first piece is not behind it
+    const uint32_t piece = plans[0].piece0 + blockIdx.x;
+    int lo = 0, hi = nscan - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (plans[mid].piece0 <= piece) lo = mid; else hi = mid - 1;
+    }
+    const lephuff::ProgRstScan pl = plans[lo];
+    const uint32_t first = (piece - pl.piece0) * pl.ipp;
+    if (piece - pl.piece0 >= pl.npieces || first >= pl.nint) return;
+    lephuff::ProgRstWave w;
+    w.run_piece(scans + lo, &ws, rows, pl.nint, first, pl.nint - first < pl.ipp ? pl.nint - first : pl.ipp, outs + piece);
+}
+__global__ __launch_bounds__(64) void lep_huffprogdec_rst_reduce_kernel(const lephuff::ProgDecScan* __restrict__ scans, const lephuff::ProgRstScan* __restrict__ plans,
+                                                                       const lephuff::ProgRstOut* outs, lephuff::HuffDecRow* rows) {
+    lephuff::prog_rst_reduce(scans + blockIdx.x, plans + blockIdx.x, outs, rows);
+}
 // ... all levels in ONE launch: a scan waits, MCU row by MCU row, for the scans of its file it follows (lep_huffprogdec.h ProgDeps)
 // (128 VGPRs: at 64 the waiting code's spills trip a register-pair alignment check in this compiler's backend; a launch of this
 // kind is small, what it needs is a short chain)
@@ -482,6 +507,8 @@ struct lep_gpu {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr;
     int huffprog_pipeline = 1;          // LEP_HUFFPROG_PIPELINE=0: progressive scan decode level by level, whatever the launch size
     int huffprog_split = 0;             // LEP_HUFFPROG_SPLIT=1: level-by-level launches split by kind of scan (measurement aid)
+    int huffprogdec_rst = 1;            // LEP_HUFFPROGDEC_RST=0: scans with restart intervals decoded by lep_huffprogdec.h whatever their descriptors carry
+    uint32_t huffprogdec_rst_floor = lephuff::kRstPieceFloor;   // LEP_HUFFPROGDEC_RST_FLOOR: bytes of scan per piece (measurements)
     int huffprogdec_win = 1;            // LEP_HUFFPROGDEC_WIN=0: progressive scans decoded by lep_huffprogdec.h's uniform vector code only
     int huffprog_simt = 1;              // LEP_HUFFPROG_SIMT=0: every progressive scan's bytes from the wavefront-per-scan kernel (lep_huffprog.h)
     void* d_huffseq[2] = {nullptr, nullptr}; size_t huffseq_bytes[2] = {0, 0};             // scans of sequential frames in a progressive launch: which / caps / byte counts / end states
@@ -570,6 +597,7 @@ struct lep_gpu {
     void* h_huffprog[2] = {nullptr, nullptr}; size_t h_huffprog_bytes[2] = {0, 0};   // pinned staging of the same: the upload does not wait for the stream
     int huffprog_turn = 0;   // the two sets are used in turn: at most two launches are ever in flight (lep_batch.hip queues chunk k+1 before it fetches chunk k)
     void* d_huffprogdec = nullptr; size_t huffprogdec_bytes = 0;   // ProgDecScan[]
+    void* d_huffprogrst = nullptr; size_t huffprogrst_bytes = 0;   // files with scans of lep_huffprogdec_rst.h: ProgDecScan[], ProgRstScan[], ProgRstOut[]
     void* d_huffdec = nullptr; size_t huffdec_bytes = 0;   // HuffDecImage[]
     void* d_huffpar = nullptr; size_t huffpar_bytes = 0;   // the lane-per-subsequence scan decoder's records (SimtImage | SimtWave | SimtSub x 2 | SimtPlace)
     void* d_scan = nullptr; size_t scan_bytes = 0;      // scan bytes of the Huffman encoder (host variant)
@@ -1036,6 +1064,8 @@ int lep_gpu_create(int device, lep_gpu** out) {
     if (const char* e = getenv("LEP_HUFFENC_SIMT")) g->huffenc_simt = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROG_SIMT")) g->huffprog_simt = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_WIN")) g->huffprogdec_win = atoi(e) != 0;
+    if (const char* e = getenv("LEP_HUFFPROGDEC_RST")) g->huffprogdec_rst = atoi(e) != 0;
+    if (const char* e = getenv("LEP_HUFFPROGDEC_RST_FLOOR")) g->huffprogdec_rst_floor = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("LEP_HUFFPROG_SPLIT")) g->huffprog_split = atoi(e) != 0;
     if (const char* e = getenv("LEP_ENC5_WAVES")) g->enc5_waves = atoi(e) == 1 ? 1 : 2;
     if (const char* e = getenv("LEP_ENC5_FOLD_APART")) g->enc5_fold_apart = atoi(e);
@@ -1074,7 +1104,7 @@ static void release_device_side(lep_gpu* g) {
     if (g->stream2) (void)hipStreamDestroy(g->stream2);
     if (g->stream3) (void)hipStreamDestroy(g->stream3);
     for (void** p : {&g->arena[0].d_models, &g->arena[0].d_ns, &g->arena[0].d_meta, &g->arena[1].d_models, &g->arena[1].d_ns, &g->arena[1].d_meta, &g->d_blocks, &g->d_streams, &g->d_lens, &g->d_huff[0], &g->d_huff[1],
-                     &g->d_huffprog[0], &g->d_huffprog[1], &g->d_huffprogsimt[0], &g->d_huffprogsimt[1], &g->d_huffseq[0], &g->d_huffseq[1], &g->d_huffprogdec, &g->d_huffdec, &g->d_huffpar, &g->d_huffenc[0], &g->d_huffenc[1], &g->d_scan, &g->d_scanlen})
+                     &g->d_huffprog[0], &g->d_huffprog[1], &g->d_huffprogsimt[0], &g->d_huffprogsimt[1], &g->d_huffseq[0], &g->d_huffseq[1], &g->d_huffprogdec, &g->d_huffprogrst, &g->d_huffdec, &g->d_huffpar, &g->d_huffenc[0], &g->d_huffenc[1], &g->d_scan, &g->d_scanlen})
         dev_release(g, p, nullptr);
     vmm_destroy(g);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
@@ -1192,6 +1222,9 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
 
 static_assert(sizeof(lep_huffprogdec_scan) == sizeof(lephuff::ProgDecScan), "C ABI mirrors");
 
+static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* d_rows, hipStream_t st);
+static int progdec_launch_by_level(lep_gpu* g, const std::vector<lep_huffprogdec_scan>& scans, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here);
+
 int lep_gpu_huffman_progressive_decode_device(lep_gpu* g, const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* d_rows, void* hip_stream) {
     if (!g) return LEP_GPU_ERROR;
     if (nscan <= 0) return 0;
@@ -1221,6 +1254,88 @@ int lep_gpu_huffman_progressive_decode_device(lep_gpu* g, const lep_huffprogdec_
             scans = progressive_only.data(); nscan = (int)progressive_only.size();
         }
     }
+    // Scans of the new form for restart intervals (lep_huffprogdec_rst.h; the caller has put the marker positions behind their slots): a file
+    // with at least one of them goes level by level as a whole, every level of it many wavefronts per scan -- none of its scans waits on a
+    // progress word.  Files without such scans keep the launches below exactly as they were.
+    for (int i = 0; i < nscan; ++i) if (scans[i].level < 0 || scans[i].level > 63) return LEP_ASSERTION_FAILURE;
+    std::vector<lep_huffprogdec_scan> others, by_level;
+    if (g->huffprogdec_rst) {
+        std::vector<const void*> frames;
+        for (int i = 0; i < nscan; ++i)
+            if (lephuff::prog_rst_takes(reinterpret_cast<const lephuff::ProgDecScan&>(scans[i]))) frames.push_back((const void*)scans[i].t.blocks[0]);
+        if (!frames.empty()) {
+            std::sort(frames.begin(), frames.end());
+            for (int i = 0; i < nscan; ++i)
+                (std::binary_search(frames.begin(), frames.end(), (const void*)scans[i].t.blocks[0]) ? by_level : others).push_back(scans[i]);
+        }
+    }
+    if (by_level.empty()) return progdec_launch_scans(g, scans, nscan, d_rows, st);
+    if (!others.empty()) { if (int rc = progdec_launch_scans(g, others.data(), (int)others.size(), d_rows, st)) return rc; }
+    return progdec_launch_by_level(g, by_level, d_rows, st, others.empty());
+}
+
+// the scans of files that have a scan of lep_huffprogdec_rst.h's: dependency level after dependency level on the stream -- the pieces of
+// the scans of that form, one launch of the window form's level-by-level kernel for the others -- and the reduce step behind the last
+static int progdec_launch_by_level(lep_gpu* g, const std::vector<lep_huffprogdec_scan>& scans, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here) {
+    std::vector<lep_huffprogdec_scan> plain, rst;
+    std::vector<lephuff::ProgRstScan> plans;
+    std::vector<int> pcut, rcut;
+    uint32_t pieces = 0;
+    bool any_win = false;
+    for (int lv = 0; lv < 64; ++lv) {
+        pcut.push_back((int)plain.size()); rcut.push_back((int)rst.size());
+        for (const lep_huffprogdec_scan& in : scans) {
+            if (in.level != lv) continue;
+            lep_huffprogdec_scan sc = in;
+            const lephuff::ProgDecScan& d = reinterpret_cast<const lephuff::ProgDecScan&>(sc);
+            if (lephuff::prog_rst_takes(d)) {
+                const lephuff::ProgRstScan pl = lephuff::prog_rst_plan(d, g->huffprogdec_rst_floor, pieces);
+                if (pl.npieces > 0x7fffffffu - pieces) return LEP_ASSERTION_FAILURE;
+                pieces += pl.npieces;
+                sc.pad = lephuff::kProgDecRst;
+                rst.push_back(sc); plans.push_back(pl);
+            } else {
+                const bool w = g->huffprogdec_win && lephuff::prog_win_takes(d);
+                sc.pad = w ? lephuff::kProgDecWin : 0;
+                any_win = any_win || w;
+                plain.push_back(sc);
+            }
+        }
+    }
+    pcut.push_back((int)plain.size()); rcut.push_back((int)rst.size());
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t o_rst = up(plain.size() * sizeof(lep_huffprogdec_scan)), o_plan = o_rst + up(rst.size() * sizeof(lep_huffprogdec_scan)),
+                 o_out = o_plan + up(plans.size() * sizeof(lephuff::ProgRstScan)), total = o_out + up((size_t)pieces * sizeof(lephuff::ProgRstOut));
+    if (int rc = ensure(g, &g->d_huffprogrst, &g->huffprogrst_bytes, total)) return rc;
+    char* base = (char*)g->d_huffprogrst;
+    if (!plain.empty()) HIPCHK(g, hipMemcpyAsync(base, plain.data(), plain.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(base + o_rst, rst.data(), rst.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(base + o_plan, plans.data(), plans.size() * sizeof(lephuff::ProgRstScan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipStreamSynchronize(st));   // (the vectors above are the copies' sources)
+    if (time_from_here) HIPCHK(g, hipEventRecord(g->ev0, st));
+    const lephuff::ProgDecScan* d_plain = (const lephuff::ProgDecScan*)base;
+    const lephuff::ProgDecScan* d_rst = (const lephuff::ProgDecScan*)(base + o_rst);
+    const lephuff::ProgRstScan* d_plan = (const lephuff::ProgRstScan*)(base + o_plan);
+    lephuff::ProgRstOut* d_out = (lephuff::ProgRstOut*)(base + o_out);
+    for (int lv = 0; lv < 64; ++lv) {
+        const int np = pcut[lv + 1] - pcut[lv], nr = rcut[lv + 1] - rcut[lv];
+        if (np > 0)
+            hipLaunchKernelGGL(any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(np), dim3(64), 0, st, d_plain + pcut[lv], (lephuff::HuffDecRow*)d_rows);
+        if (nr > 0) {
+            const uint32_t n = (rcut[lv + 1] < (int)plans.size() ? plans[(size_t)rcut[lv + 1]].piece0 : pieces) - plans[(size_t)rcut[lv]].piece0;
+            hipLaunchKernelGGL(lep_huffprogdec_rst_kernel, dim3(n), dim3(64), 0, st, d_rst + rcut[lv], d_plan + rcut[lv], nr, d_out, (lephuff::HuffDecRow*)d_rows);
+        }
+    }
+    hipLaunchKernelGGL(lep_huffprogdec_rst_reduce_kernel, dim3((unsigned)rst.size()), dim3(64), 0, st, d_rst, d_plan, d_out, (lephuff::HuffDecRow*)d_rows);
+    HIPCHK(g, hipGetLastError());
+    HIPCHK(g, hipEventRecord(g->ev1, st));
+    g->timed = true;
+    g->last_kernel = "lep_huffprogdec_rst_kernel";
+    return 0;
+}
+
+// progressive scans without that form: all levels as ONE pipelined launch, or level after level
+static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* d_rows, hipStream_t st) {
     // scans ordered by dependency level (stable): one launch per level, stream order is the dependency
     int maxlevel = 0;
     for (int i = 0; i < nscan; ++i) { if (scans[i].level < 0 || scans[i].level > 63) return LEP_ASSERTION_FAILURE; maxlevel = std::max(maxlevel, (int)scans[i].level); }

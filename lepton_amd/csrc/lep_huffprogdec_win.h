@@ -26,7 +26,7 @@
 //     positions are walked with counters, not divisions.
 //
 // One wavefront per (image, scan) as before, same pipelining between the scans of a file (ProgDeps / progress), same refusals
-// (status -> the host parser).  Restart intervals keep lep_huffprogdec.h.
+// (status -> the host parser).  Restart intervals: lep_huffprogdec_rst.h starts this wavefront at the markers; without a table of them, lep_huffprogdec.h.
 // SPMD layer of lep_wave.h: tests/emu steps it on the CPU against the host parser and against lep_huffprogdec.h.
 #pragma once
 #include "lep_huffprogdec.h"
@@ -401,16 +401,9 @@ struct ProgWinWave : ProgDecWave {
         *dpos = (int)(((m / mh) * vs + q / hs) * (uint32_t)sc->t.bch[c] + (m % mh) * hs + q % hs);
     }
 
-    template <bool PIPE = false>
-    WDEV void run_scan_win(const ProgDecScan* scan, ProgWinShared* shared, HuffDecRow* rows_arena, const ProgDeps* follow = nullptr, uint32_t* rows_done = nullptr,
-                           int index = 0) {
+    // the scan's constants into registers, its tables into LDS (what every form built on this wave starts with)
+    WDEV void setup_win(const ProgDecScan* scan, ProgWinShared* shared) {
         sc = scan; img = &scan->t; ws = shared; sh = nullptr; status = 0;
-        deps = follow; progress = PIPE ? rows_done : nullptr; self = index; ready = 0;
-        if (PIPE && progress) {
-            bool any = false;
-            for (int i = 0; i < 4; ++i) any = any || deps->dep[i] >= 0;
-            if (!any) ready = 0x7fffffffu;
-        }
         const bool dc = scan->to == 0;
         two_tables = dc;
         fast_kind = dc ? 0 : (scan->sah == 0 ? 1 : 2);
@@ -432,6 +425,19 @@ struct ProgWinWave : ProgDecWave {
             L(zz) = kZ2A[l];
         }
         LSYNC();
+    }
+
+    template <bool PIPE = false>
+    WDEV void run_scan_win(const ProgDecScan* scan, ProgWinShared* shared, HuffDecRow* rows_arena, const ProgDeps* follow = nullptr, uint32_t* rows_done = nullptr,
+                           int index = 0) {
+        deps = follow; progress = PIPE ? rows_done : nullptr; self = index; ready = 0;
+        if (PIPE && progress) {
+            bool any = false;
+            for (int i = 0; i < 4; ++i) any = any || deps->dep[i] >= 0;
+            if (!any) ready = 0x7fffffffu;
+        }
+        setup_win(scan, shared);
+        const bool dc = scan->to == 0;
         base = 0; off = 0; ring_hi = 0;
         request(0);
         stage();
