@@ -214,6 +214,8 @@ def lib():
         L.lep_file_recode_plan_progressive.argtypes = [vp, P(HuffProgImage), P(HuffProgScan), C.c_int, P(C.c_int), P(C.c_int)]
         L.lep_file_recode_finish_progressive.argtypes = [vp, P(Bytes), C.c_int, P(Bytes)]
         L.lep_gpu_huffman_progressive_encode_device.argtypes = [vp, P(HuffProgImage), C.c_int, P(HuffProgScan), C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "lep_gpu_huffman_progressive_encode_forms"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_gpu_huffman_progressive_encode_forms.argtypes = [vp, P(C.c_uint32 * 4)]   # scans of the last call by writer: lane, lane with intervals, wavefront, sequential
         L.lep_jpeg_open_gpu_progressive.argtypes = [vp, P(HuffProgDecScan), C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.lep_jpeg_finish_gpu_progressive.argtypes = [vp, P(HuffProgDecScan), C.c_int, P(HuffDecRow)]
         if hasattr(L, "lep_jpeg_scan_restarts_of"):   # (absent from an older build named by LEP_LIB_PATH, which flags no progressive scan either)
@@ -250,4 +252,5 @@ EXPORTS = [
     "lep_file_recode_plan_progressive", "lep_file_recode_finish_progressive", "lep_gpu_huffman_progressive_encode_device",
     "lep_jpeg_open_gpu_progressive", "lep_jpeg_finish_gpu_progressive", "lep_jpeg_scan_restarts_of", "lep_gpu_huffman_progressive_decode_device",
     "lep_jpeg_plan_progressive_check", "lep_gpu_last_stage_ms", "lep_jpeg_set_container_version", "lep_container_can_write_version", "lep_jpeg_plan_scan_check", "lep_jpeg_scan_file_range",
+    "lep_gpu_huffman_progressive_encode_forms",
 ]

@@ -27,6 +27,7 @@
 #include "lep_huff_simt.h"
 #include "lep_huffprog.h"
 #include "lep_huffprog_simt.h"
+#include "lep_huffprog_simt_rst.h"
 #include "lep_huffprogdec.h"
 #include "lep_huffprogdec_win.h"
 #include "lep_huffprogdec_rst.h"
@@ -359,15 +360,34 @@ __global__ __launch_bounds__(64) void lep_huffprog_simt_units_kernel(const lephu
 __global__ __launch_bounds__(64) void lep_huffprog_simt_place_kernel(const lephuff::ProgScan* __restrict__ scans, lephuff::ProgSimtScan* ps, uint32_t* unit_words, size_t units) {
     lephuff::ProgSimtUnits U;
     U.set(unit_words, units);
+    if (ps[blockIdx.x].rsti) return;   // lep_huffprog_simt_rst_place_kernel's
     lephuff::prog_simt_place(scans, ps + blockIdx.x, U);
 }
-// the bit buffers are cleared as far as the scans reach (pass 2 knows; the buffers are sized by what a scan MAY need, ten times that)
+// ... scans with a restart interval (lep_huffprog_simt_rst.h): their own count / code and place; assign, zero and stuff are shared
+template <bool WRITE>
+__global__ __launch_bounds__(64) void lep_huffprog_simt_rst_units_kernel(const lephuff::ProgImage* __restrict__ images, const lephuff::ProgScan* __restrict__ scans,
+                                                                         const lephuff::ProgSimtScan* __restrict__ ps, const lephuff::ProgSimtWave* __restrict__ waves,
+                                                                         uint32_t* unit_words, size_t units, uint8_t* scratch) {
+    __shared__ lephuff::ProgSimtShared sh;
+    const lephuff::ProgSimtWave w = waves[blockIdx.x];
+    lephuff::ProgSimtUnits U;
+    U.set(unit_words, units);
+    lephuff::prog_simt_rst_units<WRITE>(images, scans, ps + w.pscan, &sh, U, scratch, w.first_unit);
+}
+__global__ __launch_bounds__(64) void lep_huffprog_simt_rst_place_kernel(const lephuff::ProgScan* __restrict__ scans, lephuff::ProgSimtScan* ps, const uint32_t* __restrict__ which,
+                                                                         uint32_t* unit_words, size_t units) {
+    lephuff::ProgSimtUnits U;
+    U.set(unit_words, units);
+    lephuff::prog_simt_rst_place(scans, ps + which[blockIdx.x], U);
+}
+// the bit buffers are cleared as far as the scans reach (pass 2 knows; the buffers are sized by what a scan MAY need, ten times that), and the
+// marker maps behind them (an eighth of the buffer; workgroups count on through them)
 __global__ __launch_bounds__(256) void lep_huffprog_simt_zero_kernel(const lephuff::ProgSimtScan* __restrict__ ps, uint8_t* scratch, uint32_t chunk16) {
     const lephuff::ProgSimtScan s = ps[blockIdx.x];
-    const uint32_t need16 = (uint32_t)std::min<uint64_t>(((uint64_t)s.total_bits + 7) / 8 / 16 + 2, s.buf_bytes / 16);
+    const uint32_t need16 = (uint32_t)std::min<uint64_t>(((uint64_t)s.total_bits + 7) / 8 / 16 + 2, s.buf_bytes / 16), map16 = s.map_bytes / 16;
     uint4* p = reinterpret_cast<uint4*>(scratch + s.buf_off);
-    const uint32_t i0 = blockIdx.y * chunk16, i1 = i0 + chunk16 < need16 ? i0 + chunk16 : need16;
-    for (uint32_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) p[i] = uint4{0u, 0u, 0u, 0u};
+    const uint32_t i0 = blockIdx.y * chunk16, i1 = i0 + chunk16 < need16 + map16 ? i0 + chunk16 : need16 + map16;
+    for (uint32_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) p[i < need16 ? i : s.buf_bytes / 16 + (i - need16)] = uint4{0u, 0u, 0u, 0u};
 }
 __global__ void lep_huffprog_simt_assign_kernel(const lephuff::ProgSimtRegion* __restrict__ regions, int nregion, lephuff::ProgSimtScan* ps) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -511,6 +531,8 @@ struct lep_gpu {
     uint32_t huffprogdec_rst_floor = lephuff::kRstPieceFloor;   // LEP_HUFFPROGDEC_RST_FLOOR: bytes of scan per piece (measurements)
     int huffprogdec_win = 1;            // LEP_HUFFPROGDEC_WIN=0: progressive scans decoded by lep_huffprogdec.h's uniform vector code only
     int huffprog_simt = 1;              // LEP_HUFFPROG_SIMT=0: every progressive scan's bytes from the wavefront-per-scan kernel (lep_huffprog.h)
+    int huffprog_simt_rst = 1;          // LEP_HUFFPROG_SIMT_RST=0: scans with a restart interval from the wavefront-per-scan kernel (lep_huffprog_simt_rst.h off)
+    uint32_t huffprog_forms[4] = {0, 0, 0, 0};   // the last progressive write's scans by form: lane, lane with intervals, wavefront, sequential
     void* d_huffseq[2] = {nullptr, nullptr}; size_t huffseq_bytes[2] = {0, 0};             // scans of sequential frames in a progressive launch: which / caps / byte counts / end states
     void* d_huffprogsimt[2] = {nullptr, nullptr}; size_t huffprogsimt_bytes[2] = {0, 0};   // lep_huffprog_simt.h: descriptors, unit arrays, bit buffers (one per arena set)
     int huffenc_simt = 1;               // LEP_HUFFENC_SIMT=0: every segment's scan bytes from the wavefront-per-segment kernel (lep_huff.h)
@@ -1063,6 +1085,7 @@ int lep_gpu_create(int device, lep_gpu** out) {
     if (const char* e = getenv("LEP_HUFFDEC_SIMT_BITS")) g->simt_sub_bits = std::max(0, atoi(e));
     if (const char* e = getenv("LEP_HUFFENC_SIMT")) g->huffenc_simt = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROG_SIMT")) g->huffprog_simt = atoi(e) != 0;
+    if (const char* e = getenv("LEP_HUFFPROG_SIMT_RST")) g->huffprog_simt_rst = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_WIN")) g->huffprogdec_win = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_RST")) g->huffprogdec_rst = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_RST_FLOOR")) g->huffprogdec_rst_floor = (uint32_t)std::max(1, atoi(e));
@@ -1429,11 +1452,14 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     char* const h_desc = (char*)g->h_huffprog[turn];
     memcpy(h_desc, images, nimg * sizeof(lep_huffprog_image));
     memcpy(h_desc + o_scan, scans, nscan * sizeof(lep_huffprog_scan));
-    // which scans the lane-per-unit kernels take (lep_huffprog_simt.h); the wavefront-per-scan kernel keeps the others
+    // which scans the lane-per-unit kernels take (lep_huffprog_simt.h, with a restart interval lep_huffprog_simt_rst.h); the wavefront-per-scan
+    // kernel keeps the others
     lephuff::ProgScan* hs = reinterpret_cast<lephuff::ProgScan*>(h_desc + o_scan);
     std::vector<lephuff::ProgSimtScan> ps;
-    std::vector<lephuff::ProgSimtWave> waves;
+    std::vector<lephuff::ProgSimtWave> waves, waves_rst;   // (uploaded as one array, waves_rst behind waves)
+    std::vector<uint32_t> rst_which;                       // the entries of ps that lep_huffprog_simt_rst.h's passes 1 - 3 take
     std::vector<lephuff::ProgSimtRegion> regions;
+    for (uint32_t& c : g->huffprog_forms) c = 0;
     size_t nunits = 0, scratch_bytes = 0;
     std::vector<uint32_t> file_bound((size_t)nscan);
     for (int i = 0; i < nscan; ++i) { file_bound[(size_t)i] = hs[i].pad; hs[i].pad = 0; }   // (the caller's field; on the device it says which kernel owns the scan)
@@ -1463,6 +1489,7 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         if (int rc = lep_gpu_huffman_encode_device(g, seq_img.data(), (int)n, seq_seg.data(), (int)n, d_out, (uint32_t*)(b + o_len), (lep_huff_end*)(b + o_end), st)) return rc;
         hipLaunchKernelGGL(lep_huffprog_seq_lens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)b, (const uint32_t*)(b + o_cap), (const uint32_t*)(b + o_len),
                            (const lephuff::HuffEnd*)(b + o_end), (int)n, d_out_len);
+        g->huffprog_forms[3] = (uint32_t)n;
         if ((int)n == nscan) { HIPCHK(g, hipGetLastError()); return 0; }
     }
     if (g->huffprog_simt) {
@@ -1476,15 +1503,19 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
             const int im = hs[order[a]].image;
             lephuff::ProgSimtRegion r{(uint32_t)ps.size(), 0u, scratch_bytes, 0};
             uint64_t sum_cap = 0, bound = 0;
+            bool maps = false;
             for (size_t k = a; k < b && im >= 0 && im < nimg; ++k) {
                 const int i = order[k];
-                uint32_t nb = 0, nu = 0;
-                if (!lephuff::prog_simt_takes(reinterpret_cast<const lephuff::ProgImage&>(images[im]), hs[i], &nb, &nu)) continue;
+                uint32_t nb = 0, nu = 0, interval = 0;
+                const lephuff::ProgImage& pim = reinterpret_cast<const lephuff::ProgImage&>(images[im]);
+                if (!lephuff::prog_simt_takes(pim, hs[i], &nb, &nu) && !(g->huffprog_simt_rst && lephuff::prog_simt_rst_takes(pim, hs[i], &nb, &nu, &interval))) continue;
                 if (nunits + nu > 0x7fffffffu) continue;
                 lephuff::ProgSimtScan e;
                 memset(&e, 0, sizeof e);
-                e.scan = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = nu; e.nblocks = nb;
-                for (uint32_t f = 0; f < nu; f += 64) waves.push_back(lephuff::ProgSimtWave{(uint32_t)ps.size(), f});
+                e.scan = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = nu; e.nblocks = nb; e.rsti = interval;
+                for (uint32_t f = 0; f < nu; f += 64) (interval ? waves_rst : waves).push_back(lephuff::ProgSimtWave{(uint32_t)ps.size(), f});
+                if (interval) { rst_which.push_back((uint32_t)ps.size()); maps = true; }
+                ++g->huffprog_forms[interval ? 1 : 0];
                 nunits += nu;
                 sum_cap += (uint64_t)hs[i].out_cap + 96; bound = std::max<uint64_t>(bound, file_bound[(size_t)i]);
                 hs[i].pad = lephuff::kProgScanSimt;
@@ -1495,6 +1526,7 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
                 // the file's scans together are shorter than the file (lep_huffprog_scan.file_bound, where the caller said); a region
                 // that turns out too small leaves scans without a buffer, and the host re-coder takes the file
                 r.bytes = ((bound ? std::min<uint64_t>(sum_cap, bound + 96ull * r.nps + 4096) : sum_cap) + 15) & ~(uint64_t)15;
+                if (maps) r.bytes += ((r.bytes >> 3) + 16ull * r.nps + 15) & ~(uint64_t)15;   // the marker maps behind the buffers of the scans with an interval
                 scratch_bytes += r.bytes;
                 regions.push_back(r);
             }
@@ -1502,15 +1534,20 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         }
     }
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_ps = 0, o_wv = up(ps.size() * sizeof(lephuff::ProgSimtScan)), o_rg = o_wv + up(waves.size() * sizeof(lephuff::ProgSimtWave)),
-                 o_un = o_rg + up(regions.size() * sizeof(lephuff::ProgSimtRegion)), o_sc = o_un + up(nunits * 4 * lephuff::kProgSimtUnitWords),
-                 simt_total = o_sc + up(scratch_bytes);
+    const size_t o_ps = 0, o_wv = up(ps.size() * sizeof(lephuff::ProgSimtScan)), o_rg = o_wv + up((waves.size() + waves_rst.size()) * sizeof(lephuff::ProgSimtWave)),
+                 o_rw = o_rg + up(regions.size() * sizeof(lephuff::ProgSimtRegion)), o_un = o_rw + up(rst_which.size() * 4),
+                 o_sc = o_un + up(nunits * 4 * (rst_which.empty() ? lephuff::kProgSimtUnitWords : lephuff::kProgSimtRstUnitWords)), simt_total = o_sc + up(scratch_bytes);
+    g->huffprog_forms[2] = (uint32_t)((size_t)nscan - ps.size() - seq_seg.size());
     if (!ps.empty()) { if (int rc = ensure(g, &g->d_huffprogsimt[turn], &g->huffprogsimt_bytes[turn], simt_total)) return rc; }
     HIPCHK(g, hipMemcpyAsync(d_desc, h_desc, total, hipMemcpyHostToDevice, st));
     char* eb = (char*)g->d_huffprogsimt[turn];
     if (!ps.empty()) {
         if (int rc = upload(g, eb + o_ps, ps.data(), ps.size() * sizeof(lephuff::ProgSimtScan), st)) return rc;
-        if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::ProgSimtWave), st)) return rc;
+        if (!waves.empty()) { if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::ProgSimtWave), st)) return rc; }
+        if (!rst_which.empty()) {
+            if (int rc = upload(g, eb + o_wv + waves.size() * sizeof(lephuff::ProgSimtWave), waves_rst.data(), waves_rst.size() * sizeof(lephuff::ProgSimtWave), st)) return rc;
+            if (int rc = upload(g, eb + o_rw, rst_which.data(), rst_which.size() * 4, st)) return rc;
+        }
         if (int rc = upload(g, eb + o_rg, regions.data(), regions.size() * sizeof(lephuff::ProgSimtRegion), st)) return rc;
     }
     const lephuff::ProgImage* di = (const lephuff::ProgImage*)d_desc;
@@ -1524,11 +1561,20 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         uint32_t longest = 0;
         for (const lephuff::ProgSimtRegion& r : regions) longest = (uint32_t)std::max<uint64_t>(longest, r.bytes);
         const uint32_t chunk16 = 4096;   // 64 KB of a bit buffer per workgroup of the clearing kernel
-        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
-        hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, nunits);
+        const lephuff::ProgSimtWave* dwr = dwv + waves.size();
+        const uint32_t* drw = (const uint32_t*)(eb + o_rw);
+        if (!waves.empty()) {
+            hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
+            hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, nunits);
+        }
+        if (!rst_which.empty()) {
+            hipLaunchKernelGGL((lep_huffprog_simt_rst_units_kernel<false>), dim3((unsigned)waves_rst.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwr, dun, nunits, dsc);
+            hipLaunchKernelGGL(lep_huffprog_simt_rst_place_kernel, dim3((unsigned)rst_which.size()), dim3(64), 0, st, ds, dps, drw, dun, nunits);
+        }
         hipLaunchKernelGGL(lep_huffprog_simt_assign_kernel, dim3((unsigned)(regions.size() + 63) / 64), dim3(64), 0, st, (const lephuff::ProgSimtRegion*)(eb + o_rg), (int)regions.size(), dps);
         hipLaunchKernelGGL(lep_huffprog_simt_zero_kernel, dim3((unsigned)ps.size(), (longest / 16 + chunk16 - 1) / chunk16 + 1), dim3(256), 0, st, (const lephuff::ProgSimtScan*)dps, dsc, chunk16);
-        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
+        if (!waves.empty()) hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
+        if (!rst_which.empty()) hipLaunchKernelGGL((lep_huffprog_simt_rst_units_kernel<true>), dim3((unsigned)waves_rst.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwr, dun, nunits, dsc);
         hipLaunchKernelGGL(lep_huffprog_simt_stuff_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dsc, d_out, d_out_len);
     }
     if (ps.size() + seq_seg.size() < (size_t)nscan)
@@ -1659,6 +1705,11 @@ int lep_gpu_sync(lep_gpu* g) {
 }
 
 const char* lep_gpu_last_kernel_name(lep_gpu* g) { return g ? g->last_kernel : ""; }
+int lep_gpu_huffman_progressive_encode_forms(lep_gpu* g, uint32_t counts[4]) {
+    if (!g || !counts) return LEP_GPU_ERROR;
+    for (int i = 0; i < 4; ++i) counts[i] = g->huffprog_forms[i];
+    return 0;
+}
 int lep_gpu_device(lep_gpu* g) { return g ? g->device : -1; }
 // "0000:c1:00.0" of the device the object was created on (hipDeviceGetPCIBusId): which physical GPU a rank of a multi-GPU run drives
 int lep_gpu_pci_bus_id(lep_gpu* g, char* out, int cap) {

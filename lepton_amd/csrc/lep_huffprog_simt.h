@@ -24,7 +24,8 @@
 //              EOBn codes' bits from the two masks; exclusive prefix sum -> the unit's bit position
 //   3  code    lane = unit: the same walk, bits OR-ed into the scan's zero-filled bit buffer (lep_huff_simt.h's LaneSink)
 //   4  stuff   one wavefront per scan: pad bits, FF -> FF 00, clipped to the scan's slot
-// Restart intervals keep the wavefront kernel (ProgScan.pad says which kernel owns a scan): libjpeg's progressive files have none.
+// Scans with a restart interval go through the same passes with a unit map that never straddles an interval's end and a marker map
+// behind the bit buffer (lep_huffprog_simt_rst.h; ProgScan.pad says which kernel owns a scan, ProgSimtScan.rsti which unit map).
 // SPMD layer of lep_wave.h: tests/emu steps every pass on the CPU against lep_huffprog.h and the host re-coder, byte for byte.
 #pragma once
 #include "lep_huff_simt.h"
@@ -45,6 +46,11 @@ struct ProgSimtScan {       // per scan taken by this form
     uint64_t buf_off;       // its bit buffer (bytes, 16-byte aligned) in the scratch arena
     uint32_t buf_bytes;     // multiple of 16
     uint32_t total_bits;    // pass 2
+    uint32_t rsti;          // 0: units of kProgUnit blocks from the scan's first (this file);  > 0: the scan's restart interval, units cut at
+                            // every interval's end (lep_huffprog_simt_rst.h)
+    uint32_t map_bytes;     // rsti > 0, prog_simt_assign: bytes of the marker map behind the bit buffer (bit q = byte q of the buffer is a marker's FF)
+    uint32_t refused;       // rsti > 0, pass 2: the scan's bits do not fit 32 bits -- no buffer, the scan answers "outgrew"
+    uint32_t spare;
 };
 struct ProgSimtWave { uint32_t pscan, first_unit; };   // lane l = unit first_unit + l of ProgSimtScan pscan
 // The bit buffers of one image's scans share a region sized by the FILE (its scans are parts of it: together they are shorter than
@@ -60,9 +66,11 @@ struct ProgSimtUnits {
     uint32_t* pmask;        // pass 1: bit i = ... and leaves its band open (an end-of-band run starts with it)
     uint32_t* cin;          // pass 2: blocks of the current run in front of the unit's first block (0: none open)
     uint32_t* la;           // pass 2: blocks with an empty band that follow the unit's last block
-    WDEV void set(uint32_t* base, size_t units) { bits = base; nonE = base + units; pmask = base + 2 * units; cin = base + 3 * units; la = base + 4 * units; }
+    uint32_t* plain;        // lep_huffprog_simt_rst.h, pass 2: the prefix sum without pad bits and markers (a sixth array: kProgSimtRstUnitWords)
+    WDEV void set(uint32_t* base, size_t units) { bits = base; nonE = base + units; pmask = base + 2 * units; cin = base + 3 * units; la = base + 4 * units; plain = base + 5 * units; }
 };
 constexpr int kProgSimtUnitWords = 5;
+constexpr int kProgSimtRstUnitWords = 6;   // launches that hold a scan with a restart interval
 
 struct ProgSimtShared { uint32_t code[2][256]; };
 
@@ -211,6 +219,70 @@ WDEV int prog_dpos(const ProgImage* pim, int cmp, uint32_t idx) {
     return (int)((idx / nch) * (uint32_t)pim->bch[cmp] + idx % nch);
 }
 
+// one lane's walk (passes 1 and 3) over [a0, a1) of its scan: MCUs of an interleaved DC scan, blocks of a one-component scan (at most 32 of
+// them: the two masks).  fresh: nothing in front of a0 counts -- the scan or a restart interval starts there, the DC predictors are zero.
+template <bool WRITE>
+WDEV void prog_simt_walk(ProgSimtLane<WRITE>& d, uint32_t a0, uint32_t a1, bool fresh, const ProgSimtUnits& U, size_t gu, uint32_t* nonE_out, uint32_t* pmask_out) {
+    const ProgImage* pim = d.pim;
+    const ProgScan* sc = d.sc;
+    const bool dc = sc->to == 0;
+    uint32_t nonE = 0, pmask = 0;
+    if (dc && sc->cmpc > 1) {
+        // MCUs [m0, m1): inside an MCU the scan's components in order, each hs x vs blocks (next_mcupos, jpgcoder.cc:5402-5430)
+        const int m0 = (int)a0, m1 = (int)a1;
+        const int mcuh = pim->mcuh;
+        int last[4] = {0, 0, 0, 0};
+        if (!fresh && sc->sah == 0) {       // the DC of each component's last block in the MCU in front
+            const int m = m0 - 1, row = m / mcuh, mx = m - row * mcuh;
+            for (int i = 0; i < sc->cmpc; ++i) {
+                const int cmp = sc->cmp[i], hs = pim->hs[cmp], vs = pim->vs[cmp];
+                const int v = d.dc_of(cmp, (row * vs + vs - 1) * pim->bch[cmp] + mx * hs + hs - 1);
+                if (i == 0) last[0] = v; else if (i == 1) last[1] = v; else if (i == 2) last[2] = v; else last[3] = v;
+            }
+        }
+        int row = m0 / mcuh, mx = m0 - row * mcuh;
+        for (int m = m0; m < m1; ++m) {
+            for (int i = 0; i < sc->cmpc; ++i) {
+                const int cmp = sc->cmp[i], hs = pim->hs[cmp], vs = pim->vs[cmp], bch = pim->bch[cmp];
+                int cur = i == 0 ? last[0] : (i == 1 ? last[1] : (i == 2 ? last[2] : last[3]));
+                for (int v = 0; v < vs; ++v)
+                    for (int h = 0; h < hs; ++h) d.dc_block(i, cmp, (row * vs + v) * bch + mx * hs + h, &cur);
+                if (i == 0) last[0] = cur; else if (i == 1) last[1] = cur; else if (i == 2) last[2] = cur; else last[3] = cur;
+            }
+            if (++mx == mcuh) { mx = 0; ++row; }
+        }
+    } else {
+        const int cmp = sc->cmp[0];
+        const uint32_t b0 = a0, n = a1 - a0, max = (uint32_t)sc->max_eobrun;
+        if (dc) {
+            int last = (!fresh && sc->sah == 0) ? d.dc_of(cmp, prog_dpos(pim, cmp, b0 - 1)) : 0;
+            for (uint32_t i = 0; i < n; ++i) d.dc_block(0, cmp, prog_dpos(pim, cmp, b0 + i), &last);
+        } else {
+            // pass 3 knows from pass 1 which blocks code something and from pass 2 how the unit stands in its runs
+            uint32_t c = 0;                    // blocks of the open run in front of block i (the reference's eobrun)
+            if (WRITE) { nonE = U.nonE[gu]; pmask = U.pmask[gu]; c = U.cin[gu]; }
+            const uint32_t la = WRITE ? U.la[gu] : 0u;
+            for (uint32_t i = 0; i < n; ++i) {
+                uint32_t w[32];
+                d.load(pim->blocks[cmp] + (int64_t)prog_dpos(pim, cmp, b0 + i) * 64, w);
+                int type;
+                uint64_t Nm = 0, Om = 0, Pm = 0;
+                if (sc->sah == 0) type = d.ac_first_block(w);
+                else { d.refine_masks(w, &Nm, &Om, &Pm); type = d.ac_refine_front(Nm, Om, Pm); }
+                if (!WRITE) { if (type) nonE |= 1u << i; if (type == 1) pmask |= 1u << i; }
+                else if (type == 1 || (type == 0 && c == 0)) {
+                    const uint32_t rest = i + 1 < 32u ? nonE >> (i + 1) : 0u;
+                    const uint32_t follow = rest ? (uint32_t)__builtin_ctz(rest) : n - 1 - i + la;
+                    d.put_eob(follow + 1 < max ? follow + 1 : max);
+                }
+                if (WRITE) { if (type) c = type == 1 ? 1u : 0u; else ++c; if (c == max) c = 0; }
+                if (sc->sah != 0) d.ac_refine_tail(Nm, Om, Pm);
+            }
+        }
+    }
+    *nonE_out = nonE; *pmask_out = pmask;
+}
+
 // passes 1 and 3: lanes = units first_unit .. of scan `ps`
 template <bool WRITE>
 WDEV void prog_simt_units(const ProgImage* images, const ProgScan* scans, const ProgSimtScan* psp, ProgSimtShared* sh, ProgSimtUnits U, uint8_t* scratch, uint32_t first_unit) {
@@ -219,7 +291,6 @@ WDEV void prog_simt_units(const ProgImage* images, const ProgScan* scans, const 
     const ProgImage* pim = images + sc->image;
     prog_simt_tables(sc, sh);
     const bool dc = sc->to == 0, interleaved = sc->cmpc > 1;
-    const uint32_t max = (uint32_t)sc->max_eobrun;
     LANES(l) {
         const uint32_t u = first_unit + (uint32_t)l;
         if (u < ps.nunits) {
@@ -228,59 +299,8 @@ WDEV void prog_simt_units(const ProgImage* images, const ProgScan* scans, const 
             const size_t gu = (size_t)ps.first_unit + u;
             d.sink.start(WRITE ? U.bits[gu] : 0u, reinterpret_cast<uint32_t*>(scratch + ps.buf_off), ps.buf_bytes >> 2);
             uint32_t nonE = 0, pmask = 0;
-            if (dc && interleaved) {
-                // MCUs [m0, m1): inside an MCU the scan's components in order, each hs x vs blocks (next_mcupos, jpgcoder.cc:5402-5430)
-                const int m0 = (int)u * kProgDcMcus, m1 = m0 + kProgDcMcus < (int)ps.nblocks ? m0 + kProgDcMcus : (int)ps.nblocks;
-                const int mcuh = pim->mcuh;
-                int last[4] = {0, 0, 0, 0};
-                if (m0 > 0 && sc->sah == 0) {       // the DC of each component's last block in the MCU in front
-                    const int m = m0 - 1, row = m / mcuh, mx = m - row * mcuh;
-                    for (int i = 0; i < sc->cmpc; ++i) {
-                        const int cmp = sc->cmp[i], hs = pim->hs[cmp], vs = pim->vs[cmp];
-                        const int v = d.dc_of(cmp, (row * vs + vs - 1) * pim->bch[cmp] + mx * hs + hs - 1);
-                        if (i == 0) last[0] = v; else if (i == 1) last[1] = v; else if (i == 2) last[2] = v; else last[3] = v;
-                    }
-                }
-                int row = m0 / mcuh, mx = m0 - row * mcuh;
-                for (int m = m0; m < m1; ++m) {
-                    for (int i = 0; i < sc->cmpc; ++i) {
-                        const int cmp = sc->cmp[i], hs = pim->hs[cmp], vs = pim->vs[cmp], bch = pim->bch[cmp];
-                        int cur = i == 0 ? last[0] : (i == 1 ? last[1] : (i == 2 ? last[2] : last[3]));
-                        for (int v = 0; v < vs; ++v)
-                            for (int h = 0; h < hs; ++h) d.dc_block(i, cmp, (row * vs + v) * bch + mx * hs + h, &cur);
-                        if (i == 0) last[0] = cur; else if (i == 1) last[1] = cur; else if (i == 2) last[2] = cur; else last[3] = cur;
-                    }
-                    if (++mx == mcuh) { mx = 0; ++row; }
-                }
-            } else {
-                const int cmp = sc->cmp[0];
-                const uint32_t b0 = u * (uint32_t)kProgUnit, n = ps.nblocks - b0 < (uint32_t)kProgUnit ? ps.nblocks - b0 : (uint32_t)kProgUnit;
-                if (dc) {
-                    int last = (b0 > 0 && sc->sah == 0) ? d.dc_of(cmp, prog_dpos(pim, cmp, b0 - 1)) : 0;
-                    for (uint32_t i = 0; i < n; ++i) d.dc_block(0, cmp, prog_dpos(pim, cmp, b0 + i), &last);
-                } else {
-                    // pass 3 knows from pass 1 which blocks code something and from pass 2 how the unit stands in its runs
-                    uint32_t c = 0;                    // blocks of the open run in front of block i (the reference's eobrun)
-                    if (WRITE) { nonE = U.nonE[gu]; pmask = U.pmask[gu]; c = U.cin[gu]; }
-                    const uint32_t la = WRITE ? U.la[gu] : 0u;
-                    for (uint32_t i = 0; i < n; ++i) {
-                        uint32_t w[32];
-                        d.load(pim->blocks[cmp] + (int64_t)prog_dpos(pim, cmp, b0 + i) * 64, w);
-                        int type;
-                        uint64_t Nm = 0, Om = 0, Pm = 0;
-                        if (sc->sah == 0) type = d.ac_first_block(w);
-                        else { d.refine_masks(w, &Nm, &Om, &Pm); type = d.ac_refine_front(Nm, Om, Pm); }
-                        if (!WRITE) { if (type) nonE |= 1u << i; if (type == 1) pmask |= 1u << i; }
-                        else if (type == 1 || (type == 0 && c == 0)) {
-                            const uint32_t rest = i + 1 < 32u ? nonE >> (i + 1) : 0u;
-                            const uint32_t follow = rest ? (uint32_t)__builtin_ctz(rest) : n - 1 - i + la;
-                            d.put_eob(follow + 1 < max ? follow + 1 : max);
-                        }
-                        if (WRITE) { if (type) c = type == 1 ? 1u : 0u; else ++c; if (c == max) c = 0; }
-                        if (sc->sah != 0) d.ac_refine_tail(Nm, Om, Pm);
-                    }
-                }
-            }
+            const uint32_t per = dc && interleaved ? (uint32_t)kProgDcMcus : (uint32_t)kProgUnit, a0 = u * per;
+            prog_simt_walk<WRITE>(d, a0, ps.nblocks - a0 < per ? ps.nblocks : a0 + per, u == 0, U, gu, &nonE, &pmask);
             d.sink.finish();
             if (!WRITE) { U.bits[gu] = d.sink.total; U.nonE[gu] = nonE; U.pmask[gu] = pmask; }
         }
@@ -397,12 +417,14 @@ WDEV void prog_simt_assign(const ProgSimtRegion& r, ProgSimtScan* ps) {
     for (uint32_t k = 0; k < r.nps; ++k) {
         ProgSimtScan* s = ps + r.first_ps + k;
         const uint64_t need = ((((uint64_t)s->total_bits + 7) >> 3) + 64 + 15) & ~(uint64_t)15;
-        if (off + need <= r.off + r.bytes && need < 0xfffffff0ull) { s->buf_off = off; s->buf_bytes = (uint32_t)need; off += need; }
-        else { s->buf_off = r.off; s->buf_bytes = 0; }
+        const uint64_t map = s->rsti ? ((need >> 3) + 15) & ~(uint64_t)15 : 0;   // (scans with a restart interval: the marker map behind the buffer)
+        if (off + need + map <= r.off + r.bytes && need < 0xfffffff0ull && !s->refused) { s->buf_off = off; s->buf_bytes = (uint32_t)need; s->map_bytes = (uint32_t)map; off += need + map; }
+        else { s->buf_off = r.off; s->buf_bytes = 0; s->map_bytes = 0; }
     }
 }
 
-// pass 4: one wavefront per scan (abitwriter::pad, then the FF00 rule of the JPEG byte stream)
+// pass 4: one wavefront per scan (abitwriter::pad, then the FF00 rule of the JPEG byte stream -- but for the FFs the marker map names:
+// the restart markers the code pass of lep_huffprog_simt_rst.h put into the buffer)
 WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const ProgSimtScan& ps, uint8_t* scratch, uint8_t* arena, uint32_t* out_len) {
     const ProgScan* sc = scans + ps.scan;
     const ProgImage* pim = images + sc->image;
@@ -425,24 +447,26 @@ WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const 
     }
     const uint32_t nb = total >> 3, cap = sc->out_cap;
     uint8_t* out = arena + sc->out_off;
+    const uint32_t* marker_map = ps.map_bytes ? reinterpret_cast<const uint32_t*>(scratch + ps.buf_off + ps.buf_bytes) : nullptr;
     uint32_t written = 0;
     for (uint32_t base = 0; base < nb; base += 1024) {
         LV(int, nff); LV(int, before);
-        LV(uint32_t, w0); LV(uint32_t, w1); LV(uint32_t, w2); LV(uint32_t, w3);
+        LV(uint32_t, w0); LV(uint32_t, w1); LV(uint32_t, w2); LV(uint32_t, w3); LV(uint32_t, mk);
         LANES(l) {
             const uint32_t i = base + 16u * (uint32_t)l;
-            uint32_t a = 0, b = 0, c = 0, d = 0;
+            uint32_t a = 0, b = 0, c = 0, d = 0, markers = 0;
             int n = 0;
             if (i < nb) {
                 const uint32_t* p = buf + (i >> 2);
                 a = p[0]; b = p[1]; c = p[2]; d = p[3];
+                if (marker_map) markers = (marker_map[i >> 5] >> (i & 16u)) & 0xffffu;   // bit k: byte i + k is a restart marker's FF
                 const uint32_t have = nb - i < 16u ? nb - i : 16u;
                 for (uint32_t k = 0; k < have; ++k) {
                     const uint32_t word = k < 4 ? a : (k < 8 ? b : (k < 12 ? c : d));
-                    n += ((word >> (24 - 8 * (k & 3))) & 255u) == 0xffu;
+                    n += (((word >> (24 - 8 * (k & 3))) & 255u) == 0xffu) & (~markers >> k & 1u);
                 }
             }
-            L(w0) = a; L(w1) = b; L(w2) = c; L(w3) = d; L(nff) = n;
+            L(w0) = a; L(w1) = b; L(w2) = c; L(w3) = d; L(nff) = n; L(mk) = markers;
         }
         const int ffs = lepwave::wave_excl_scan(nff, before);
         LANES(l) {
@@ -455,7 +479,7 @@ WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const 
                     const uint32_t byte = (word >> (24 - 8 * (k & 3))) & 255u;
                     if (pos < cap) out[pos] = (uint8_t)byte;
                     ++pos;
-                    if (byte == 0xffu) { if (pos < cap) out[pos] = 0; ++pos; }
+                    if (byte == 0xffu && !(L(mk) >> k & 1u)) { if (pos < cap) out[pos] = 0; ++pos; }
                 }
             }
         }
@@ -464,7 +488,7 @@ WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const 
     LANES(l) if (l == 0) out_len[ps.scan] = (written < cap ? written : cap) | ((over || written > cap) ? 0x80000000u : 0u);
 }
 
-// which scans this form takes, and how many units it cuts one into
+// which scans this form takes, and how many units it cuts one into (scans with a restart interval: prog_simt_rst_takes, lep_huffprog_simt_rst.h)
 inline bool prog_simt_takes(const ProgImage& im, const ProgScan& sc, uint32_t* nblocks, uint32_t* nunits) {
     if (prog_scan_rsti(im, sc) != 0 || prog_is_sequential(sc)) return false;
     const bool dc = sc.to == 0;

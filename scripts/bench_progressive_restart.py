@@ -5,6 +5,10 @@ larger of the two intervals of the reference's phone images).  Pe
 (median and min, MB/s), and the scan-decode time alone -- lep_gpu_huffman_progressive_decode_device on the same files resident on the
 device, from lep_gpu_last_kernel_ms.  One JSON line per corpus.
 
+--write adds the other direction: decompress_batch warm with --repeats timed runs, and the scan WRITE alone on resident frames
+(lep_gpu_huffman_progressive_encode_device, from lep_gpu_last_kernel_ms; duplicates of a picture share its frame on the device).
+--write-only leaves the compress leg out.
+
 The baseline is ANOTHER BUILD of the library (LEP_LIB_PATH=<the parent commit's liblepton_mi355x.so>), alternated with this one in the
 same visit; LEP_HUFFPROGDEC_RST=0 on this build is a convenience, not the baseline.  --cache DIR keeps the corpus between processes."""
 import argparse
@@ -23,7 +27,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CORPORA = {"rows_1": dict(restart_marker_rows=1), "blocks_516": dict(restart_marker_blocks=516)}
+CORPORA = {"rows_1": dict(restart_marker_rows=1), "blocks_516": dict(restart_marker_blocks=516),
+           "blocks_5": dict(restart_marker_blocks=5)}    # (blocks_5: a marker per five blocks, about 26,000 units per luma scan; not part of "both")
+BOTH = ["blocks_516", "rows_1"]
 
 
 def picture(args):
@@ -111,6 +117,86 @@ def resident(L, g, jpgs):
     return arr, len(all_scans), d_frames, frames, d_rows, nrec, (d_scan, d_frames, d_rows)
 
 
+def resident_frames(L, g, distinct, files):
+    """the distinct pictures' frames on the device and the plan that writes every scan of `files` files again (lep_jpeg_plan_progressive_check)"""
+    from lepton_amd import abi
+    from lepton_amd.codec import JpegImage
+
+    per, mem = [], []
+    for jpg in distinct:
+        src = JpegImage(jpg)
+        img, scans = abi.HuffProgImage(), (abi.HuffProgScan * 64)()
+        first, flen = (C.c_uint32 * 64)(), (C.c_uint32 * 64)()
+        n, ok = C.c_int(0), C.c_int(0)
+        assert L.lep_jpeg_plan_progressive_check(src.handle, len(jpg), C.byref(img), scans, first, flen, 64, C.byref(n), C.byref(ok)) == 0 and ok.value
+        for c in range(src.desc.ncomp):
+            nbytes = src.desc.nblocks(c) * 128
+            d = C.c_void_p()
+            assert L.lep_gpu_malloc(g, nbytes, C.byref(d)) == 0
+            assert L.lep_gpu_memcpy_h2d(g, d, C.string_at(src.desc.blocks[c], nbytes), nbytes) == 0
+            img.blocks[c] = d.value
+            mem.append(d)
+        per.append((img, [(abi.HuffProgScan.from_buffer_copy(scans[i]), flen[i], jpg[first[i]: first[i] + flen[i]]) for i in range(n.value)]))
+    imgs, all_scans, want = [], [], []
+    out_total = corr_total = 0
+    for k in range(files):
+        img, scans = per[k % len(per)]
+        imgs.append(img)
+        for sc0, ln, own in scans:
+            sc = abi.HuffProgScan.from_buffer_copy(sc0)
+            sc.image = k
+            sc.out_cap = min(sc.out_cap, ln + 64)
+            sc.out_off = out_total
+            out_total += (sc.out_cap + 15) & ~15
+            sc.corr_off = corr_total
+            corr_total += sc.corr_cap
+            all_scans.append(sc); want.append(own)
+    return (abi.HuffProgImage * files)(*imgs), (abi.HuffProgScan * len(all_scans))(*all_scans), len(all_scans), out_total + 64, corr_total + 8, mem, want
+
+
+def write_leg(L, codec, distinct, jpgs, repeats):
+    """decompress_batch and the scan write alone; every scan's bytes are held against the file's own"""
+    g = codec.handle
+    leps, st, _ = codec.compress_batch(distinct)
+    assert st == [0] * len(distinct)
+    leps = [leps[i % len(distinct)] for i in range(len(jpgs))]
+    back, st, stats = codec.decompress_batch(leps)                      # warm
+    assert st == [0] * len(leps) and back == jpgs, "a file of the corpus was not restored"
+    assert stats["gpu_huffman_files"] == len(leps), "a file of the corpus went to the host re-coder"
+    secs = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        _, st, _ = codec.decompress_batch(leps)
+        secs.append(time.perf_counter() - t0)
+        assert st == [0] * len(leps)
+    imgs, scans, n, out_bytes, corr_words, mem, want = resident_frames(L, g, distinct, len(jpgs))
+    d_out, d_corr, d_len = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    assert L.lep_gpu_malloc(g, out_bytes, C.byref(d_out)) == 0 and L.lep_gpu_malloc(g, corr_words * 4, C.byref(d_corr)) == 0 and L.lep_gpu_malloc(g, n * 4 + 16, C.byref(d_len)) == 0
+    ms, kernel = [], ""
+    for rep in range(repeats + 1):                                      # (the first one warm)
+        assert L.lep_gpu_huffman_progressive_encode_device(g, imgs, len(jpgs), scans, n, d_out, d_corr, d_len, None) == 0, codec.last_error()
+        assert L.lep_gpu_sync(g) == 0, codec.last_error()
+        if rep:
+            ms.append(L.lep_gpu_last_kernel_ms(g))
+        kernel = L.lep_gpu_last_kernel_name(g).decode()
+    forms = None
+    if hasattr(L, "lep_gpu_huffman_progressive_encode_forms"):
+        counts = (C.c_uint32 * 4)()
+        L.lep_gpu_huffman_progressive_encode_forms(g, C.byref(counts))
+        forms = list(counts)
+    out, lens = C.create_string_buffer(out_bytes), (C.c_uint32 * n)()
+    assert L.lep_gpu_memcpy_d2h(g, out, d_out, out_bytes) == 0 and L.lep_gpu_memcpy_d2h(g, lens, d_len, n * 4) == 0
+    got = memoryview(out)                                               # (out.raw would copy the whole arena once per scan)
+    wrong = sum(1 for i in range(n) if lens[i] >= 0x80000000 or bytes(got[scans[i].out_off: scans[i].out_off + lens[i]]) != want[i])
+    for m in mem + [d_out, d_corr, d_len]:
+        L.lep_gpu_free(g, m)
+    nbytes = sum(map(len, jpgs))
+    return {"decompress_batch_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4)},
+            "decompress_MB_s": {"median": round(nbytes / statistics.median(secs) / 1e6, 1), "best": round(nbytes / min(secs) / 1e6, 1)},
+            "scan_write_ms": {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}, "scan_write_kernel": kernel,
+            "scans_written": n, "scans_by_form": forms, "scans_not_the_files_own": wrong, "knob_LEP_HUFFPROG_SIMT_RST": os.environ.get("LEP_HUFFPROG_SIMT_RST")}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--files", type=int, default=256)
@@ -120,6 +206,8 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--corpus", choices=sorted(CORPORA) + ["both"], default="both")
     ap.add_argument("--cache", default=None)
+    ap.add_argument("--write", action="store_true", help="add the write leg: decompress_batch and the scan write alone")
+    ap.add_argument("--write-only", action="store_true", help="the write leg without the compress leg")
     ap.add_argument("--label", default=os.environ.get("LEP_LIB_PATH") and "LEP_LIB_PATH" or "this build")
     a = ap.parse_args()
     assert a.repeats >= 5, "at least 5 repeats"
@@ -128,10 +216,14 @@ def main():
 
     L = abi.lib()
     codec = GpuCodec(0)
-    for name in (sorted(CORPORA) if a.corpus == "both" else [a.corpus]):
+    for name in (BOTH if a.corpus == "both" else [a.corpus]):
         distinct = corpus(name, a.width, a.height, a.distinct, a.cache)
         jpgs = [distinct[i % len(distinct)] for i in range(a.files)]
         nbytes = sum(map(len, jpgs))
+        if a.write_only:
+            print(json.dumps(dict({"corpus": name, "label": a.label, "library": abi.LIB_PATH, "files": a.files, "distinct": a.distinct, "size": [a.width, a.height], "jpeg_bytes": nbytes,
+                                   "repeats": a.repeats}, **write_leg(L, codec, distinct, jpgs, a.repeats))), flush=True)
+            continue
         _, st, stats = codec.compress_batch(jpgs)                       # warm: staging, workspaces
         assert st == [0] * len(jpgs), "a file of the corpus was refused"
         assert stats["gpu_huffman_files"] == len(jpgs), "a file of the corpus went to the host parser"
@@ -156,8 +248,9 @@ def main():
         refused = sum(1 for sc in arr if rows[sc.result_off].aux >> 8)
         for m in mem:
             L.lep_gpu_free(g, m)
+        written = write_leg(L, codec, distinct, jpgs, a.repeats) if a.write else {}
         print(json.dumps({"corpus": name, "label": a.label, "library": abi.LIB_PATH, "files": a.files, "distinct": a.distinct, "size": [a.width, a.height], "jpeg_bytes": nbytes,
-                          "knob_LEP_HUFFPROGDEC_RST": os.environ.get("LEP_HUFFPROGDEC_RST"), "repeats": a.repeats,
+                          "knob_LEP_HUFFPROGDEC_RST": os.environ.get("LEP_HUFFPROGDEC_RST"), "repeats": a.repeats, **written,
                           "compress_batch_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4)},
                           "compress_MB_s": {"median": round(nbytes / statistics.median(secs) / 1e6, 1), "best": round(nbytes / min(secs) / 1e6, 1)},
                           "scan_decode_ms": {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3)}, "scan_decode_kernel": kernel,
