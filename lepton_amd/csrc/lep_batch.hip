@@ -26,6 +26,7 @@
 
 #include "../../include/lepton_mi355x.h"
 #include "jpeg_model.h"
+#include "lep_buffers.h"
 #include "lep_container.h"
 
 namespace {
@@ -116,30 +117,34 @@ void tune_malloc_for_pool() {
     mallopt(M_ARENA_MAX, 512);
 }
 
+// Every buffer of a slot, once -- X(Dev | Pin, type, name, counted): Slot declares them from this list, and release / footprint /
+// poison walk it.  `counted`: pinned memory, or one of the large device arenas (lep_batch_footprint; the per-segment tables are KBs)
+#define LEP_SLOT_BUFFERS(X)                                                                                                                  \
+    X(Dev, char, d_frames, 1)     X(Pin, char, h_frames, 1)                                                                                  \
+    X(Dev, char, d_scratch, 1)         /* the verification decode's frames: as large as d_frames, only allocated when asked for */           \
+    X(Dev, uint8_t, d_streams, 1) X(Pin, uint8_t, h_streams, 1)   /* device arena (worst-case sized for encode) / pinned mirror (actual bytes) */ \
+    X(Dev, uint32_t, d_len, 0)    X(Dev, int32_t, d_status, 0)   /* d_status: [nseg] coder statuses + [nseg] verification-decode statuses */ \
+    X(Dev, uint32_t, d_flags, 0)                                                                                                             \
+    X(Dev, uint8_t, d_scan, 1)    X(Pin, uint8_t, h_scan, 1)   /* JPEG scan bytes of the GPU Huffman encoder */                              \
+    X(Dev, uint32_t, d_scanlen, 0)     /* nseg byte counts, then (16-byte aligned) nseg lep_huff_end records */                              \
+    X(Dev, lep_huffdec_row, d_rows, 1) /* row records of the GPU Huffman decoder */                                                          \
+    X(Dev, uint8_t, d_pscan, 1)        /* progressive files: the scans' device arena (sized for the worst case) ... */                       \
+    X(Pin, uint8_t, h_pscan, 1)        /* ... and the pinned mirror, packed by the bytes actually written */                                 \
+    X(Dev, uint32_t, d_corr, 1)        /* held-back correction bits of the refinement scans (dwords) */                                      \
+    X(Dev, uint32_t, d_pscanlen, 0)    X(Dev, ScanCheck, d_pcheck, 0)   /* compression with verify: what lep_scan_check_kernel compares */   \
+    X(Dev, uint8_t, d_vscan, 1)        /* ... and for baseline files: their scans written again from the device frame, */                    \
+    X(Dev, uint32_t, d_vscanlen, 0)    X(Dev, ScanCheck, d_vcheck, 0)   /* per thread segment */
+
 struct Slot {   // one chunk's buffers (double-buffered)
-    char* h_frames = nullptr; char* d_frames = nullptr; char* d_scratch = nullptr; size_t frames_cap = 0, hframes_cap = 0;
-    uint8_t* d_streams = nullptr; uint8_t* h_streams = nullptr; size_t streams_cap = 0, hstreams_cap = 0;   // device arena (worst-case sized for encode) / pinned mirror (actual bytes)
-    uint32_t* d_len = nullptr; int32_t* d_status = nullptr; uint32_t* d_flags = nullptr; size_t seg_cap = 0, img_cap = 0;
-    uint8_t* d_scan = nullptr; uint8_t* h_scan = nullptr; size_t scan_cap = 0;   // JPEG scan bytes of the GPU Huffman encoder
-    uint32_t* d_scanlen = nullptr; size_t scanlen_cap = 0;   // nseg byte counts, then (16-byte aligned) nseg lep_huff_end records
-    char* d_rows = nullptr; size_t rows_cap = 0;   // row records of the GPU Huffman decoder
-    uint8_t* d_pscan = nullptr; size_t pscan_cap = 0;      // progressive files: the scans' device arena (sized for the worst case) ...
-    uint8_t* h_pscan = nullptr; size_t hpscan_cap = 0;     // ... and the pinned mirror, packed by the bytes actually written
-    uint32_t* d_corr = nullptr; size_t corr_cap = 0;       // held-back correction bits of the refinement scans (dwords)
-    uint32_t* d_pscanlen = nullptr; size_t pscanlen_cap = 0;
-    ScanCheck* d_pcheck = nullptr; size_t pcheck_cap = 0;   // compression with verify: what lep_scan_check_kernel compares
-    uint8_t* d_vscan = nullptr; size_t vscan_cap = 0;       // ... and for baseline files: their scans written again from the device frame,
-    uint32_t* d_vscanlen = nullptr; ScanCheck* d_vcheck = nullptr; size_t vseg_cap = 0;   // per thread segment
+#define X(kind, T, name, counted) lepbuf::kind##Buf<T> name;
+    LEP_SLOT_BUFFERS(X)
+#undef X
     hipEvent_t up = nullptr, done = nullptr, decoded = nullptr;
     bool done_recorded = false;   // `done` has been recorded in the current batch call
     void release() {
-        if (h_frames) (void)hipHostFree(h_frames);
-        if (h_streams) (void)hipHostFree(h_streams);
-        if (h_scan) (void)hipHostFree(h_scan);
-        if (h_pscan) (void)hipHostFree(h_pscan);
-        for (void* p : {(void*)d_vscan, (void*)d_vscanlen, (void*)d_vcheck}) if (p) (void)hipFree(p);
-        for (void* p : {(void*)d_pscan, (void*)d_corr, (void*)d_pscanlen, (void*)d_pcheck, (void*)d_frames, (void*)d_scratch, (void*)d_streams, (void*)d_len, (void*)d_status, (void*)d_flags, (void*)d_scan, (void*)d_scanlen, (void*)d_rows})
-            if (p) (void)hipFree(p);
+#define X(kind, T, name, counted) (void)name.release();
+        LEP_SLOT_BUFFERS(X)
+#undef X
         if (up) (void)hipEventDestroy(up);
         if (done) (void)hipEventDestroy(done);
         if (decoded) (void)hipEventDestroy(decoded);
@@ -191,150 +196,61 @@ struct HandleVector {   // parsed files of a batch: whatever is still open when 
 };
 
 double g_alloc_s = 0;   // time spent in (re)allocating staging buffers during the current call (single orchestrator thread)
+struct AllocTimer {
+    const double t0 = now_s();
+    ~AllocTimer() { g_alloc_s += now_s() - t0; }
+};
+// a slot's device buffers ask for exactly what they need
+template <class T> hipError_t grow(lepbuf::DevBuf<T>& b, size_t need) { return b.ensure(need, 0, dev_alloc); }
 
-int slot_reserve_impl(Slot* s, size_t frames, size_t streams, size_t nseg, size_t nimg, bool scratch, size_t host_streams);
 // host_streams: bytes of the pinned mirror of the stream arena (decompress: all of it; compress: reserved later, once the
 // encoder has reported how many bytes it really wrote -- the arena itself is sized for the worst case, 5x more)
 int slot_reserve(Slot* s, size_t frames, size_t streams, size_t nseg, size_t nimg, bool scratch, size_t host_streams) {
-    const double t0 = now_s();
-    const int rc = slot_reserve_impl(s, frames, streams, nseg, nimg, scratch, host_streams);
-    g_alloc_s += now_s() - t0;
-    return rc;
-}
-int slot_reserve_impl(Slot* s, size_t frames, size_t streams, size_t nseg, size_t nimg, bool scratch, size_t host_streams) {
-    if (frames > s->frames_cap) {
-        if (s->d_frames) (void)hipFree(s->d_frames);
-        if (s->d_scratch) (void)hipFree(s->d_scratch);
-        s->d_frames = s->d_scratch = nullptr; s->frames_cap = 0;   // (a capacity never outlives its allocation: the next hipMalloc may fail)
-        HIPOK(dev_alloc((void**)&s->d_frames, frames));
-        s->frames_cap = frames;
-    }
-    if (scratch && !s->d_scratch) HIPOK(dev_alloc((void**)&s->d_scratch, s->frames_cap));
-    if (streams > s->streams_cap) {
-        if (s->d_streams) (void)hipFree(s->d_streams);
-        s->d_streams = nullptr; s->streams_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_streams, streams));
-        s->streams_cap = streams;
-    }
-    if (host_streams > s->hstreams_cap) {
-        if (s->h_streams) (void)hipHostFree(s->h_streams);
-        s->h_streams = nullptr; s->hstreams_cap = 0;
-        const size_t want = host_streams + host_streams / 4;   // head room: the next chunk of similar files should not reallocate
-        HIPOK(hipHostMalloc((void**)&s->h_streams, want, hipHostMallocDefault));
-        s->hstreams_cap = want;
-    }
-    if (nseg > s->seg_cap) {
-        if (s->d_len) (void)hipFree(s->d_len);
-        if (s->d_status) (void)hipFree(s->d_status);
-        s->d_len = nullptr; s->d_status = nullptr; s->seg_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_len, nseg * 4));
-        HIPOK(dev_alloc((void**)&s->d_status, nseg * 8));   // [nseg] coder statuses + [nseg] verification-decode statuses
-        s->seg_cap = nseg;
-    }
-    if (nimg > s->img_cap) {
-        if (s->d_flags) (void)hipFree(s->d_flags);
-        s->d_flags = nullptr; s->img_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_flags, nimg * 4));
-        s->img_cap = nimg;
-    }
+    AllocTimer timed;
+    if (frames > s->d_frames.cap) (void)s->d_scratch.release();   // (as large as d_frames: it goes when that grows)
+    HIPOK(grow(s->d_frames, frames));
+    if (scratch) HIPOK(grow(s->d_scratch, s->d_frames.cap));
+    HIPOK(grow(s->d_streams, streams));
+    HIPOK(s->h_streams.ensure(host_streams, host_streams / 4));   // head room: the next chunk of similar files should not reallocate
+    HIPOK(grow(s->d_len, nseg * 4));
+    HIPOK(grow(s->d_status, nseg * 8));
+    HIPOK(grow(s->d_flags, nimg * 4));
     if (!s->up) HIPOK(hipEventCreateWithFlags(&s->up, hipEventDisableTiming));
     if (!s->done) HIPOK(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
     if (!s->decoded) HIPOK(hipEventCreateWithFlags(&s->decoded, hipEventDisableTiming));
     return 0;
 }
 
-// the end-state records live behind the byte counts of the same allocation (16-byte aligned)
-lep_huff_end* huff_ends(Slot* s) { return (lep_huff_end*)((char*)s->d_scanlen + ((s->scanlen_cap * 4 + 15) & ~(size_t)15)); }
+// the end-state records of a launch of nseg segments live behind its byte counts in the same allocation (16-byte aligned)
+lep_huff_end* huff_ends(Slot* s, size_t nseg) { return s->d_scanlen.at<lep_huff_end>(lepbuf::round_up(nseg * 4, 16)); }
 
 int scan_reserve(Slot* s, size_t bytes, size_t nseg) {
-    const double t0 = now_s();
-    if (bytes > s->scan_cap) {
-        if (s->h_scan) (void)hipHostFree(s->h_scan);
-        if (s->d_scan) (void)hipFree(s->d_scan);
-        s->h_scan = s->d_scan = nullptr; s->scan_cap = 0;
-        HIPOK(hipHostMalloc((void**)&s->h_scan, bytes, hipHostMallocDefault));
-        HIPOK(dev_alloc((void**)&s->d_scan, bytes));
-        s->scan_cap = bytes;
-    }
-    if (nseg > s->scanlen_cap) {
-        if (s->d_scanlen) (void)hipFree(s->d_scanlen);
-        s->d_scanlen = nullptr; s->scanlen_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_scanlen, nseg * 4 + 16 + nseg * sizeof(lep_huff_end)));
-        s->scanlen_cap = nseg;
-    }
-    g_alloc_s += now_s() - t0;
+    AllocTimer timed;
+    HIPOK(s->h_scan.ensure(bytes));
+    HIPOK(grow(s->d_scan, bytes));
+    HIPOK(grow(s->d_scanlen, nseg ? nseg * 4 + 16 + nseg * sizeof(lep_huff_end) : 0));
     return 0;
 }
-
 int prog_reserve(Slot* s, size_t scan_bytes, size_t corr_words, size_t nscan) {
-    const double t0 = now_s();
-    if (scan_bytes > s->pscan_cap) {
-        if (s->d_pscan) (void)hipFree(s->d_pscan);
-        s->d_pscan = nullptr; s->pscan_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_pscan, scan_bytes));
-        s->pscan_cap = scan_bytes;
-    }
-    if (corr_words > s->corr_cap) {
-        if (s->d_corr) (void)hipFree(s->d_corr);
-        s->d_corr = nullptr; s->corr_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_corr, corr_words * 4));
-        s->corr_cap = corr_words;
-    }
-    if (nscan > s->pscanlen_cap) {
-        if (s->d_pscanlen) (void)hipFree(s->d_pscanlen);
-        s->d_pscanlen = nullptr; s->pscanlen_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_pscanlen, nscan * 4));
-        s->pscanlen_cap = nscan;
-    }
-    if (nscan > s->pcheck_cap) {
-        if (s->d_pcheck) (void)hipFree(s->d_pcheck);
-        s->d_pcheck = nullptr; s->pcheck_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_pcheck, nscan * sizeof(ScanCheck)));
-        s->pcheck_cap = nscan;
-    }
-    g_alloc_s += now_s() - t0;
+    AllocTimer timed;
+    HIPOK(grow(s->d_pscan, scan_bytes));
+    HIPOK(grow(s->d_corr, corr_words * 4));
+    HIPOK(grow(s->d_pscanlen, nscan * 4));
+    HIPOK(grow(s->d_pcheck, nscan * sizeof(ScanCheck)));
     return 0;
 }
 int vscan_reserve(Slot* s, size_t bytes, size_t nseg) {
-    const double t0 = now_s();
-    if (bytes > s->vscan_cap) {
-        if (s->d_vscan) (void)hipFree(s->d_vscan);
-        s->d_vscan = nullptr; s->vscan_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_vscan, bytes));
-        s->vscan_cap = bytes;
-    }
-    if (nseg > s->vseg_cap) {
-        if (s->d_vscanlen) (void)hipFree(s->d_vscanlen);
-        if (s->d_vcheck) (void)hipFree(s->d_vcheck);
-        s->d_vscanlen = nullptr; s->d_vcheck = nullptr; s->vseg_cap = 0;
-        HIPOK(dev_alloc((void**)&s->d_vscanlen, nseg * 4));
-        HIPOK(dev_alloc((void**)&s->d_vcheck, nseg * sizeof(ScanCheck)));
-        s->vseg_cap = nseg;
-    }
-    g_alloc_s += now_s() - t0;
+    AllocTimer timed;
+    HIPOK(grow(s->d_vscan, bytes));
+    HIPOK(grow(s->d_vscanlen, nseg * 4));
+    HIPOK(grow(s->d_vcheck, nseg * sizeof(ScanCheck)));
     return 0;
 }
-int prog_host_reserve(Slot* s, size_t bytes) {
-    if (bytes <= s->hpscan_cap) return 0;
-    const double t0 = now_s();
-    if (s->h_pscan) (void)hipHostFree(s->h_pscan);
-    s->h_pscan = nullptr; s->hpscan_cap = 0;
-    const size_t want = bytes + bytes / 4;
-    HIPOK(hipHostMalloc((void**)&s->h_pscan, want, hipHostMallocDefault));
-    s->hpscan_cap = want;
-    g_alloc_s += now_s() - t0;
-    return 0;
-}
-
-// pinned host staging for whole frames: only needed for files the host Huffman coder handles
-int host_frames_reserve(Slot* s, size_t frames) {
-    if (frames <= s->hframes_cap) return 0;
-    const double t0 = now_s();
-    if (s->h_frames) (void)hipHostFree(s->h_frames);
-    s->h_frames = nullptr; s->hframes_cap = 0;
-    HIPOK(hipHostMalloc((void**)&s->h_frames, frames, hipHostMallocDefault));
-    s->hframes_cap = frames;
-    g_alloc_s += now_s() - t0;
+// pinned staging that is only taken where a path needs it: whole frames for the files the host Huffman coder handles (head 0), the
+// progressive scans' mirror (a quarter of head room, like h_streams)
+template <class T> int pinned_reserve(lepbuf::PinBuf<T>& b, size_t need, size_t head = 0) {
+    AllocTimer timed;
+    HIPOK(b.ensure(need, head));
     return 0;
 }
 
@@ -378,7 +294,7 @@ size_t frame_exact_bytes(const lep_image_desc& d) {
     for (int c = 0; c < d.ncomp; ++c) b += (size_t)d.width_blocks[c] * d.height_blocks[c] * 128;
     return b;
 }
-size_t frame_bytes_of(const lep_image_desc& d) { return (frame_exact_bytes(d) + 255) & ~(size_t)255; }
+size_t frame_bytes_of(const lep_image_desc& d) { return lepbuf::round_up(frame_exact_bytes(d)); }
 
 }  // namespace
 
@@ -392,9 +308,9 @@ void lep_batch_release(void) { for (Slot& s : g_slots) s.release(); }
 void lep_batch_footprint(size_t* pinned_bytes, size_t* device_bytes) {
     size_t pinned = 0, device = 0;
     for (const Slot& s : g_slots) {
-        pinned += (s.h_frames ? s.hframes_cap : 0) + (s.h_streams ? s.hstreams_cap : 0) + (s.h_scan ? s.scan_cap : 0) + (s.h_pscan ? s.hpscan_cap : 0);
-        device += (s.d_frames ? s.frames_cap : 0) + (s.d_scratch ? s.frames_cap : 0) + (s.d_streams ? s.streams_cap : 0) + (s.d_scan ? s.scan_cap : 0)
-                  + (s.d_rows ? s.rows_cap : 0) + (s.d_pscan ? s.pscan_cap : 0) + (s.d_corr ? s.corr_cap * 4 : 0) + (s.d_vscan ? s.vscan_cap : 0);
+#define X(kind, T, name, counted) if (counted) (s.name.pinned ? pinned : device) += s.name.cap;
+        LEP_SLOT_BUFFERS(X)
+#undef X
     }
     if (pinned_bytes) *pinned_bytes = pinned;
     if (device_bytes) *device_bytes = device;
@@ -404,9 +320,9 @@ void lep_batch_footprint(size_t* pinned_bytes, size_t* device_bytes) {
 // show that nothing stale from an earlier batch (the padding between frames, the tails of streams) reaches a result
 void lep_batch_debug_poison(int value) {
     for (Slot& s : g_slots) {
-        if (s.h_frames) memset(s.h_frames, value, s.hframes_cap);
-        if (s.h_streams) memset(s.h_streams, value, s.hstreams_cap);
-        if (s.h_scan) memset(s.h_scan, value, s.scan_cap);
+#define X(kind, T, name, counted) if (s.name.pinned && s.name.p) memset(s.name.p, value, s.name.cap);
+        LEP_SLOT_BUFFERS(X)
+#undef X
     }
 }
 
@@ -440,7 +356,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
         for (int i = first[k]; i < first[k + 1]; ++i) {
             if (status[i]) continue;
             c->live.push_back(i); c->frame_off.push_back(bytes);
-            bytes += (fbytes[i] + 255) & ~(size_t)255;
+            bytes += lepbuf::round_up(fbytes[i]);
         }
         c->count = first[k + 1] - first[k];
         c->frame_bytes = bytes;
@@ -537,7 +453,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
         bool any_host = false;
         for (int k = 0; k < nl; ++k) any_host |= need_host[k] != 0;
         if (any_host) {
-            if (int rc = host_frames_reserve(s, c->frame_bytes)) return rc;
+            if (int rc = pinned_reserve(s->h_frames, c->frame_bytes)) return rc;
             parallel_for(nl, threads, [&](int k) { if (need_host[k]) host_parse_one(c, s, k); });
         }
         // scan arena (pinned -> device), row records
@@ -579,14 +495,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
         std::vector<lep_huffdec_row> rows(rows_total);
         if (ngpu) {
             if (int rc = scan_reserve(s, scan_total + 256, 0)) return rc;
-            const double ta = now_s();
-            if (rows_total * sizeof(lep_huffdec_row) > s->rows_cap) {
-                if (s->d_rows) (void)hipFree(s->d_rows);
-                s->d_rows = nullptr; s->rows_cap = 0;
-                HIPOK(dev_alloc((void**)&s->d_rows, rows_total * sizeof(lep_huffdec_row)));
-                s->rows_cap = rows_total * sizeof(lep_huffdec_row);
-            }
-            g_alloc_s += now_s() - ta;
+            { AllocTimer timed; HIPOK(grow(s->d_rows, rows_total * sizeof(lep_huffdec_row))); }
             parallel_for(nl, threads, [&](int k) {
                 if (!on_gpu[k] && !on_prog[k]) return;
                 const uint8_t* p = nullptr; size_t len = 0;
@@ -653,10 +562,10 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
             if (simt) {
                 std::vector<lep_huffdec_image> many, one;
                 for (const lep_huffdec_image& hi : launch) ((hi.rsti && !(hi.flags & LEP_HUFFDEC_RST_TABLE)) ? one : many).push_back(hi);
-                if (!many.empty()) { if (int rc = lep_gpu_huffman_decode_simt_device(g, many.data(), (int)many.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc; }
-                if (!one.empty()) { if (int rc = lep_gpu_huffman_decode_device(g, one.data(), (int)one.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc; }
+                if (!many.empty()) { if (int rc = lep_gpu_huffman_decode_simt_device(g, many.data(), (int)many.size(), s->d_rows, s_huff)) return rc; }
+                if (!one.empty()) { if (int rc = lep_gpu_huffman_decode_device(g, one.data(), (int)one.size(), s->d_rows, s_huff)) return rc; }
             } else
-            if (int rc = lep_gpu_huffman_decode_device(g, launch.data(), (int)launch.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc;
+            if (int rc = lep_gpu_huffman_decode_device(g, launch.data(), (int)launch.size(), s->d_rows, s_huff)) return rc;
             // progressive files: one wavefront per (image, scan), launched dependency level by dependency level
             std::vector<lep_huffprogdec_scan> plaunch;
             std::vector<size_t> pfirst_desc(nl, 0);
@@ -675,7 +584,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                     plaunch.push_back(sc);
                 }
             }
-            if (!plaunch.empty()) { if (int rc = lep_gpu_huffman_progressive_decode_device(g, plaunch.data(), (int)plaunch.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc; }
+            if (!plaunch.empty()) { if (int rc = lep_gpu_huffman_progressive_decode_device(g, plaunch.data(), (int)plaunch.size(), s->d_rows, s_huff)) return rc; }
             HIPOK(hipMemcpyAsync(rows.data(), s->d_rows, rows_total * sizeof(lep_huffdec_row), hipMemcpyDeviceToHost, s_huff));
             HIPOK(hipStreamSynchronize(s_huff));
             st.d2h_bytes += (double)(rows_total * sizeof(lep_huffdec_row));
@@ -690,7 +599,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                     again.push_back(hi);
                 }
                 if (!again.empty()) {
-                    if (int rc = lep_gpu_huffman_decode_device(g, again.data(), (int)again.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc;
+                    if (int rc = lep_gpu_huffman_decode_device(g, again.data(), (int)again.size(), s->d_rows, s_huff)) return rc;
                     HIPOK(hipMemcpyAsync(rows.data(), s->d_rows, rows_total * sizeof(lep_huffdec_row), hipMemcpyDeviceToHost, s_huff));
                     HIPOK(hipStreamSynchronize(s_huff));
                 }
@@ -718,7 +627,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                     }
                 }
                 if (!again.empty()) {
-                    if (int rc = lep_gpu_huffman_progressive_decode_device(g, again.data(), (int)again.size(), (lep_huffdec_row*)s->d_rows, s_huff)) return rc;
+                    if (int rc = lep_gpu_huffman_progressive_decode_device(g, again.data(), (int)again.size(), s->d_rows, s_huff)) return rc;
                     HIPOK(hipMemcpyAsync(rows.data(), s->d_rows, rows_total * sizeof(lep_huffdec_row), hipMemcpyDeviceToHost, s_huff));
                     HIPOK(hipStreamSynchronize(s_huff));
                 }
@@ -740,7 +649,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
             bool any_redo = false;
             for (int k = 0; k < nl; ++k) any_redo |= redo[k] != 0;
             if (any_redo) {
-                if (int rc = host_frames_reserve(s, c->frame_bytes)) return rc;
+                if (int rc = pinned_reserve(s->h_frames, c->frame_bytes)) return rc;
                 parallel_for(nl, threads, [&](int k) { if (redo[k]) host_parse_one(c, s, k); });
             }
             st.parse_s += now_s() - t0;
@@ -780,7 +689,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                 const bool prog = lep_jpeg_is_progressive(parsed[c->live[k]]) != 0;
                 const size_t by_bytes = (size_t)ho[q].segment_size + ho[q].segment_size / 4, by_blocks = prog ? blocks * 40 / ns : 0;
                 c->segs.push_back(sg[q]);
-                c->offs.push_back(c->offs.back() + ((std::max(by_bytes, by_blocks) + 65536 + 255) & ~(size_t)255));
+                c->offs.push_back(c->offs.back() + lepbuf::round_up(std::max(by_bytes, by_blocks) + 65536));
             }
         }
         c->seg_first.push_back((int)c->segs.size());
@@ -1048,7 +957,7 @@ int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, lep_bytes* ou
                 lep_file_close(files[i]); files[i] = nullptr;
                 return;
             }
-            if (!rc) fbytes[i] = (lep_file_frame_bytes(files[i]) + 255) & ~(size_t)255;
+            if (!rc) fbytes[i] = lepbuf::round_up(lep_file_frame_bytes(files[i]));
             if (rc) { status[i] = rc; if (files[i]) { lep_file_close(files[i]); files[i] = nullptr; } }
         });
         st.parse_s += now_s() - t0;
@@ -1196,7 +1105,7 @@ int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, lep_bytes* ou
         bool any_host = false;
         for (size_t k = 0; k < c->live.size(); ++k) { any_host |= c->hfirst[k] < 0 && c->pfirst[k] < 0; if (c->hfirst[k] >= 0 || c->pfirst[k] >= 0) st.gpu_huffman_files += 1; }
         if (any_host) {
-            if (int rc = host_frames_reserve(s, c->frame_bytes)) return rc;
+            if (int rc = pinned_reserve(s->h_frames, c->frame_bytes)) return rc;
             for (size_t k = 0; k < c->live.size(); ++k)
                 if (c->hfirst[k] < 0 && c->pfirst[k] < 0) lep_file_describe_into(files[c->live[k]], s->h_frames + c->frame_off[k], fbytes[c->live[k]], &c->host_desc[k]);
         }
@@ -1268,7 +1177,7 @@ int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, lep_bytes* ou
         const double tt1 = now_s();
         if (s_scan != s_compute) { HIPOK(hipEventRecord(s->decoded, s_compute)); HIPOK(hipStreamWaitEvent(s_scan, s->decoded, 0)); }
         if (!c->hseg.empty()) {
-            rc = lep_gpu_huffman_encode_device(g, c->himg.data(), (int)c->himg.size(), c->hseg.data(), (int)c->hseg.size(), s->d_scan, s->d_scanlen, huff_ends(s), s_scan);
+            rc = lep_gpu_huffman_encode_device(g, c->himg.data(), (int)c->himg.size(), c->hseg.data(), (int)c->hseg.size(), s->d_scan, s->d_scanlen, huff_ends(s, c->hseg.size()), s_scan);
             if (rc) return rc;
         }
         if (tr) fprintf(stderr, "[batch] launch_chunk first=%d: decode launch %.3f s, scan-encode launch %.3f s (t=%.3f)\n", c->first, tt1 - tt0, now_s() - tt1, now_s() - t_pipe0);
@@ -1325,7 +1234,7 @@ int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, lep_bytes* ou
             HIPOK(hipStreamWaitEvent(s_down, s->done, 0));
             HIPOK(hipMemcpyAsync(sts.data(), s->d_status, (size_t)nseg * 4, hipMemcpyDeviceToHost, s_down));
             if (!c->hseg.empty()) HIPOK(hipMemcpyAsync(slens.data(), s->d_scanlen, c->hseg.size() * 4, hipMemcpyDeviceToHost, s_down));
-            if (!c->hseg.empty()) HIPOK(hipMemcpyAsync(sends.data(), huff_ends(s), c->hseg.size() * sizeof(lep_huff_end), hipMemcpyDeviceToHost, s_down));
+            if (!c->hseg.empty()) HIPOK(hipMemcpyAsync(sends.data(), huff_ends(s, c->hseg.size()), c->hseg.size() * sizeof(lep_huff_end), hipMemcpyDeviceToHost, s_down));
             if (!c->pscan.empty()) HIPOK(hipMemcpyAsync(plens.data(), s->d_pscanlen, c->pscan.size() * 4, hipMemcpyDeviceToHost, s_down));
             HIPOK(hipStreamSynchronize(s_down));
             if (!c->pscan.empty()) {
@@ -1336,13 +1245,13 @@ int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, lep_bytes* ou
                     for (int q = c->pfirst[k]; q < c->pfirst[k] + c->pcount[k]; ++q) fits = fits && !(plens[q] & 0x80000000u);
                     if (!fits) {   // a scan outgrew its slot or its scratch: that file takes the host re-coder
                         c->pfirst[k] = -1;
-                        if (int rc = host_frames_reserve(s, c->frame_bytes)) { rc_all = rc; break; }
+                        if (int rc = pinned_reserve(s->h_frames, c->frame_bytes)) { rc_all = rc; break; }
                         lep_file_describe_into(files[c->live[k]], s->h_frames + c->frame_off[k], fbytes[c->live[k]], &c->host_desc[k]);
                         continue;
                     }
                     for (int q = c->pfirst[k]; q < c->pfirst[k] + c->pcount[k]; ++q) { poff[q] = total; total += ((size_t)plens[q] + 15) & ~(size_t)15; }
                 }
-                if (!rc_all) { if (int rc = prog_host_reserve(s, total + 256)) rc_all = rc; }
+                if (!rc_all) { if (int rc = pinned_reserve(s->h_pscan, total + 256, (total + 256) / 4)) rc_all = rc; }
                 if (rc_all) break;
                 for (int k = 0; k < nimg; ++k) {
                     if (c->pfirst[k] < 0) continue;
@@ -1388,7 +1297,7 @@ int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, lep_bytes* ou
                     if (!on_gpu) {
                         st.gpu_huffman_files -= 1;
                         c->hfirst[k] = -1;
-                        if (int rc = host_frames_reserve(s, c->frame_bytes)) { rc_all = rc; break; }
+                        if (int rc = pinned_reserve(s->h_frames, c->frame_bytes)) { rc_all = rc; break; }
                         lep_file_describe_into(files[c->live[k]], s->h_frames + c->frame_off[k], fbytes[c->live[k]], &c->host_desc[k]);
                     }
                     else if (!scan_whole) for (int q = h0; q < h1; ++q)

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <map>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +14,7 @@
 #include <vector>
 
 #include "../../include/lepton_mi355x.h"
+#include "lep_buffers.h"
 
 #define LEP_DEV __device__ __forceinline__
 #include "lep_core.h"
@@ -533,10 +533,7 @@ struct lep_gpu {
     int huffprog_simt = 1;              // LEP_HUFFPROG_SIMT=0: every progressive scan's bytes from the wavefront-per-scan kernel (lep_huffprog.h)
     int huffprog_simt_rst = 1;          // LEP_HUFFPROG_SIMT_RST=0: scans with a restart interval from the wavefront-per-scan kernel (lep_huffprog_simt_rst.h off)
     uint32_t huffprog_forms[4] = {0, 0, 0, 0};   // the last progressive write's scans by form: lane, lane with intervals, wavefront, sequential
-    void* d_huffseq[2] = {nullptr, nullptr}; size_t huffseq_bytes[2] = {0, 0};             // scans of sequential frames in a progressive launch: which / caps / byte counts / end states
-    void* d_huffprogsimt[2] = {nullptr, nullptr}; size_t huffprogsimt_bytes[2] = {0, 0};   // lep_huffprog_simt.h: descriptors, unit arrays, bit buffers (one per arena set)
     int huffenc_simt = 1;               // LEP_HUFFENC_SIMT=0: every segment's scan bytes from the wavefront-per-segment kernel (lep_huff.h)
-    void* d_huffenc[2] = {nullptr, nullptr}; size_t huffenc_bytes[2] = {0, 0};   // lep_huff_simt.h: segment / wave descriptors, unit bit counts, bit buffers (one per arena set, like d_huff)
     int simt_sub_bits = 0;              // LEP_HUFFDEC_SIMT_BITS: bits per subsequence of the lane-per-subsequence scan decoder (0 = from the launch's size)
     int huffprog_pipeline_max = 16384;  // LEP_HUFFPROG_PIPELINE_MAX: scans per launch up to which the levels go out as one pipelined launch (measured to 10240:
                                         // 1024 4K files, 798 -> 938 MB/s; a workgroup takes the scan of the ticket it draws when it starts, so a scan's predecessors are always running or done)
@@ -562,7 +559,7 @@ struct lep_gpu {
                              // fill them, else 4 / 128 VGPRs, no spills); LEP_DEC_WAVES = 4 | 8 forces one
     std::string err;
     const char* last_kernel = "";   // name of the kernel the most recent launch used
-    // Device memory the object owns (round 4): every grow-only workspace below is a virtual address range of its own (hipMemAddressReserve)
+    // Device memory the object owns (round 4): every large grow-only workspace below is a virtual address range of its own (hipMemAddressReserve)
     // into which physical chunks of 512 MB (hipMemCreate) are mapped as it grows -- growing maps more chunks behind what is there, nothing
     // is freed and taken again.  A workspace that is given back (lep_gpu_trim) is unmapped and its chunks go to the object's POOL, from
     // which the next workspace that grows takes them: memory moves between the encoder's scratch, the decoder's models and the rings
@@ -570,60 +567,62 @@ struct lep_gpu {
     // what it hands out -- hipMalloc of 96 GB takes 2.9 - 4.1 s, hipMemCreate the same per byte -- while unmapping 96 GB of chunks takes
     // 19 ms and mapping them again 14 ms.  Round 3's "2x cliff" after a trim was the next launch paying ~40 ms per GB for ~140 GB again.
     // Only lep_gpu_release_memory (and an allocation that fails elsewhere) hands the pool to the driver.  LEP_VMM=0: plain hipMalloc /
-    // hipFree as before (A/B).
-    struct VBuf { char* va = nullptr; size_t reserved = 0, mapped = 0; std::vector<hipMemGenericAllocationHandle_t> chunks; };
+    // hipFree as before (A/B).  A workspace's range and chunks are the buffer's own (lep_buffers.h, DevBuf::v).
     struct Vmm {
         bool on = false;
         size_t chunk = (size_t)512 << 20;   // (64 MB chunks cost the encoder 2 %: 470 -> 480 ms, more page-table fragments; 512 MB: as one hipMalloc -- profiles/r05q_*)
         hipMemAllocationProp prop;
         hipMemAccessDesc access;
-        std::map<void**, VBuf> bufs;   // keyed by the member that holds the workspace's pointer
         std::vector<hipMemGenericAllocationHandle_t> pool;   // chunks of workspaces that were given back (lep_gpu_trim): unmapped, still ours --
                                                              // the next workspace that grows, of whatever kind, maps them again
         size_t mapped_total = 0, creates = 0, releases = 0;
     } vmm;
-    // grow-only device workspace of a coder launch (models, neighbour summaries, descriptors).  There are two sets so that two
-    // launches may be in flight at once on different streams (lep_gpu_use_arena: the next chunk's coder kernel starts in the
-    // wave slots that the long segments of the current one leave free); everything else uses set 0.
-    struct Arena {
-        void* d_models = nullptr; size_t models_bytes = 0;
-        void* d_ns = nullptr; size_t ns_bytes = 0;
-        void* d_meta = nullptr; size_t meta_bytes = 0;      // ImageDev[] | SegDev[] | ns_offsets[] | bins[]
-    } arena[2];
-    int cur = 0;
-    // split-phase encoder scratch: ONE set (a 4K image takes ~140 MB of it), shared by the two arena sets -- a split-phase launch
-    // waits for the one before it (ev_enc5_done), which fills the chip on its own anyway
-    struct Enc5Scratch {
-        void* d_plans = nullptr; size_t plans_bytes = 0;       // SegPlan5[] | counts | totals
-        void* d_entries = nullptr; size_t entries_bytes = 0;   // the chains' entry streams, records, places
-        void* d_binlist = nullptr; size_t binlist_bytes = 0;   // the segments' bin lists
-        void* d_wchunks = nullptr; size_t wchunks_bytes = 0;   // the stitched writer's records, one per (segment, chunk)
-    } enc5;
+    // Every device workspace of the object, once: release_device_side, lep_gpu_trim and release_idle_caches walk ws[].  A name with _1
+    // behind it is one of a pair (W_X + k): one per arena set, or two used in turn.
+    enum Ws {
+        // -- what lep_gpu_trim gives back: all of it is re-acquired by the next launch that needs it.  release_idle_caches takes the same,
+        //    bar the models and summaries of the arena set a launch is being set up in.
+        // split-phase encoder scratch: ONE set (a 4K image takes ~140 MB of it), shared by the two arena sets -- a split-phase launch
+        // waits for the one before it (ev_enc5_done), which fills the chip on its own anyway
+        W_ENC5_ENTRIES,             // the chains' entry streams, records, places
+        W_ENC5_BINLIST,             // the segments' bin lists
+        // grow-only device workspace of a coder launch (models, neighbour summaries; descriptors: W_META).  There are two sets so that two
+        // launches may be in flight at once on different streams (lep_gpu_use_arena: the next chunk's coder kernel starts in the
+        // wave slots that the long segments of the current one leave free); everything else uses set 0.
+        W_MODELS, W_MODELS_1,
+        W_NS, W_NS_1,
+        W_TRIMMED,                  // -- what stays through a trim: from here on
+        W_META = W_TRIMMED, W_META_1,   // ImageDev[] | SegDev[] | ns_offsets[] | bins[]
+        W_ENC5_PLANS,               // SegPlan5[] | counts | totals
+        W_ENC5_WCHUNKS,             // the stitched writer's records, one per (segment, chunk)
+        // host-variant staging
+        W_BLOCKS, W_STREAMS, W_LENS,
+        // HuffImage[] | HuffSegment[], one per arena set: the batch compressor's round-trip check writes the scans of chunk k and of chunk k + 1 on two
+        // streams (lep_gpu_use_arena picks the set), and a short chunk k + 1 reaches its scan encoder before a long chunk k does -- with one buffer its
+        // descriptors replaced the ones chunk k's kernels were still to read (a memory fault in tests/test_gpu_parity.py::*overlapped_launches, once,
+        // round 6: the scans of sequential frames in several scans come through here a second time per chunk)
+        W_HUFF, W_HUFF_1,
+        W_HUFFENC, W_HUFFENC_1,     // lep_huff_simt.h: segment / wave descriptors, unit bit counts, bit buffers (one per arena set, like W_HUFF)
+        W_HUFFPROG, W_HUFFPROG_1,   // ProgImage[] | ProgScan[], one per turn (two launches on two streams)
+        W_HUFFPROGSIMT, W_HUFFPROGSIMT_1,   // lep_huffprog_simt.h: descriptors, unit arrays, bit buffers (one per turn)
+        W_HUFFSEQ, W_HUFFSEQ_1,     // scans of sequential frames in a progressive launch: which / caps / byte counts / end states (one per turn)
+        W_HUFFPROGDEC,              // ProgDecScan[]
+        W_HUFFPROGRST,              // files with scans of lep_huffprogdec_rst.h: ProgDecScan[], ProgRstScan[], ProgRstOut[]
+        W_HUFFDEC,                  // HuffDecImage[]
+        W_HUFFPAR,                  // the lane-per-subsequence scan decoder's records (SimtImage | SimtWave | SimtSub x 2 | SimtPlace)
+        W_COUNT
+    };
+    lepbuf::DevBuf<> ws[W_COUNT];
+    int cur = 0;                    // the arena set of the launches being set up (lep_gpu_use_arena)
     hipEvent_t ev_enc5_done = nullptr;
     uint32_t* d_bins = nullptr;
     std::vector<uint32_t> h_bins;
-    // host-variant staging
-    void* d_blocks = nullptr; size_t blocks_bytes = 0;
-    void* d_streams = nullptr; size_t streams_bytes = 0;
-    void* d_lens = nullptr; size_t lens_bytes = 0;
-    // HuffImage[] | HuffSegment[], one per arena set: the batch compressor's round-trip check writes the scans of chunk k and of chunk k + 1 on two
-    // streams (lep_gpu_use_arena picks the set), and a short chunk k + 1 reaches its scan encoder before a long chunk k does -- with one buffer its
-    // descriptors replaced the ones chunk k's kernels were still to read (a memory fault in tests/test_gpu_parity.py::*overlapped_launches, once,
-    // round 6: the scans of sequential frames in several scans come through here a second time per chunk)
-    void* d_huff[2] = {nullptr, nullptr}; size_t huff_bytes[2] = {0, 0};
-    void* d_huffprog[2] = {nullptr, nullptr}; size_t huffprog_bytes[2] = {0, 0};   // ProgImage[] | ProgScan[], one per arena set (two launches on two streams)
     struct Staging { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
     Staging staging[16];                // pinned ring for descriptor uploads (upload()): nothing on a launch path waits for its stream
     int staging_next = 0;
     std::vector<void*> staging_retired;
-    void* h_huffprog[2] = {nullptr, nullptr}; size_t h_huffprog_bytes[2] = {0, 0};   // pinned staging of the same: the upload does not wait for the stream
+    lepbuf::PinBuf<char> h_huffprog[2];   // pinned staging of W_HUFFPROG: the upload does not wait for the stream
     int huffprog_turn = 0;   // the two sets are used in turn: at most two launches are ever in flight (lep_batch.hip queues chunk k+1 before it fetches chunk k)
-    void* d_huffprogdec = nullptr; size_t huffprogdec_bytes = 0;   // ProgDecScan[]
-    void* d_huffprogrst = nullptr; size_t huffprogrst_bytes = 0;   // files with scans of lep_huffprogdec_rst.h: ProgDecScan[], ProgRstScan[], ProgRstOut[]
-    void* d_huffdec = nullptr; size_t huffdec_bytes = 0;   // HuffDecImage[]
-    void* d_huffpar = nullptr; size_t huffpar_bytes = 0;   // the lane-per-subsequence scan decoder's records (SimtImage | SimtWave | SimtSub x 2 | SimtPlace)
-    void* d_scan = nullptr; size_t scan_bytes = 0;      // scan bytes of the Huffman encoder (host variant)
-    void* d_scanlen = nullptr; size_t scanlen_bytes = 0;
 };
 
 #define HIPCHK(g, call)                                                                        \
@@ -653,8 +652,10 @@ static void vmm_init(lep_gpu* g) {
     g->vmm.access.flags = hipMemAccessFlagsProtReadWrite;
     g->vmm.on = true;
 }
-// gives a workspace back: its chunks unmapped and pooled (or released to the driver), the address range kept for the next time it grows
-static void vmm_unmap(lep_gpu* g, lep_gpu::VBuf& b, bool to_driver = false) {
+typedef lepbuf::DevBuf<> Workspace;
+// gives a workspace's range back: its chunks unmapped and pooled (or released to the driver), the address range kept for the next time it grows
+static void vmm_unmap(lep_gpu* g, Workspace& w, bool to_driver = false) {
+    lepbuf::VRange& b = w.v;
     if (b.mapped) (void)hipMemUnmap(b.va, b.mapped);
     for (hipMemGenericAllocationHandle_t h : b.chunks) {
         if (to_driver) { (void)hipMemRelease(h); ++g->vmm.releases; }
@@ -662,49 +663,44 @@ static void vmm_unmap(lep_gpu* g, lep_gpu::VBuf& b, bool to_driver = false) {
     }
     g->vmm.mapped_total -= b.mapped;
     b.chunks.clear(); b.mapped = 0;
+    w.set(nullptr, 0);
 }
 static void vmm_drain_pool(lep_gpu* g) {
     for (hipMemGenericAllocationHandle_t h : g->vmm.pool) { (void)hipMemRelease(h); ++g->vmm.releases; }
     g->vmm.pool.clear();
 }
-static void dev_release(lep_gpu* g, void** p, size_t* have) {
-    if (g->vmm.on) {
-        auto it = g->vmm.bufs.find(p);
-        if (it != g->vmm.bufs.end()) { vmm_unmap(g, it->second); *p = nullptr; if (have) *have = 0; return; }
-    }
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; if (have) *have = 0;
+static void dev_release(lep_gpu* g, Workspace& w) {
+    if (w.v.va) vmm_unmap(g, w);
+    else (void)w.release();
 }
 static void vmm_destroy(lep_gpu* g) {
-    for (auto& kv : g->vmm.bufs) {
-        vmm_unmap(g, kv.second, true);
-        if (kv.second.va) (void)hipMemAddressFree(kv.second.va, kv.second.reserved);
-        *kv.first = nullptr;
+    for (Workspace& w : g->ws) {
+        if (!w.v.va) continue;
+        vmm_unmap(g, w, true);
+        (void)hipMemAddressFree(w.v.va, w.v.reserved);
+        w.v = lepbuf::VRange();
     }
-    g->vmm.bufs.clear();
     vmm_drain_pool(g);
 }
 // before an allocation failure is reported: the cached memory no launch that is being set up depends on -- the split-phase
 // encoder's scratch (its launches take the single-kernel encoder when they cannot have it) and the other arena set's models
 static void release_idle_caches(lep_gpu* g) {
     (void)hipDeviceSynchronize();
-    lep_gpu::Arena& O = g->arena[g->cur ^ 1];
-    void** ps[] = {&g->enc5.d_entries, &g->enc5.d_binlist, &O.d_models, &O.d_ns};
-    size_t* ns[] = {&g->enc5.entries_bytes, &g->enc5.binlist_bytes, &O.models_bytes, &O.ns_bytes};
-    for (int i = 0; i < 4; ++i) dev_release(g, ps[i], ns[i]);
+    for (int w = 0; w < lep_gpu::W_TRIMMED; ++w)
+        if (w != lep_gpu::W_MODELS + g->cur && w != lep_gpu::W_NS + g->cur) dev_release(g, g->ws[w]);
 }
-static int vmm_ensure(lep_gpu* g, void** p, size_t* have, size_t need, bool may_release) {
+static int vmm_ensure(lep_gpu* g, Workspace& w, size_t need, bool may_release) {
     lep_gpu::Vmm& V = g->vmm;
-    lep_gpu::VBuf& b = V.bufs[p];
+    lepbuf::VRange& b = w.v;
     const size_t want = ((need + V.chunk - 1) / V.chunk) * V.chunk;
     if (want > b.reserved) {   // a longer address range (what the workspace held is not kept: every launch fills it anew)
         // The old range is unmapped and freed here, and launches do not wait for their streams any more (upload() ring; lep_batch.hip
         // queues chunk k + 1 while chunk k's kernels run): a kernel still in flight would lose its mapping under its feet.  hipFree
         // used to synchronise implicitly; this path has to ask.  Rare: growth inside the reservation maps behind.
         if (b.mapped) (void)hipDeviceSynchronize();
-        vmm_unmap(g, b);
+        vmm_unmap(g, w);
         if (b.va) (void)hipMemAddressFree(b.va, b.reserved);
-        b.va = nullptr; b.reserved = 0; *p = nullptr; *have = 0;
+        b.va = nullptr; b.reserved = 0;
         size_t res = want + want / 2;
         res = ((std::max(res, (size_t)256 << 20) + V.chunk - 1) / V.chunk) * V.chunk;
         void* va = nullptr;
@@ -729,31 +725,24 @@ static int vmm_ensure(lep_gpu* g, void** p, size_t* have, size_t need, bool may_
         b.chunks.push_back(h); b.mapped += V.chunk; V.mapped_total += V.chunk;
     }
     if (b.mapped > old) HIPCHK(g, hipMemSetAccess(b.va + old, b.mapped - old, &V.access, 1));
-    *p = b.va; *have = b.mapped;
+    w.set(b.va, b.mapped);
     return 0;
 }
-static int ensure(lep_gpu* g, void** p, size_t* have, size_t need, bool may_release = true) {
-    if (*have >= need) return 0;
+static int ensure(lep_gpu* g, Workspace& w, size_t need, bool may_release = true) {
+    if (w.cap >= need) return 0;
     // the large workspaces (models, rings, scratch: GBs) are owned address ranges with pooled chunks; descriptors and other small ones
     // (a chunk would be mostly slack) stay plain allocations
-    if (g->vmm.on && (need >= ((size_t)32 << 20) || g->vmm.bufs.count(p))) {
-        if (*p && !g->vmm.bufs.count(p)) { HIPCHK(g, hipFree(*p)); *p = nullptr; *have = 0; }
-        return vmm_ensure(g, p, have, need, may_release);
+    if (g->vmm.on && (need >= ((size_t)32 << 20) || w.v.va)) {
+        if (!w.v.va) HIPCHK(g, w.release());   // a plain buffer that turns virtual
+        return vmm_ensure(g, w, need, may_release);
     }
-    if (*p) HIPCHK(g, hipFree(*p));
-    *p = nullptr; *have = 0;
-    size_t want = need + need / 8;
-    if (hipMalloc(p, want) != hipSuccess) {   // (the head room is a convenience: without it before giving up)
+    hipError_t e = w.ensure(need, need / 8);   // (the head room is a convenience: without it before giving up)
+    if (e != hipSuccess && may_release) {
         (void)hipGetLastError();
-        *p = nullptr; want = need;
-        if (hipMalloc(p, want) != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            if (may_release) release_idle_caches(g);
-            HIPCHK(g, hipMalloc(p, want));
-        }
+        release_idle_caches(g);
+        e = w.ensure(need);
     }
-    *have = want;
+    if (e != hipSuccess) { g->err = std::string("hipMalloc: ") + hipGetErrorString(e); return LEP_GPU_ERROR; }
     return 0;
 }
 
@@ -765,8 +754,8 @@ static int ensure(lep_gpu* g, void** p, size_t* have, size_t need, bool may_rele
 constexpr int kEnc5NoMemory = -1000;   // launch_enc5: the scratch could not be allocated (nothing has been written for the caller yet)
 static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, const uint64_t* d_nsoff, int nseg, uint8_t* d_streams,
                        uint32_t* d_stream_len, int32_t* d_status, hipStream_t st) {
-    lep_gpu::Arena& A = g->arena[g->cur];
-    lep_gpu::Enc5Scratch& E = g->enc5;
+    Workspace &models = g->ws[lep_gpu::W_MODELS + g->cur], &ns = g->ws[lep_gpu::W_NS + g->cur];
+    Workspace &ws_plans = g->ws[lep_gpu::W_ENC5_PLANS], &ws_entries = g->ws[lep_gpu::W_ENC5_ENTRIES], &ws_binlist = g->ws[lep_gpu::W_ENC5_BINLIST], &wchunks = g->ws[lep_gpu::W_ENC5_WCHUNKS];
     if (!g->stream2) {
         HIPCHK(g, hipEventCreateWithFlags(&g->ev_enc5_done, hipEventDisableTiming));
         for (auto& e : g->ev_part) HIPCHK(g, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -777,13 +766,14 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         HIPCHK(g, hipEventCreateWithFlags(&g->ev_join3, hipEventDisableTiming));
         for (auto& e : g->ev_stage) HIPCHK(g, hipEventCreate(&e));
     }
-    const size_t o_counts = ((size_t)nseg * sizeof(lep5::SegPlan5) + 255) & ~(size_t)255,
-                 o_tot = o_counts + (((size_t)nseg * lep5::kCountWords * 4 + 255) & ~(size_t)255);
+    lepbuf::Layout L;
+    L.add<lep5::SegPlan5>((size_t)nseg);
+    const size_t o_counts = L.add<uint32_t>((size_t)nseg * lep5::kCountWords), o_tot = L.add<uint64_t>(2);
     HIPCHK(g, hipStreamWaitEvent(st, g->ev_enc5_done, 0));   // (the scratch is the previous split-phase launch's until its writer is done)
-    if (int rc = ensure(g, &E.d_plans, &E.plans_bytes, o_tot + 256)) return rc;
-    lep5::SegPlan5* plans = (lep5::SegPlan5*)E.d_plans;
-    uint32_t* counts = (uint32_t*)((char*)E.d_plans + o_counts);
-    uint64_t* d_tot = (uint64_t*)((char*)E.d_plans + o_tot);
+    if (int rc = ensure(g, ws_plans, L.padded())) return rc;
+    lep5::SegPlan5* plans = ws_plans.at<lep5::SegPlan5>(0);
+    uint32_t* counts = ws_plans.at<uint32_t>(o_counts);
+    uint64_t* d_tot = ws_plans.at<uint64_t>(o_tot);
     const int groups = (nseg + 63) / 64;
     g->nstage = 0;
     HIPCHK(g, hipEventRecord(g->ev_stage[0], st));
@@ -792,7 +782,7 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     auto walk = [&](int mode, uint8_t* entries, uint16_t* binlist, int part = 0) {
         size_t lds = lep5::walk_lds_bytes(mode);
         if (mode == lep5::kGather && g->enc5_gather_wgs > 0) lds = std::max(lds, (size_t)(160 * 1024 / g->enc5_gather_wgs) & ~(size_t)255);   // (measurement aid: fewer resident workgroups)
-#define LEP_WALK(MODE, NW) hipLaunchKernelGGL((lep_enc5_walk_kernel<MODE, NW>), dim3(nseg), dim3(64 * NW), lds, st, d_img, d_seg, (NSum*)A.d_ns, d_nsoff, plans, entries, binlist, counts, part, nparts)
+#define LEP_WALK(MODE, NW) hipLaunchKernelGGL((lep_enc5_walk_kernel<MODE, NW>), dim3(nseg), dim3(64 * NW), lds, st, d_img, d_seg, (NSum*)ns.p, d_nsoff, plans, entries, binlist, counts, part, nparts)
         if (mode == lep5::kCount) { if (two) LEP_WALK(lep5::kCount, 2); else LEP_WALK(lep5::kCount, 1); }
         else if (mode == lep5::kEmit) { if (two) LEP_WALK(lep5::kEmit, 2); else LEP_WALK(lep5::kEmit, 1); }
         else { if (two) LEP_WALK(lep5::kGather, 2); else LEP_WALK(lep5::kGather, 1); }
@@ -802,12 +792,12 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     hipLaunchKernelGGL(lep_enc5_plan_kernel, dim3(groups), dim3(64), 0, st, (const uint32_t*)counts, plans, nseg);
     hipLaunchKernelGGL(lep_enc5_offsets_kernel, dim3(1), dim3(64), 0, st, plans, nseg, d_tot);
     // the threshold Branches are the only model state in HBM: 2 MB per segment, reset while the count pass is looked at
-    hipLaunchKernelGGL(lep_enc5_fill_kernel, dim3(4096), dim3(256), 0, st, (uint4*)A.d_models, (size_t)nseg * lep5::kThreshWords / 4, kBranchInit);
+    hipLaunchKernelGGL(lep_enc5_fill_kernel, dim3(4096), dim3(256), 0, st, (uint4*)models.p, (size_t)nseg * lep5::kThreshWords / 4, kBranchInit);
     uint64_t tot[2] = {0, 0};
     HIPCHK(g, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
     HIPCHK(g, hipStreamSynchronize(st));
     // no room for the scratch (~140 MB per 4K image): the single-kernel encoder takes the launch -- it needs none
-    if ((size_t)tot[0] + (size_t)tot[1] * 2 > g->enc5_scratch_max || ensure(g, &E.d_entries, &E.entries_bytes, (size_t)tot[0] + 256, false) || ensure(g, &E.d_binlist, &E.binlist_bytes, (size_t)tot[1] * 2 + 256, false)) {
+    if ((size_t)tot[0] + (size_t)tot[1] * 2 > g->enc5_scratch_max || ensure(g, ws_entries, (size_t)tot[0] + 256, false) || ensure(g, ws_binlist, (size_t)tot[1] * 2 + 256, false)) {
         (void)hipGetLastError();
         g->err.clear();
         static bool told = false;
@@ -818,25 +808,25 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     // and dropped: MI355X, 1024 x 4K, profiles/r04l_*: 1 group 784 ms, 2: 875, 4: 1232; launches this large do not share the chip.)
     {
         HIPCHK(g, hipEventRecord(g->ev_stage[1], st));
-        walk(lep5::kEmit, (uint8_t*)E.d_entries, nullptr);
+        walk(lep5::kEmit, (uint8_t*)ws_entries.p, nullptr);
         HIPCHK(g, hipEventRecord(g->ev_stage[2], st));
-        hipLaunchKernelGGL(lep_enc5_bucket_kernel, dim3(nseg), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)E.d_entries);
+        hipLaunchKernelGGL(lep_enc5_bucket_kernel, dim3(nseg), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p);
         HIPCHK(g, hipEventRecord(g->ev_fork, st));
         HIPCHK(g, hipStreamWaitEvent(g->stream2, g->ev_fork, 0));
         HIPCHK(g, hipStreamWaitEvent(g->stream3, g->ev_fork, 0));
         if (g->enc5_fold_apart) {   // measurement aid (LEP_ENC5_FOLD_APART=1): every kind of chain as a launch of its own, one after the other
             const int small0[4] = {0, 2, 14, 46}, big0[3] = {0, 12, 32};   // sign | threshold | edge counts;  DC | 7x7 counts
             for (int i = 0; i < 3; ++i)
-                hipLaunchKernelGGL(lep_enc5_fold_small_kernel, dim3((unsigned)groups * (small0[i + 1] - small0[i])), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)E.d_entries,
-                                   (uint32_t*)A.d_models, nseg, groups, small0[i]);
+                hipLaunchKernelGGL(lep_enc5_fold_small_kernel, dim3((unsigned)groups * (small0[i + 1] - small0[i])), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p,
+                                   (uint32_t*)models.p, nseg, groups, small0[i]);
             for (int i = 0; i < 2; ++i)
-                hipLaunchKernelGGL(lep_enc5_fold_big_kernel, dim3((unsigned)groups * (big0[i + 1] - big0[i])), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)E.d_entries, nseg, groups, big0[i]);
+                hipLaunchKernelGGL(lep_enc5_fold_big_kernel, dim3((unsigned)groups * (big0[i + 1] - big0[i])), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p, nseg, groups, big0[i]);
         } else {
-        hipLaunchKernelGGL(lep_enc5_fold_small_kernel, dim3((unsigned)groups * kFold5SmallJobs), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (uint8_t*)E.d_entries,
-                           (uint32_t*)A.d_models, nseg, groups, 0);
-        hipLaunchKernelGGL(lep_enc5_fold_big_kernel, dim3((unsigned)groups * kFold5BigJobs), dim3(64), 0, g->stream3, (const lep5::SegPlan5*)plans, (uint8_t*)E.d_entries, nseg, groups, 0);
+        hipLaunchKernelGGL(lep_enc5_fold_small_kernel, dim3((unsigned)groups * kFold5SmallJobs), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p,
+                           (uint32_t*)models.p, nseg, groups, 0);
+        hipLaunchKernelGGL(lep_enc5_fold_big_kernel, dim3((unsigned)groups * kFold5BigJobs), dim3(64), 0, g->stream3, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p, nseg, groups, 0);
         }
-        hipLaunchKernelGGL(lep_enc5_fold_coef_kernel, dim3((unsigned)groups * 1260u), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)E.d_entries, nseg, groups);
+        hipLaunchKernelGGL(lep_enc5_fold_coef_kernel, dim3((unsigned)groups * 1260u), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p, nseg, groups);
         HIPCHK(g, hipEventRecord(g->ev_join, g->stream2));
         HIPCHK(g, hipEventRecord(g->ev_join3, g->stream3));
         HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0));
@@ -849,13 +839,13 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         // segments on the lane-per-segment writer beside gather stays: there the walks fill the chip and hide it.
         int K = 0;
         if (g->enc5_wchunks >= 2 && nseg <= g->enc5_wmaxseg) { K = 1; while (K * 2 <= g->enc5_wchunks && (long)nseg * K * 2 <= g->enc5_wlanes) K *= 2; }
-        if (K >= 2 && ensure(g, &E.d_wchunks, &E.wchunks_bytes, (size_t)nseg * K * sizeof(lep5::WChunk5) + 256, false)) { (void)hipGetLastError(); g->err.clear(); K = 0; }
+        if (K >= 2 && ensure(g, wchunks, (size_t)nseg * K * sizeof(lep5::WChunk5) + 256, false)) { (void)hipGetLastError(); g->err.clear(); K = 0; }
         if (K >= 2) {
-            for (int part = 0; part < nparts; ++part) walk(lep5::kGather, (uint8_t*)E.d_entries, (uint16_t*)E.d_binlist, part);
+            for (int part = 0; part < nparts; ++part) walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
             HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
-            lep5::WChunk5* recs = (lep5::WChunk5*)E.d_wchunks;
+            lep5::WChunk5* recs = (lep5::WChunk5*)wchunks.p;
             const int lane_groups = (int)(((long)nseg * K + 63) / 64);
-#define LEP_WCHUNK(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (const uint16_t*)E.d_binlist, d_seg, nseg, K, recs, d_streams, d_stream_len, d_status, g->d_bins)
+#define LEP_WCHUNK(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, K, recs, d_streams, d_stream_len, d_status, g->d_bins)
             LEP_WCHUNK(0, lane_groups); LEP_WCHUNK(1, groups); LEP_WCHUNK(2, lane_groups); LEP_WCHUNK(3, groups);
 #undef LEP_WCHUNK
             HIPCHK(g, hipEventRecord(g->ev_stage[5], st));
@@ -864,11 +854,11 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         // gather and write in parts (tile ranges of every segment): the writer is 128 wavefronts that take the same time whatever the
         // batch -- part k is written (second stream) while part k + 1 is gathered
         for (int part = 0; part < nparts; ++part) {
-            walk(lep5::kGather, (uint8_t*)E.d_entries, (uint16_t*)E.d_binlist, part);
+            walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
             HIPCHK(g, hipEventRecord(g->ev_part[part], st));
             HIPCHK(g, hipStreamWaitEvent(g->stream2, g->ev_part[part], 0));
-            hipLaunchKernelGGL(lep_enc5_write_kernel, dim3(groups), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)E.d_binlist, d_seg, nseg, d_streams,
-                               d_stream_len, d_status, g->d_bins, (uint8_t*)E.d_entries, part, nparts);
+            hipLaunchKernelGGL(lep_enc5_write_kernel, dim3(groups), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, d_streams,
+                               d_stream_len, d_status, g->d_bins, (uint8_t*)ws_entries.p, part, nparts);
         }
         HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
         HIPCHK(g, hipEventRecord(g->ev_join, g->stream2));
@@ -983,13 +973,13 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
         ns_total += (uint64_t)himg[segs[s].image].ns_total;
     }
     HIPCHK(g, hipSetDevice(g->device));
-    if (int rc = ensure(g, &g->arena[g->cur].d_models, &g->arena[g->cur].models_bytes, (size_t)nseg * kModelStride * 4)) return rc;
-    if (int rc = ensure(g, &g->arena[g->cur].d_ns, &g->arena[g->cur].ns_bytes, (size_t)ns_total * sizeof(NSum) + 16)) return rc;
-    const size_t o_img = 0, o_seg = o_img + ((nimg * sizeof(ImageDev) + 255) & ~(size_t)255),
-                 o_ns = o_seg + ((nseg * sizeof(SegDev) + 255) & ~(size_t)255),
-                 o_bins = o_ns + ((nseg * sizeof(uint64_t) + 255) & ~(size_t)255), total = o_bins + nseg * sizeof(uint32_t);
-    if (int rc = ensure(g, &g->arena[g->cur].d_meta, &g->arena[g->cur].meta_bytes, total)) return rc;
-    char* meta = (char*)g->arena[g->cur].d_meta;
+    Workspace &models = g->ws[lep_gpu::W_MODELS + g->cur], &ns = g->ws[lep_gpu::W_NS + g->cur];
+    if (int rc = ensure(g, models, (size_t)nseg * kModelStride * 4)) return rc;
+    if (int rc = ensure(g, ns, (size_t)ns_total * sizeof(NSum) + 16)) return rc;
+    lepbuf::Layout L;
+    const size_t o_img = L.add<ImageDev>((size_t)nimg), o_seg = L.add<SegDev>((size_t)nseg), o_ns = L.add<uint64_t>((size_t)nseg), o_bins = L.add<uint32_t>((size_t)nseg);
+    if (int rc = ensure(g, g->ws[lep_gpu::W_META + g->cur], L.bytes())) return rc;
+    char* meta = g->ws[lep_gpu::W_META + g->cur].at<char>(0);
     if (int rc = upload(g, meta + o_img, himg.data(), nimg * sizeof(ImageDev), st)) return rc;      // (the host vectors above go out of scope:
     if (int rc = upload(g, meta + o_seg, hseg.data(), nseg * sizeof(SegDev), st)) return rc;        //  upload() keeps a copy)
     if (int rc = upload(g, meta + o_ns, hns.data(), nseg * sizeof(uint64_t), st)) return rc;
@@ -1003,7 +993,7 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
 #endif
 #define LEP_LAUNCH_DEC4(W)                                                                                                     \
     hipLaunchKernelGGL((lep_decode_v4_kernel<W>), dim3(nseg), dim3(64), 0, st, (const ImageDev*)(meta + o_img),                  \
-                       (const SegDev*)(meta + o_seg), (uint32_t*)g->arena[g->cur].d_models, (NSum*)g->arena[g->cur].d_ns, (const uint64_t*)(meta + o_ns), \
+                       (const SegDev*)(meta + o_seg), (uint32_t*)models.p, (NSum*)ns.p, (const uint64_t*)(meta + o_ns), \
                        d_streams, d_stream_len, d_status, g->d_bins)
         // more resident waves only pay once the batch can fill them (MI355X, 4K corpus: below ~4600 segments the 4-wave
         // build, which does not spill, is faster)
@@ -1018,7 +1008,7 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
     } else {
 #define LEP_LAUNCH_ENC3(W)                                                                                                     \
     hipLaunchKernelGGL((lep_encode_v3_kernel<W>), dim3(nseg), dim3(64), 0, st, (const ImageDev*)(meta + o_img),                  \
-                       (const SegDev*)(meta + o_seg), (uint32_t*)g->arena[g->cur].d_models, (NSum*)g->arena[g->cur].d_ns, (const uint64_t*)(meta + o_ns), \
+                       (const SegDev*)(meta + o_seg), (uint32_t*)models.p, (NSum*)ns.p, (const uint64_t*)(meta + o_ns), \
                        d_streams, d_stream_len, d_status, g->d_bins)
         // like the decoder: a launch that cannot fill 8 wavefronts per SIMD takes the 4-wave build (128 VGPRs, no spills)
         int waves = g->enc_waves;
@@ -1033,7 +1023,7 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
         else if (waves == 2) {   // few segments: two wavefronts per segment (producer / bool coder), half the serial chain
             g->last_kernel = "lep_encode_v3x2_kernel";
             hipLaunchKernelGGL(lep_encode_v3x2_kernel, dim3(nseg), dim3(128), 0, st, (const ImageDev*)(meta + o_img),
-                               (const SegDev*)(meta + o_seg), (uint32_t*)g->arena[g->cur].d_models, (NSum*)g->arena[g->cur].d_ns, (const uint64_t*)(meta + o_ns),
+                               (const SegDev*)(meta + o_seg), (uint32_t*)models.p, (NSum*)ns.p, (const uint64_t*)(meta + o_ns),
                                d_streams, d_stream_len, d_status, g->d_bins);
         }
         else if (waves >= 8) { g->last_kernel = "lep_encode_v3_kernel<8>"; LEP_LAUNCH_ENC3(8); }
@@ -1117,7 +1107,6 @@ static void release_device_side(lep_gpu* g) {
     g->released = true;
     (void)hipSetDevice(g->device);
     (void)hipStreamSynchronize(g->stream);
-    for (void** p : {&g->enc5.d_plans, &g->enc5.d_entries, &g->enc5.d_binlist, &g->enc5.d_wchunks}) dev_release(g, p, nullptr);
     if (g->ev_enc5_done) (void)hipEventDestroy(g->ev_enc5_done);
     for (auto& e : g->ev_part) if (e) (void)hipEventDestroy(e);
     for (auto& e : g->ev_stage) if (e) (void)hipEventDestroy(e);
@@ -1126,14 +1115,12 @@ static void release_device_side(lep_gpu* g) {
     if (g->ev_join3) (void)hipEventDestroy(g->ev_join3);
     if (g->stream2) (void)hipStreamDestroy(g->stream2);
     if (g->stream3) (void)hipStreamDestroy(g->stream3);
-    for (void** p : {&g->arena[0].d_models, &g->arena[0].d_ns, &g->arena[0].d_meta, &g->arena[1].d_models, &g->arena[1].d_ns, &g->arena[1].d_meta, &g->d_blocks, &g->d_streams, &g->d_lens, &g->d_huff[0], &g->d_huff[1],
-                     &g->d_huffprog[0], &g->d_huffprog[1], &g->d_huffprogsimt[0], &g->d_huffprogsimt[1], &g->d_huffseq[0], &g->d_huffseq[1], &g->d_huffprogdec, &g->d_huffprogrst, &g->d_huffdec, &g->d_huffpar, &g->d_huffenc[0], &g->d_huffenc[1], &g->d_scan, &g->d_scanlen})
-        dev_release(g, p, nullptr);
+    for (Workspace& w : g->ws) dev_release(g, w);
     vmm_destroy(g);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    for (void* p : {g->h_huffprog[0], g->h_huffprog[1]}) if (p) (void)hipHostFree(p);
+    for (auto& h : g->h_huffprog) (void)h.release();
     for (lep_gpu::Staging& sl : g->staging) { if (sl.host) (void)hipHostFree(sl.host); if (sl.ev) (void)hipEventDestroy(sl.ev); sl = lep_gpu::Staging(); }
     for (void* p : g->staging_retired) (void)hipHostFree(p);
     g->staging_retired.clear();
@@ -1174,11 +1161,13 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
     if (nseg <= 0) return 0;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    const size_t o_seg = (nimg * sizeof(lep_huff_image) + 255) & ~(size_t)255, total = o_seg + nseg * sizeof(lep_huff_segment);
+    lepbuf::Layout D;
+    D.add<lep_huff_image>((size_t)nimg);
+    const size_t o_seg = D.add<lep_huff_segment>((size_t)nseg);
     const int set = g->cur & 1;                            // (the arena set the caller chose: two launches on two streams never share descriptors or scratch)
-    if (int rc = ensure(g, &g->d_huff[set], &g->huff_bytes[set], total)) return rc;
+    Workspace &huff = g->ws[lep_gpu::W_HUFF + set], &huffenc = g->ws[lep_gpu::W_HUFFENC + set];
+    if (int rc = ensure(g, huff, D.bytes())) return rc;
     // which segments the lane-per-unit kernels take (lep_huff_simt.h); the wavefront-per-segment kernel keeps the others
-    static_assert(sizeof(lep_huff_image) == sizeof(lephuff::HuffImage) && sizeof(lep_huff_segment) == sizeof(lephuff::HuffSegment), "C ABI mirrors");
     std::vector<lep_huff_segment> sv(segs, segs + nseg);
     std::vector<lephuff::SimtEncSeg> es;
     std::vector<lephuff::SimtEncWave> waves;
@@ -1208,20 +1197,21 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
             sv[(size_t)i].pad = lephuff::kHuffSegSimt;
             es.push_back(e);
         }
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_es = 0, o_wv = up(es.size() * sizeof(lephuff::SimtEncSeg)), o_ub = o_wv + up(waves.size() * sizeof(lephuff::SimtEncWave)),
-                 o_sc = o_ub + up(nunits * 8), simt_total = o_sc + up(scratch_bytes);   // (units: bit counts / positions, and the plain prefix sum of scans with restart intervals)
-    if (!es.empty()) { if (int rc = ensure(g, &g->d_huffenc[set], &g->huffenc_bytes[set], simt_total)) return rc; }
-    if (int rc = upload(g, g->d_huff[set], images, nimg * sizeof(lep_huff_image), st)) return rc;           // (the caller's arrays and ours may go away)
-    if (int rc = upload(g, (char*)g->d_huff[set] + o_seg, sv.data(), nseg * sizeof(lep_huff_segment), st)) return rc;
-    char* eb = (char*)g->d_huffenc[set];
+    lepbuf::Layout L;
+    const size_t o_es = L.add<lephuff::SimtEncSeg>(es.size()), o_wv = L.add<lephuff::SimtEncWave>(waves.size()),
+                 o_ub = L.add<uint32_t>(nunits * 2),   // (units: bit counts / positions, and the plain prefix sum of scans with restart intervals)
+                 o_sc = L.add<uint8_t>(scratch_bytes);
+    if (!es.empty()) { if (int rc = ensure(g, huffenc, L.padded())) return rc; }
+    if (int rc = upload(g, huff, images, nimg * sizeof(lep_huff_image), st)) return rc;           // (the caller's arrays and ours may go away)
+    if (int rc = upload(g, huff.at<char>(o_seg), sv.data(), nseg * sizeof(lep_huff_segment), st)) return rc;
+    char* eb = huffenc.at<char>(0);
     if (!es.empty()) {
         if (int rc = upload(g, eb + o_es, es.data(), es.size() * sizeof(lephuff::SimtEncSeg), st)) return rc;
         if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::SimtEncWave), st)) return rc;
         hipLaunchKernelGGL(lep_zero_kernel, dim3(8192), dim3(256), 0, st, (uint4*)(eb + o_sc), scratch_bytes / 16);   // (buf_bytes are multiples of 16)
     }
-    const lephuff::HuffImage* di = (const lephuff::HuffImage*)g->d_huff[set];
-    const lephuff::HuffSegment* ds = (const lephuff::HuffSegment*)((char*)g->d_huff[set] + o_seg);
+    const lephuff::HuffImage* di = huff.at<lephuff::HuffImage>(0);
+    const lephuff::HuffSegment* ds = huff.at<lephuff::HuffSegment>(o_seg);
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (!es.empty()) {
         lephuff::SimtEncSeg* des = (lephuff::SimtEncSeg*)(eb + o_es);
@@ -1326,11 +1316,11 @@ static int progdec_launch_by_level(lep_gpu* g, const std::vector<lep_huffprogdec
         }
     }
     pcut.push_back((int)plain.size()); rcut.push_back((int)rst.size());
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t o_rst = up(plain.size() * sizeof(lep_huffprogdec_scan)), o_plan = o_rst + up(rst.size() * sizeof(lep_huffprogdec_scan)),
-                 o_out = o_plan + up(plans.size() * sizeof(lephuff::ProgRstScan)), total = o_out + up((size_t)pieces * sizeof(lephuff::ProgRstOut));
-    if (int rc = ensure(g, &g->d_huffprogrst, &g->huffprogrst_bytes, total)) return rc;
-    char* base = (char*)g->d_huffprogrst;
+    lepbuf::Layout L;
+    L.add<lep_huffprogdec_scan>(plain.size());
+    const size_t o_rst = L.add<lep_huffprogdec_scan>(rst.size()), o_plan = L.add<lephuff::ProgRstScan>(plans.size()), o_out = L.add<lephuff::ProgRstOut>((size_t)pieces);
+    if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGRST], L.padded())) return rc;
+    char* base = g->ws[lep_gpu::W_HUFFPROGRST].at<char>(0);
     if (!plain.empty()) HIPCHK(g, hipMemcpyAsync(base, plain.data(), plain.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipMemcpyAsync(base + o_rst, rst.data(), rst.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipMemcpyAsync(base + o_plan, plans.data(), plans.size() * sizeof(lephuff::ProgRstScan), hipMemcpyHostToDevice, st));
@@ -1389,9 +1379,11 @@ static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, i
         deps.resize((size_t)nscan);
         pipelined = lephuff::prog_scan_deps(reinterpret_cast<const lephuff::ProgDecScan*>(sorted.data()), order.data(), nscan, deps.data());
     }
-    const size_t o_deps = ((size_t)nscan * sizeof(lep_huffprogdec_scan) + 255) & ~(size_t)255, o_prog = o_deps + (((size_t)nscan * sizeof(lephuff::ProgDeps) + 255) & ~(size_t)255),
-                 total = o_prog + (size_t)nscan * 4 + 4;   // (+ the ticket counter behind the progress words)
-    if (int rc = ensure(g, &g->d_huffprogdec, &g->huffprogdec_bytes, total)) return rc;
+    lepbuf::Layout L;
+    L.add<lep_huffprogdec_scan>((size_t)nscan);
+    const size_t o_deps = L.add<lephuff::ProgDeps>((size_t)nscan), o_prog = L.add<uint32_t>((size_t)nscan + 1);   // (+ the ticket counter behind the progress words)
+    Workspace& progdec = g->ws[lep_gpu::W_HUFFPROGDEC];
+    if (int rc = ensure(g, progdec, L.bytes())) return rc;
     // which scans the window of speculative codes decodes (lep_huffprogdec_win.h); lep_huffprogdec.h's uniform vector code keeps the others
     bool any_win = false;
     for (lep_huffprogdec_scan& sc : sorted) {
@@ -1399,17 +1391,17 @@ static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, i
         sc.pad = w ? lephuff::kProgDecWin : 0;
         any_win = any_win || w;
     }
-    HIPCHK(g, hipMemcpyAsync(g->d_huffprogdec, sorted.data(), (size_t)nscan * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(progdec, sorted.data(), (size_t)nscan * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
     if (pipelined) {
-        HIPCHK(g, hipMemcpyAsync((char*)g->d_huffprogdec + o_deps, deps.data(), (size_t)nscan * sizeof(lephuff::ProgDeps), hipMemcpyHostToDevice, st));
-        HIPCHK(g, hipMemsetAsync((char*)g->d_huffprogdec + o_prog, 0, (size_t)nscan * 4 + 4, st));
+        HIPCHK(g, hipMemcpyAsync(progdec.at<char>(o_deps), deps.data(), (size_t)nscan * sizeof(lephuff::ProgDeps), hipMemcpyHostToDevice, st));
+        HIPCHK(g, hipMemsetAsync(progdec.at<char>(o_prog), 0, (size_t)nscan * 4 + 4, st));
     }
     HIPCHK(g, hipStreamSynchronize(st));
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (pipelined) {
         hipLaunchKernelGGL(any_win ? lep_huffprogdec_win_pipelined_kernel : lep_huffman_progressive_pipelined_kernel, dim3(nscan), dim3(64), 0, st,
-                           (const lephuff::ProgDecScan*)g->d_huffprogdec, (lephuff::HuffDecRow*)d_rows,
-                           (const lephuff::ProgDeps*)((char*)g->d_huffprogdec + o_deps), (uint32_t*)((char*)g->d_huffprogdec + o_prog), (uint32_t*)((char*)g->d_huffprogdec + o_prog) + nscan);
+                           progdec.at<const lephuff::ProgDecScan>(0), (lephuff::HuffDecRow*)d_rows,
+                           progdec.at<const lephuff::ProgDeps>(o_deps), progdec.at<uint32_t>(o_prog), progdec.at<uint32_t>(o_prog) + nscan);
         HIPCHK(g, hipGetLastError());
         HIPCHK(g, hipEventRecord(g->ev1, st));
         g->timed = true;
@@ -1420,7 +1412,7 @@ static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, i
         const int n = cut[c + 1] - cut[c];
         if (n <= 0) continue;
         hipLaunchKernelGGL(any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(n), dim3(64), 0, st,
-                           (const lephuff::ProgDecScan*)g->d_huffprogdec + cut[c], (lephuff::HuffDecRow*)d_rows);
+                           progdec.at<const lephuff::ProgDecScan>(0) + cut[c], (lephuff::HuffDecRow*)d_rows);
     }
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
@@ -1437,19 +1429,16 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     if (nscan <= 0) return 0;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    const size_t o_scan = (nimg * sizeof(lep_huffprog_image) + 255) & ~(size_t)255, total = o_scan + nscan * sizeof(lep_huffprog_scan);
+    lepbuf::Layout D;
+    D.add<lep_huffprog_image>((size_t)nimg);
+    const size_t o_scan = D.add<lep_huffprog_scan>((size_t)nscan), total = D.bytes();
     const int turn = (g->huffprog_turn ^= 1);
-    if (int rc = ensure(g, &g->d_huffprog[turn], &g->huffprog_bytes[turn], total)) return rc;
-    char* const d_desc = (char*)g->d_huffprog[turn];
+    if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROG + turn], total)) return rc;
+    char* const d_desc = g->ws[lep_gpu::W_HUFFPROG + turn].at<char>(0);
     // descriptors through a pinned copy of this set (its previous user, two launches ago, has been waited for by then): the
     // caller's arrays may go away, and nothing here waits for the kernels already queued on the stream
-    if (g->h_huffprog_bytes[turn] < total) {
-        if (g->h_huffprog[turn]) HIPCHK(g, hipHostFree(g->h_huffprog[turn]));
-        g->h_huffprog[turn] = nullptr; g->h_huffprog_bytes[turn] = 0;
-        HIPCHK(g, hipHostMalloc(&g->h_huffprog[turn], total + total / 8, hipHostMallocDefault));
-        g->h_huffprog_bytes[turn] = total + total / 8;
-    }
-    char* const h_desc = (char*)g->h_huffprog[turn];
+    HIPCHK(g, g->h_huffprog[turn].ensure(total, total / 8));
+    char* const h_desc = g->h_huffprog[turn];
     memcpy(h_desc, images, nimg * sizeof(lep_huffprog_image));
     memcpy(h_desc + o_scan, scans, nscan * sizeof(lep_huffprog_scan));
     // which scans the lane-per-unit kernels take (lep_huffprog_simt.h, with a restart interval lep_huffprog_simt_rst.h); the wavefront-per-scan
@@ -1481,9 +1470,12 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         hs[i].pad = lephuff::kProgScanSeq;
     }
     if (!seq_seg.empty()) {
-        const size_t n = seq_seg.size(), o_cap = n * 4, o_len = o_cap + n * 4, o_end = (o_len + n * 4 + 15) & ~(size_t)15, bytes = o_end + n * sizeof(lep_huff_end);
-        if (int rc = ensure(g, &g->d_huffseq[turn], &g->huffseq_bytes[turn], bytes)) return rc;
-        char* b = (char*)g->d_huffseq[turn];
+        const size_t n = seq_seg.size();
+        lepbuf::Layout S;   // which | caps | byte counts | (16-byte aligned) end states
+        S.add<uint32_t>(n, 4);
+        const size_t o_cap = S.add<uint32_t>(n, 4), o_len = S.add<uint32_t>(n, 4), o_end = S.add<lep_huff_end>(n, 16);
+        if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFSEQ + turn], S.bytes())) return rc;
+        char* b = g->ws[lep_gpu::W_HUFFSEQ + turn].at<char>(0);
         if (int rc = upload(g, b, seq_which.data(), n * 4, st)) return rc;
         if (int rc = upload(g, b + o_cap, seq_cap.data(), n * 4, st)) return rc;
         if (int rc = lep_gpu_huffman_encode_device(g, seq_img.data(), (int)n, seq_seg.data(), (int)n, d_out, (uint32_t*)(b + o_len), (lep_huff_end*)(b + o_end), st)) return rc;
@@ -1533,14 +1525,14 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
             a = b;
         }
     }
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_ps = 0, o_wv = up(ps.size() * sizeof(lephuff::ProgSimtScan)), o_rg = o_wv + up((waves.size() + waves_rst.size()) * sizeof(lephuff::ProgSimtWave)),
-                 o_rw = o_rg + up(regions.size() * sizeof(lephuff::ProgSimtRegion)), o_un = o_rw + up(rst_which.size() * 4),
-                 o_sc = o_un + up(nunits * 4 * (rst_which.empty() ? lephuff::kProgSimtUnitWords : lephuff::kProgSimtRstUnitWords)), simt_total = o_sc + up(scratch_bytes);
+    lepbuf::Layout L;
+    const size_t o_ps = L.add<lephuff::ProgSimtScan>(ps.size()), o_wv = L.add<lephuff::ProgSimtWave>(waves.size() + waves_rst.size()),
+                 o_rg = L.add<lephuff::ProgSimtRegion>(regions.size()), o_rw = L.add<uint32_t>(rst_which.size()),
+                 o_un = L.add<uint32_t>(nunits * (rst_which.empty() ? lephuff::kProgSimtUnitWords : lephuff::kProgSimtRstUnitWords)), o_sc = L.add<uint8_t>(scratch_bytes);
     g->huffprog_forms[2] = (uint32_t)((size_t)nscan - ps.size() - seq_seg.size());
-    if (!ps.empty()) { if (int rc = ensure(g, &g->d_huffprogsimt[turn], &g->huffprogsimt_bytes[turn], simt_total)) return rc; }
+    if (!ps.empty()) { if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGSIMT + turn], L.padded())) return rc; }
     HIPCHK(g, hipMemcpyAsync(d_desc, h_desc, total, hipMemcpyHostToDevice, st));
-    char* eb = (char*)g->d_huffprogsimt[turn];
+    char* eb = g->ws[lep_gpu::W_HUFFPROGSIMT + turn].at<char>(0);
     if (!ps.empty()) {
         if (int rc = upload(g, eb + o_ps, ps.data(), ps.size() * sizeof(lephuff::ProgSimtScan), st)) return rc;
         if (!waves.empty()) { if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::ProgSimtWave), st)) return rc; }
@@ -1593,11 +1585,12 @@ int lep_gpu_huffman_decode_device(lep_gpu* g, const lep_huffdec_image* images, i
     if (nimg <= 0) return 0;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    if (int rc = ensure(g, &g->d_huffdec, &g->huffdec_bytes, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
-    HIPCHK(g, hipMemcpyAsync(g->d_huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
+    Workspace& huffdec = g->ws[lep_gpu::W_HUFFDEC];
+    if (int rc = ensure(g, huffdec, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
+    HIPCHK(g, hipMemcpyAsync(huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipStreamSynchronize(st));   // the caller's array may go away
     HIPCHK(g, hipEventRecord(g->ev0, st));
-    hipLaunchKernelGGL(lep_huffman_decode_kernel, dim3(nimg), dim3(64), 0, st, (const lephuff::HuffDecImage*)g->d_huffdec,
+    hipLaunchKernelGGL(lep_huffman_decode_kernel, dim3(nimg), dim3(64), 0, st, (const lephuff::HuffDecImage*)huffdec.p,
                        (lephuff::HuffDecRow*)d_rows);
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
@@ -1640,17 +1633,18 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
         nsub_all += n;
     }
     if (nsub_all > 0x7fffffffu) return LEP_ASSERTION_FAILURE;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_si = 0, o_wv = up(si.size() * sizeof(lephuff::SimtImage)), o_s0 = o_wv + up(waves.size() * sizeof(lephuff::SimtWave)),
-                 o_s1 = o_s0 + up(nsub_all * sizeof(lephuff::SimtSub)), o_pl = o_s1 + up(nsub_all * sizeof(lephuff::SimtSub)), total = o_pl + up(nsub_all * sizeof(lephuff::SimtPlace));
-    if (int rc = ensure(g, &g->d_huffdec, &g->huffdec_bytes, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
-    if (int rc = ensure(g, &g->d_huffpar, &g->huffpar_bytes, total)) return rc;
-    char* base = (char*)g->d_huffpar;
-    HIPCHK(g, hipMemcpyAsync(g->d_huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
+    lepbuf::Layout P;
+    const size_t o_si = P.add<lephuff::SimtImage>(si.size()), o_wv = P.add<lephuff::SimtWave>(waves.size()), o_s0 = P.add<lephuff::SimtSub>(nsub_all),
+                 o_s1 = P.add<lephuff::SimtSub>(nsub_all), o_pl = P.add<lephuff::SimtPlace>(nsub_all);
+    Workspace& huffdec = g->ws[lep_gpu::W_HUFFDEC];
+    if (int rc = ensure(g, huffdec, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
+    if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPAR], P.padded())) return rc;
+    char* base = g->ws[lep_gpu::W_HUFFPAR].at<char>(0);
+    HIPCHK(g, hipMemcpyAsync(huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipMemcpyAsync(base + o_si, si.data(), si.size() * sizeof(lephuff::SimtImage), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipMemcpyAsync(base + o_wv, waves.data(), waves.size() * sizeof(lephuff::SimtWave), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipStreamSynchronize(st));   // the caller's array (and ours) may go away
-    const lephuff::HuffDecImage* di = (const lephuff::HuffDecImage*)g->d_huffdec;
+    const lephuff::HuffDecImage* di = (const lephuff::HuffDecImage*)huffdec.p;
     lephuff::SimtImage* dsi = (lephuff::SimtImage*)(base + o_si);
     const lephuff::SimtWave* dwv = (const lephuff::SimtWave*)(base + o_wv);
     lephuff::SimtSub* buf[2] = {(lephuff::SimtSub*)(base + o_s0), (lephuff::SimtSub*)(base + o_s1)};
@@ -1757,10 +1751,11 @@ int lep_gpu_selftest(lep_gpu* g) {
 // unit positions, plain prefix sums, bit buffers + marker maps; the layout is that function's), copied to `out`; returns the bytes copied.
 // scripts/diag_scan_encode_isolate.py compares two builds of the library pass by pass with it.
 size_t lep_gpu_debug_huffenc(lep_gpu* g, void* out, size_t cap) {
-    if (!g || !g->d_huffenc[g->cur & 1]) return 0;
+    if (!g || !g->ws[lep_gpu::W_HUFFENC + (g->cur & 1)].p) return 0;
+    const Workspace& w = g->ws[lep_gpu::W_HUFFENC + (g->cur & 1)];
     if (hipSetDevice(g->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
-    const size_t n = std::min(cap, g->huffenc_bytes[g->cur & 1]);
-    return hipMemcpy(out, g->d_huffenc[g->cur & 1], n, hipMemcpyDeviceToHost) == hipSuccess ? n : 0;
+    const size_t n = std::min(cap, w.cap);
+    return hipMemcpy(out, w.p, n, hipMemcpyDeviceToHost) == hipSuccess ? n : 0;
 }
 
 // profiling builds (-DLEP_PROF) only: per-phase shader-clock totals folded over the segments of the last decoder launch
@@ -1783,9 +1778,7 @@ int lep_gpu_debug_prof(lep_gpu* g, uint64_t* out /* [64][32] */) {
 int lep_gpu_trim(lep_gpu* g) {
     HIPCHK(g, hipSetDevice(g->device));
     HIPCHK(g, hipDeviceSynchronize());
-    void** ps[] = {&g->enc5.d_entries, &g->enc5.d_binlist, &g->arena[0].d_models, &g->arena[1].d_models, &g->arena[0].d_ns, &g->arena[1].d_ns};
-    size_t* ns[] = {&g->enc5.entries_bytes, &g->enc5.binlist_bytes, &g->arena[0].models_bytes, &g->arena[1].models_bytes, &g->arena[0].ns_bytes, &g->arena[1].ns_bytes};
-    for (int i = 0; i < 6; ++i) dev_release(g, ps[i], ns[i]);
+    for (int w = 0; w < lep_gpu::W_TRIMMED; ++w) dev_release(g, g->ws[w]);
     return 0;
 }
 // ... and hand them to the driver (the pool too): for a process that wants the device's memory for something else
@@ -1818,15 +1811,16 @@ static int stage_images(lep_gpu* g, const lep_image_desc* images, int nimg, std:
     size_t total = 0;
     for (int i = 0; i < nimg; ++i)
         for (int c = 0; c < images[i].ncomp && c < 3; ++c) total += (size_t)images[i].width_blocks[c] * images[i].height_blocks[c] * 128;
-    if (int rc = ensure(g, &g->d_blocks, &g->blocks_bytes, total + 256)) return rc;
+    if (int rc = ensure(g, g->ws[lep_gpu::W_BLOCKS], total + 256)) return rc;
+    char* const d_blocks = g->ws[lep_gpu::W_BLOCKS].at<char>(0);
     dev->assign(images, images + nimg);
     size_t off = 0;
     for (int i = 0; i < nimg; ++i)
         for (int c = 0; c < images[i].ncomp && c < 3; ++c) {
             size_t bytes = (size_t)images[i].width_blocks[c] * images[i].height_blocks[c] * 128;
-            (*dev)[i].blocks[c] = (int16_t*)((char*)g->d_blocks + off);
-            if (upload) HIPCHK(g, hipMemcpyAsync((char*)g->d_blocks + off, images[i].blocks[c], bytes, hipMemcpyHostToDevice, g->stream));
-            else HIPCHK(g, hipMemsetAsync((char*)g->d_blocks + off, 0, bytes, g->stream));
+            (*dev)[i].blocks[c] = (int16_t*)(d_blocks + off);
+            if (upload) HIPCHK(g, hipMemcpyAsync(d_blocks + off, images[i].blocks[c], bytes, hipMemcpyHostToDevice, g->stream));
+            else HIPCHK(g, hipMemsetAsync(d_blocks + off, 0, bytes, g->stream));
             off += bytes;
         }
     return 0;
@@ -1840,11 +1834,12 @@ int lep_gpu_encode_host(lep_gpu* g, const lep_image_desc* images, int nimg, cons
     if (int rc = stage_images(g, images, nimg, &dev, true)) return rc;
     std::vector<uint64_t> offs(nseg + 1, 0);
     for (int s = 0; s < nseg; ++s) offs[s + 1] = offs[s] + out[s].cap;
-    if (int rc = ensure(g, &g->d_streams, &g->streams_bytes, offs[nseg] + 16)) return rc;
-    if (int rc = ensure(g, &g->d_lens, &g->lens_bytes, (size_t)nseg * 8 + 16)) return rc;
-    uint32_t* d_len = (uint32_t*)g->d_lens;
+    if (int rc = ensure(g, g->ws[lep_gpu::W_STREAMS], offs[nseg] + 16)) return rc;
+    if (int rc = ensure(g, g->ws[lep_gpu::W_LENS], (size_t)nseg * 8 + 16)) return rc;
+    uint8_t* const d_streams = g->ws[lep_gpu::W_STREAMS].at<uint8_t>(0);
+    uint32_t* d_len = g->ws[lep_gpu::W_LENS].at<uint32_t>(0);
     int32_t* d_status = (int32_t*)(d_len + nseg);
-    int rc = launch<false>(g, dev.data(), nimg, segs, nseg, (uint8_t*)g->d_streams, offs.data(), d_len, d_status, g->stream);
+    int rc = launch<false>(g, dev.data(), nimg, segs, nseg, d_streams, offs.data(), d_len, d_status, g->stream);
     if (rc) return rc;
     std::vector<uint32_t> lens(nseg);
     std::vector<int32_t> st(nseg);
@@ -1856,7 +1851,7 @@ int lep_gpu_encode_host(lep_gpu* g, const lep_image_desc* images, int nimg, cons
         if (status) status[s] = st[s];
         if (st[s] && !worst) worst = st[s];
         out[s].len = st[s] ? 0 : lens[s];
-        if (!st[s] && lens[s]) HIPCHK(g, hipMemcpyAsync(out[s].data, (char*)g->d_streams + offs[s], lens[s], hipMemcpyDeviceToHost, g->stream));
+        if (!st[s] && lens[s]) HIPCHK(g, hipMemcpyAsync(out[s].data, d_streams + offs[s], lens[s], hipMemcpyDeviceToHost, g->stream));
     }
     HIPCHK(g, hipStreamSynchronize(g->stream));
     return worst;
@@ -1871,15 +1866,16 @@ int lep_gpu_decode_host(lep_gpu* g, const lep_image_desc* images, int nimg, cons
     std::vector<uint64_t> offs(nseg + 1, 0);
     std::vector<uint32_t> lens(nseg);
     for (int s = 0; s < nseg; ++s) { offs[s + 1] = offs[s] + in[s].len; lens[s] = (uint32_t)in[s].len; }
-    if (int rc = ensure(g, &g->d_streams, &g->streams_bytes, offs[nseg] + 16)) return rc;
-    if (int rc = ensure(g, &g->d_lens, &g->lens_bytes, (size_t)nseg * 8 + 16)) return rc;
-    uint32_t* d_len = (uint32_t*)g->d_lens;
+    if (int rc = ensure(g, g->ws[lep_gpu::W_STREAMS], offs[nseg] + 16)) return rc;
+    if (int rc = ensure(g, g->ws[lep_gpu::W_LENS], (size_t)nseg * 8 + 16)) return rc;
+    uint8_t* const d_streams = g->ws[lep_gpu::W_STREAMS].at<uint8_t>(0);
+    uint32_t* d_len = g->ws[lep_gpu::W_LENS].at<uint32_t>(0);
     int32_t* d_status = (int32_t*)(d_len + nseg);
     for (int s = 0; s < nseg; ++s)
-        if (in[s].len) HIPCHK(g, hipMemcpyAsync((char*)g->d_streams + offs[s], in[s].data, in[s].len, hipMemcpyHostToDevice, g->stream));
+        if (in[s].len) HIPCHK(g, hipMemcpyAsync(d_streams + offs[s], in[s].data, in[s].len, hipMemcpyHostToDevice, g->stream));
     HIPCHK(g, hipMemcpyAsync(d_len, lens.data(), nseg * 4, hipMemcpyHostToDevice, g->stream));
     HIPCHK(g, hipStreamSynchronize(g->stream));
-    int rc = launch<true>(g, dev.data(), nimg, segs, nseg, (uint8_t*)g->d_streams, offs.data(), d_len, d_status, g->stream);
+    int rc = launch<true>(g, dev.data(), nimg, segs, nseg, d_streams, offs.data(), d_len, d_status, g->stream);
     if (rc) return rc;
     std::vector<int32_t> st(nseg);
     HIPCHK(g, hipMemcpyAsync(st.data(), d_status, nseg * 4, hipMemcpyDeviceToHost, g->stream));

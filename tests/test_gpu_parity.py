@@ -291,7 +291,7 @@ def test_gpu_overlapped_chunks_of_unequal_length_with_verification(gpu_codec, mo
     round-trip check) on the second stream BEFORE the long chunk in front of it does on the first.  Until the end of round 6 the scan
     encoder's descriptors and scratch were one buffer for both streams: the short chunk's replaced the ones the long chunk's kernels were
     still to read -- a memory fault (HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION), seen once in the closing visit and then every time under
-    scripts/stress_overlap_verify.py.  They are per workspace set now (lep_gpu.hip d_huff / d_huffenc)."""
+    scripts/stress_overlap_verify.py.  They are per workspace set now (lep_gpu.hip W_HUFF / W_HUFFENC)."""
     monkeypatch.setenv("LEP_BATCH_OVERLAP", "1")
     names = golden_cases()
     big = [corpus.synth_jpeg(3840, 2160, 900 + i) for i in range(2)]
