@@ -163,8 +163,8 @@ int lep_gpu_huffman_encode_device(lep_gpu *g, const lep_huff_image *images, int 
 /* The same for PROGRESSIVE files (BASELINE.json configs[4]; replaces the scan loop of recode_jpeg, src/lepton/jpgcoder.cc:3309-3716,
  * with encode_dc_prg_*, encode_ac_prg_fs / _sa, encode_eobrun, encode_crbits :4991-5400): every scan of a progressive file is a
  * function of the finished frame alone, so its bytes (FF00-stuffed, restart markers included) are written to d_out +
- * scans[i].out_off by one LANE per 32 blocks (lep_huffprog_simt.h: count / place / assign / code / stuff; scans with a restart
- * interval: lep_huffprog_simt_rst.h, units cut at the intervals' ends); d_out_len[i] = byte count, bit 31 set = the scan outgrew its slot or its
+ * scans[i].out_off by one LANE per 32 blocks (lep_huffprog_simt.h: count / place / assign / code / stuff; in a scan with a restart
+ * interval the units are cut at the intervals' ends); d_out_len[i] = byte count, bit 31 set = the scan outgrew its slot or its
  * scratch (let the host re-coder do that file).  d_corr: scratch for correction bits held back behind end-of-band runs
  * (scans[i].corr_off / corr_cap dwords).  lep_file_recode_plan_progressive fills both structs. */
 typedef struct lep_huffprog_image {
@@ -193,8 +193,8 @@ typedef struct lep_huffprog_scan {
 int lep_gpu_huffman_progressive_encode_device(lep_gpu *g, const lep_huffprog_image *images, int nimg, const lep_huffprog_scan *scans,
                                               int nscan, uint8_t *d_out, uint32_t *d_corr, uint32_t *d_out_len, void *hip_stream);
 /* How many scans of this codec's most recent lep_gpu_huffman_progressive_encode_device call (lep_decompress_batch and the round-trip check of
- * lep_compress_batch make one per chunk) went to each writer: counts[0] one lane per 32 blocks (lep_huffprog_simt.h), [1] the same for scans
- * with a restart interval (lep_huffprog_simt_rst.h; LEP_HUFFPROG_SIMT_RST=0 when the codec is made: off), [2] one wavefront per scan
+ * lep_compress_batch make one per chunk) went to each writer: counts[0] one lane per 32 blocks (lep_huffprog_simt.h), scans without a restart
+ * interval, [1] the same kernels, scans with one (LEP_HUFFPROG_SIMT_RST=0 when the codec is made: these go to [2]), [2] one wavefront per scan
  * (lep_huffprog.h), [3] the sequential scan encoders (scans of sequential frames). */
 int lep_gpu_huffman_progressive_encode_forms(lep_gpu *g, uint32_t counts[4]);
 /* JPEG Huffman scan decode on the GPU (replaces decode_jpeg / decode_block_seq, src/lepton/jpgcoder.cc:2799-3302,

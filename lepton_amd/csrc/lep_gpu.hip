@@ -27,7 +27,6 @@
 #include "lep_huff_simt.h"
 #include "lep_huffprog.h"
 #include "lep_huffprog_simt.h"
-#include "lep_huffprog_simt_rst.h"
 #include "lep_huffprogdec.h"
 #include "lep_huffprogdec_win.h"
 #include "lep_huffprogdec_rst.h"
@@ -346,7 +345,7 @@ __global__ void lep_huffprog_seq_lens_kernel(const uint32_t* __restrict__ which,
     const bool over = ends[i].attempted > cap[i] || (ends[i].pad & (lephuff::kHuffEndCut | lephuff::kHuffEndRefused)) != 0;
     out_len[which[i]] = lens[i] | (over ? 0x80000000u : 0u);
 }
-// ... with one lane per run of blocks (lep_huffprog_simt.h): count / place / code / stuff
+// ... with one lane per run of blocks (lep_huffprog_simt.h): count / place / code / stuff, scans with and without a restart interval alike
 template <bool WRITE>
 __global__ __launch_bounds__(64) void lep_huffprog_simt_units_kernel(const lephuff::ProgImage* __restrict__ images, const lephuff::ProgScan* __restrict__ scans,
                                                                      const lephuff::ProgSimtScan* __restrict__ ps, const lephuff::ProgSimtWave* __restrict__ waves,
@@ -360,25 +359,7 @@ __global__ __launch_bounds__(64) void lep_huffprog_simt_units_kernel(const lephu
 __global__ __launch_bounds__(64) void lep_huffprog_simt_place_kernel(const lephuff::ProgScan* __restrict__ scans, lephuff::ProgSimtScan* ps, uint32_t* unit_words, size_t units) {
     lephuff::ProgSimtUnits U;
     U.set(unit_words, units);
-    if (ps[blockIdx.x].rsti) return;   // lep_huffprog_simt_rst_place_kernel's
     lephuff::prog_simt_place(scans, ps + blockIdx.x, U);
-}
-// ... scans with a restart interval (lep_huffprog_simt_rst.h): their own count / code and place; assign, zero and stuff are shared
-template <bool WRITE>
-__global__ __launch_bounds__(64) void lep_huffprog_simt_rst_units_kernel(const lephuff::ProgImage* __restrict__ images, const lephuff::ProgScan* __restrict__ scans,
-                                                                         const lephuff::ProgSimtScan* __restrict__ ps, const lephuff::ProgSimtWave* __restrict__ waves,
-                                                                         uint32_t* unit_words, size_t units, uint8_t* scratch) {
-    __shared__ lephuff::ProgSimtShared sh;
-    const lephuff::ProgSimtWave w = waves[blockIdx.x];
-    lephuff::ProgSimtUnits U;
-    U.set(unit_words, units);
-    lephuff::prog_simt_rst_units<WRITE>(images, scans, ps + w.pscan, &sh, U, scratch, w.first_unit);
-}
-__global__ __launch_bounds__(64) void lep_huffprog_simt_rst_place_kernel(const lephuff::ProgScan* __restrict__ scans, lephuff::ProgSimtScan* ps, const uint32_t* __restrict__ which,
-                                                                         uint32_t* unit_words, size_t units) {
-    lephuff::ProgSimtUnits U;
-    U.set(unit_words, units);
-    lephuff::prog_simt_rst_place(scans, ps + which[blockIdx.x], U);
 }
 // the bit buffers are cleared as far as the scans reach (pass 2 knows; the buffers are sized by what a scan MAY need, ten times that), and the
 // marker maps behind them (an eighth of the buffer; workgroups count on through them)
@@ -531,7 +512,7 @@ struct lep_gpu {
     uint32_t huffprogdec_rst_floor = lephuff::kRstPieceFloor;   // LEP_HUFFPROGDEC_RST_FLOOR: bytes of scan per piece (measurements)
     int huffprogdec_win = 1;            // LEP_HUFFPROGDEC_WIN=0: progressive scans decoded by lep_huffprogdec.h's uniform vector code only
     int huffprog_simt = 1;              // LEP_HUFFPROG_SIMT=0: every progressive scan's bytes from the wavefront-per-scan kernel (lep_huffprog.h)
-    int huffprog_simt_rst = 1;          // LEP_HUFFPROG_SIMT_RST=0: scans with a restart interval from the wavefront-per-scan kernel (lep_huffprog_simt_rst.h off)
+    int huffprog_simt_rst = 1;          // LEP_HUFFPROG_SIMT_RST=0: scans with a restart interval from the wavefront-per-scan kernel
     uint32_t huffprog_forms[4] = {0, 0, 0, 0};   // the last progressive write's scans by form: lane, lane with intervals, wavefront, sequential
     int huffenc_simt = 1;               // LEP_HUFFENC_SIMT=0: every segment's scan bytes from the wavefront-per-segment kernel (lep_huff.h)
     int simt_sub_bits = 0;              // LEP_HUFFDEC_SIMT_BITS: bits per subsequence of the lane-per-subsequence scan decoder (0 = from the launch's size)
@@ -1441,12 +1422,11 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     char* const h_desc = g->h_huffprog[turn];
     memcpy(h_desc, images, nimg * sizeof(lep_huffprog_image));
     memcpy(h_desc + o_scan, scans, nscan * sizeof(lep_huffprog_scan));
-    // which scans the lane-per-unit kernels take (lep_huffprog_simt.h, with a restart interval lep_huffprog_simt_rst.h); the wavefront-per-scan
-    // kernel keeps the others
+    // which scans the lane-per-unit kernels take (lep_huffprog_simt.h); the wavefront-per-scan kernel keeps the others
     lephuff::ProgScan* hs = reinterpret_cast<lephuff::ProgScan*>(h_desc + o_scan);
     std::vector<lephuff::ProgSimtScan> ps;
-    std::vector<lephuff::ProgSimtWave> waves, waves_rst;   // (uploaded as one array, waves_rst behind waves)
-    std::vector<uint32_t> rst_which;                       // the entries of ps that lep_huffprog_simt_rst.h's passes 1 - 3 take
+    std::vector<lephuff::ProgSimtWave> waves;
+    bool intervals = false;   // a scan with a restart interval among them: the unit arrays' sixth word
     std::vector<lephuff::ProgSimtRegion> regions;
     for (uint32_t& c : g->huffprog_forms) c = 0;
     size_t nunits = 0, scratch_bytes = 0;
@@ -1500,13 +1480,13 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
                 const int i = order[k];
                 uint32_t nb = 0, nu = 0, interval = 0;
                 const lephuff::ProgImage& pim = reinterpret_cast<const lephuff::ProgImage&>(images[im]);
-                if (!lephuff::prog_simt_takes(pim, hs[i], &nb, &nu) && !(g->huffprog_simt_rst && lephuff::prog_simt_rst_takes(pim, hs[i], &nb, &nu, &interval))) continue;
+                if (!lephuff::prog_simt_takes(pim, hs[i], &nb, &nu, &interval) || (interval && !g->huffprog_simt_rst)) continue;
                 if (nunits + nu > 0x7fffffffu) continue;
                 lephuff::ProgSimtScan e;
                 memset(&e, 0, sizeof e);
                 e.scan = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = nu; e.nblocks = nb; e.rsti = interval;
-                for (uint32_t f = 0; f < nu; f += 64) (interval ? waves_rst : waves).push_back(lephuff::ProgSimtWave{(uint32_t)ps.size(), f});
-                if (interval) { rst_which.push_back((uint32_t)ps.size()); maps = true; }
+                for (uint32_t f = 0; f < nu; f += 64) waves.push_back(lephuff::ProgSimtWave{(uint32_t)ps.size(), f});
+                if (interval) maps = intervals = true;
                 ++g->huffprog_forms[interval ? 1 : 0];
                 nunits += nu;
                 sum_cap += (uint64_t)hs[i].out_cap + 96; bound = std::max<uint64_t>(bound, file_bound[(size_t)i]);
@@ -1526,20 +1506,15 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         }
     }
     lepbuf::Layout L;
-    const size_t o_ps = L.add<lephuff::ProgSimtScan>(ps.size()), o_wv = L.add<lephuff::ProgSimtWave>(waves.size() + waves_rst.size()),
-                 o_rg = L.add<lephuff::ProgSimtRegion>(regions.size()), o_rw = L.add<uint32_t>(rst_which.size()),
-                 o_un = L.add<uint32_t>(nunits * (rst_which.empty() ? lephuff::kProgSimtUnitWords : lephuff::kProgSimtRstUnitWords)), o_sc = L.add<uint8_t>(scratch_bytes);
+    const size_t o_ps = L.add<lephuff::ProgSimtScan>(ps.size()), o_wv = L.add<lephuff::ProgSimtWave>(waves.size()), o_rg = L.add<lephuff::ProgSimtRegion>(regions.size()),
+                 o_un = L.add<uint32_t>(nunits * lephuff::prog_simt_unit_words(intervals)), o_sc = L.add<uint8_t>(scratch_bytes);
     g->huffprog_forms[2] = (uint32_t)((size_t)nscan - ps.size() - seq_seg.size());
     if (!ps.empty()) { if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGSIMT + turn], L.padded())) return rc; }
     HIPCHK(g, hipMemcpyAsync(d_desc, h_desc, total, hipMemcpyHostToDevice, st));
     char* eb = g->ws[lep_gpu::W_HUFFPROGSIMT + turn].at<char>(0);
     if (!ps.empty()) {
         if (int rc = upload(g, eb + o_ps, ps.data(), ps.size() * sizeof(lephuff::ProgSimtScan), st)) return rc;
-        if (!waves.empty()) { if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::ProgSimtWave), st)) return rc; }
-        if (!rst_which.empty()) {
-            if (int rc = upload(g, eb + o_wv + waves.size() * sizeof(lephuff::ProgSimtWave), waves_rst.data(), waves_rst.size() * sizeof(lephuff::ProgSimtWave), st)) return rc;
-            if (int rc = upload(g, eb + o_rw, rst_which.data(), rst_which.size() * 4, st)) return rc;
-        }
+        if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::ProgSimtWave), st)) return rc;
         if (int rc = upload(g, eb + o_rg, regions.data(), regions.size() * sizeof(lephuff::ProgSimtRegion), st)) return rc;
     }
     const lephuff::ProgImage* di = (const lephuff::ProgImage*)d_desc;
@@ -1553,20 +1528,11 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         uint32_t longest = 0;
         for (const lephuff::ProgSimtRegion& r : regions) longest = (uint32_t)std::max<uint64_t>(longest, r.bytes);
         const uint32_t chunk16 = 4096;   // 64 KB of a bit buffer per workgroup of the clearing kernel
-        const lephuff::ProgSimtWave* dwr = dwv + waves.size();
-        const uint32_t* drw = (const uint32_t*)(eb + o_rw);
-        if (!waves.empty()) {
-            hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
-            hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, nunits);
-        }
-        if (!rst_which.empty()) {
-            hipLaunchKernelGGL((lep_huffprog_simt_rst_units_kernel<false>), dim3((unsigned)waves_rst.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwr, dun, nunits, dsc);
-            hipLaunchKernelGGL(lep_huffprog_simt_rst_place_kernel, dim3((unsigned)rst_which.size()), dim3(64), 0, st, ds, dps, drw, dun, nunits);
-        }
+        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
+        hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, nunits);
         hipLaunchKernelGGL(lep_huffprog_simt_assign_kernel, dim3((unsigned)(regions.size() + 63) / 64), dim3(64), 0, st, (const lephuff::ProgSimtRegion*)(eb + o_rg), (int)regions.size(), dps);
         hipLaunchKernelGGL(lep_huffprog_simt_zero_kernel, dim3((unsigned)ps.size(), (longest / 16 + chunk16 - 1) / chunk16 + 1), dim3(256), 0, st, (const lephuff::ProgSimtScan*)dps, dsc, chunk16);
-        if (!waves.empty()) hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
-        if (!rst_which.empty()) hipLaunchKernelGGL((lep_huffprog_simt_rst_units_kernel<true>), dim3((unsigned)waves_rst.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwr, dun, nunits, dsc);
+        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
         hipLaunchKernelGGL(lep_huffprog_simt_stuff_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dsc, d_out, d_out_len);
     }
     if (ps.size() + seq_seg.size() < (size_t)nscan)

@@ -16,16 +16,31 @@
 //     the scan's end) -- a suffix minimum over "first coding block at or after unit u";
 //   * how far into a run a unit starts: distance to the last block that coded something -- a prefix maximum.
 //
-// Passes (kernels in lep_gpu.hip; a unit = kProgUnit consecutive blocks of the scan's block order, DC scans of several components
-// kProgDcMcus MCUs):
+// Passes (kernels in lep_gpu.hip; a unit = at most kProgUnit consecutive blocks of the scan's block order, DC scans of several
+// components kProgDcMcus MCUs):
 //   1  count   lane = unit: bits of everything but the EOBn codes; per unit which blocks code something (nonE) and which of
 //              those leave their band open (P: the last coefficient is not at `to`)
 //   2  place   one wavefront per scan: prefix maximum / suffix minimum over the units -> every unit's run state (cin, la); the
-//              EOBn codes' bits from the two masks; exclusive prefix sum -> the unit's bit position
+//              EOBn codes' bits from the two masks; exclusive prefix sum -> the unit's bit position.  Summed in 64 bits: a scan of
+//              more than 2^32 - 1 bits gets no buffer and answers "outgrew" (ProgSimtScan.refused)
 //   3  code    lane = unit: the same walk, bits OR-ed into the scan's zero-filled bit buffer (lep_huff_simt.h's LaneSink)
 //   4  stuff   one wavefront per scan: pad bits, FF -> FF 00, clipped to the scan's slot
-// Scans with a restart interval go through the same passes with a unit map that never straddles an interval's end and a marker map
-// behind the bit buffer (lep_huffprog_simt_rst.h; ProgScan.pad says which kernel owns a scan, ProgSimtScan.rsti which unit map).
+//
+// A restart interval makes the lane form easier, not harder: where an interval ends the end-of-band run is written, the correction bits
+// it held back are out, the stream is padded to a byte, the marker FF D0+(k & 7) follows (k counts the scan's intervals from 0; none behind
+// the scan's last interval) and the DC predictors are zero again.  So every scan goes through the same passes with ONE unit map, and a scan
+// without an interval is a scan with one interval as long as the scan:
+//   * unit map      a restart unit is one MCU for an interleaved (DC) scan and one block for a one-component scan; an interval of R restart
+//                   units is cut into ceil(R / 32) units of blocks (ceil(R / 8) of MCUs), the last as short as it comes out, so no unit
+//                   straddles an interval's end; a unit's range is a closed form of its index (ProgUnitMap);
+//   * count / code  a unit an interval starts with starts from zero predictors; the unit an interval ends with inside the scan appends, in
+//                   the code pass, the pad bits to the byte boundary and the marker's 16 bits and names the marker's FF in the marker map
+//                   behind the bit buffer (one bit per buffer byte, as lep_huff_simt.h does);
+//   * place         the run state is cut at the intervals' ends: `la` stops at the end of the unit's interval, `cin` counts from the
+//                   interval's first block at the earliest; the prefix sum adds the pad bits and the 16 behind every interval that ends
+//                   inside the scan (an interval starts on a byte, so its pad is minus its own bit count modulo eight);
+//   * assign, zero, stuff   know the marker map (ProgSimtScan.rsti / map_bytes): only a scan with an interval has one.
+// ProgScan.pad says which kernel owns a scan.
 // SPMD layer of lep_wave.h: tests/emu steps every pass on the CPU against lep_huffprog.h and the host re-coder, byte for byte.
 #pragma once
 #include "lep_huff_simt.h"
@@ -46,10 +61,9 @@ struct ProgSimtScan {       // per scan taken by this form
     uint64_t buf_off;       // its bit buffer (bytes, 16-byte aligned) in the scratch arena
     uint32_t buf_bytes;     // multiple of 16
     uint32_t total_bits;    // pass 2
-    uint32_t rsti;          // 0: units of kProgUnit blocks from the scan's first (this file);  > 0: the scan's restart interval, units cut at
-                            // every interval's end (lep_huffprog_simt_rst.h)
+    uint32_t rsti;          // the scan's restart interval, units cut at every interval's end;  0: no interval on this scan
     uint32_t map_bytes;     // rsti > 0, prog_simt_assign: bytes of the marker map behind the bit buffer (bit q = byte q of the buffer is a marker's FF)
-    uint32_t refused;       // rsti > 0, pass 2: the scan's bits do not fit 32 bits -- no buffer, the scan answers "outgrew"
+    uint32_t refused;       // pass 2: the scan's bits do not fit 32 bits -- no buffer, the scan answers "outgrew"
     uint32_t spare;
 };
 struct ProgSimtWave { uint32_t pscan, first_unit; };   // lane l = unit first_unit + l of ProgSimtScan pscan
@@ -66,13 +80,39 @@ struct ProgSimtUnits {
     uint32_t* pmask;        // pass 1: bit i = ... and leaves its band open (an end-of-band run starts with it)
     uint32_t* cin;          // pass 2: blocks of the current run in front of the unit's first block (0: none open)
     uint32_t* la;           // pass 2: blocks with an empty band that follow the unit's last block
-    uint32_t* plain;        // lep_huffprog_simt_rst.h, pass 2: the prefix sum without pad bits and markers (a sixth array: kProgSimtRstUnitWords)
+    uint32_t* plain;        // pass 2, scans with an interval only: the prefix sum without pad bits and markers (the sixth array)
     WDEV void set(uint32_t* base, size_t units) { bits = base; nonE = base + units; pmask = base + 2 * units; cin = base + 3 * units; la = base + 4 * units; plain = base + 5 * units; }
 };
+// words per unit; the sixth array is there when, and only when, the launch holds a scan with a restart interval (no other scan touches it)
 constexpr int kProgSimtUnitWords = 5;
-constexpr int kProgSimtRstUnitWords = 6;   // launches that hold a scan with a restart interval
+constexpr int prog_simt_unit_words(bool intervals) { return kProgSimtUnitWords + (intervals ? 1 : 0); }
 
 struct ProgSimtShared { uint32_t code[2][256]; };
+
+// Which restart units (blocks of a one-component scan, MCUs of an interleaved DC scan) a unit codes: interval iv = u / per_interval holds
+// [iv * rsti, min((iv + 1) * rsti, n)), cut into runs of `per` from its first.  A scan without an interval sets rsti = n: units of `per`
+// from the scan's first, one interval [0, n).
+struct ProgUnitMap {
+    uint32_t n, rsti, per, per_interval;
+    LEPH_BOTH void set(uint32_t nblocks, uint32_t interval, bool mcus) {
+        n = nblocks; rsti = interval; per = mcus ? (uint32_t)kProgDcMcus : (uint32_t)kProgUnit;
+        per_interval = (uint32_t)(((uint64_t)rsti + per - 1) / per);
+    }
+    LEPH_BOTH uint64_t count() const { return (uint64_t)(n / rsti) * per_interval + ((uint64_t)(n % rsti) + per - 1) / per; }
+    // unit u: [*a0, *a1), the first restart unit of its interval and the interval's end
+    LEPH_BOTH void span(uint32_t u, uint32_t* a0, uint32_t* a1, uint32_t* ibegin, uint32_t* iend) const {
+        const uint32_t iv = u / per_interval, k = u - iv * per_interval;
+        const uint32_t b = iv * rsti, e = n - b < rsti ? n : b + rsti, from = b + k * per;
+        *a0 = from; *a1 = e - from < per ? e : from + per; *ibegin = b; *iend = e;
+    }
+    LEPH_BOTH uint32_t interval_first_unit(uint32_t u) const { return u - u % per_interval; }
+};
+// the map of scan `ps`
+LEPH_BOTH ProgUnitMap prog_simt_map(const ProgSimtScan& ps, const ProgScan* sc) {
+    ProgUnitMap map;
+    map.set(ps.nblocks, ps.rsti ? ps.rsti : ps.nblocks, sc->to == 0 && sc->cmpc > 1);
+    return map;
+}
 
 // bits of the EOBn code of a run of `run` blocks (encode_eobrun, jpgcoder.cc:5337-5368)
 WDEV void prog_eob_code(const uint32_t* ac, uint32_t run, uint32_t* bits, uint32_t* n) {
@@ -290,17 +330,27 @@ WDEV void prog_simt_units(const ProgImage* images, const ProgScan* scans, const 
     const ProgScan* sc = scans + ps.scan;
     const ProgImage* pim = images + sc->image;
     prog_simt_tables(sc, sh);
-    const bool dc = sc->to == 0, interleaved = sc->cmpc > 1;
+    const ProgUnitMap map = prog_simt_map(ps, sc);
     LANES(l) {
         const uint32_t u = first_unit + (uint32_t)l;
         if (u < ps.nunits) {
+            uint32_t a0, a1, ibegin, iend;
+            map.span(u, &a0, &a1, &ibegin, &iend);
             ProgSimtLane<WRITE> d;
             d.pim = pim; d.sc = sc; d.sh = sh; d.from = sc->from; d.to = sc->to; d.sal = sc->sal;
             const size_t gu = (size_t)ps.first_unit + u;
             d.sink.start(WRITE ? U.bits[gu] : 0u, reinterpret_cast<uint32_t*>(scratch + ps.buf_off), ps.buf_bytes >> 2);
             uint32_t nonE = 0, pmask = 0;
-            const uint32_t per = dc && interleaved ? (uint32_t)kProgDcMcus : (uint32_t)kProgUnit, a0 = u * per;
-            prog_simt_walk<WRITE>(d, a0, ps.nblocks - a0 < per ? ps.nblocks : a0 + per, u == 0, U, gu, &nonE, &pmask);
+            prog_simt_walk<WRITE>(d, a0, a1, a0 == ibegin, U, gu, &nonE, &pmask);
+            if (WRITE && a1 == iend && iend < ps.nblocks) {   // the interval ends with this unit, inside the scan: abitwriter::pad, then the marker
+                const uint32_t n = (0u - d.sink.bitpos()) & 7u;
+                uint32_t v = 0;
+                for (uint32_t j = 0; j < n; ++j) v = (v << 1) | (uint32_t)((pim->padbit >> j) & 1);
+                d.sink.put(v, n);
+                const uint32_t q = d.sink.bitpos() >> 3;   // the buffer byte the marker's FF becomes
+                if (q < ps.buf_bytes && ps.map_bytes) simt_or_word(reinterpret_cast<uint32_t*>(scratch + ps.buf_off + ps.buf_bytes) + (q >> 5), 1u << (q & 31u));
+                d.sink.put(0xffd0u | ((ibegin / map.rsti) & 7u), 16);
+            }
             d.sink.finish();
             if (!WRITE) { U.bits[gu] = d.sink.total; U.nonE[gu] = nonE; U.pmask[gu] = pmask; }
         }
@@ -313,52 +363,61 @@ WDEV void prog_simt_place(const ProgScan* scans, ProgSimtScan* psp, ProgSimtUnit
     const ProgScan* sc = scans + ps.scan;
     const bool ac = sc->to != 0;
     const uint32_t nunits = ps.nunits, fu = ps.first_unit, max = (uint32_t)sc->max_eobrun;
+    const ProgUnitMap map = prog_simt_map(ps, sc);
     if (ac) {
-        // (a) la: empty-band blocks behind every unit = (first coding block at or after the next unit, or the scan's end) - the unit's end.
-        //     Suffix minimum, batches of 64 units from the back.
+        // (a) la: empty-band blocks behind every unit = min(first coding block at or after the next unit, end of the unit's interval) - the
+        //     unit's end.  Suffix minimum, batches of 64 units from the back.
         uint32_t carry = ps.nblocks;   // first coding block at or after the batch behind this one
         for (uint32_t top = nunits; top > 0;) {
             const uint32_t base = top > 64 ? top - 64 : 0, cnt = top - base;
             LV(int, v); LV(int, sm);
             LANES(l) {
-                // lane l looks at unit base + l + 1 (its own successor)
-                const uint32_t nx = base + (uint32_t)l + 1;
+                const uint32_t nx = base + (uint32_t)l + 1;   // lane l looks at its unit's successor
                 int first = (int)kProgNone;
-                if ((uint32_t)l < cnt && nx < nunits) { const uint32_t m = U.nonE[fu + nx]; if (m) first = (int)(nx * (uint32_t)kProgUnit + (uint32_t)__builtin_ctz(m)); }
+                if ((uint32_t)l < cnt && nx < nunits) {
+                    const uint32_t m = U.nonE[fu + nx];
+                    if (m) { uint32_t a0, a1, ib, ie; map.span(nx, &a0, &a1, &ib, &ie); first = (int)(a0 + (uint32_t)__builtin_ctz(m)); }
+                }
                 L(v) = first;
             }
             lepwave::wave_suffix_min(v, sm);
             LANES(l) {
                 const uint32_t u = base + (uint32_t)l;
                 if ((uint32_t)l < cnt) {
+                    uint32_t a0, a1, ib, ie;
+                    map.span(u, &a0, &a1, &ib, &ie);
                     uint32_t nn = (uint32_t)L(sm) < carry ? (uint32_t)L(sm) : carry;
-                    const uint32_t end = (u + 1) * (uint32_t)kProgUnit < ps.nblocks ? (u + 1) * (uint32_t)kProgUnit : ps.nblocks;
-                    U.la[fu + u] = nn - end;
+                    if (ie < nn) nn = ie;
+                    U.la[fu + u] = nn - a1;
                 }
             }
             {   // the batch in front needs the first coding block at or after unit `base`
                 const uint32_t sm0 = lepwave::wave_read((const uint32_t*)sm, 0);
                 uint32_t own = kProgNone;
                 const uint32_t m = U.nonE[fu + base];
-                if (m) own = base * (uint32_t)kProgUnit + (uint32_t)__builtin_ctz(m);
-                uint32_t c2 = sm0 < carry ? sm0 : carry;
+                if (m) { uint32_t a0, a1, ib, ie; map.span(base, &a0, &a1, &ib, &ie); own = a0 + (uint32_t)__builtin_ctz(m); }
+                const uint32_t c2 = sm0 < carry ? sm0 : carry;
                 carry = own < c2 ? own : c2;
             }
             top = base;
         }
         LSYNC();
-        // (b) cin: blocks of the open run in front of every unit.  Block x stands (x - B) mod max blocks into a run, B = the last
-        //     coding block in front of it if that one left its band open, the block behind it if it closed it (no coding block
-        //     in front: the scan's first block).  Prefix maximum of B over the units.
+        // (b) cin: block x stands (x - B) mod max blocks into a run, B = the last coding block in front of it if that one left its band
+        //     open, the block behind it if it closed it -- and the first block of x's interval at the earliest.  Prefix maximum over the units.
         uint32_t bcarry = 0;
         for (uint32_t base = 0; base < nunits; base += 64) {
             LV(int, v); LV(int, pm);
             LANES(l) {
-                const uint32_t u = base + (uint32_t)l;   // lane l looks at unit u - 1 (its predecessor)
+                const uint32_t u = base + (uint32_t)l;   // lane l looks at its unit's predecessor
                 int b = 0;
                 if (u < nunits && u > 0) {
                     const uint32_t m = U.nonE[fu + u - 1];
-                    if (m) { const uint32_t i = 31u - (uint32_t)__builtin_clz(m); b = (int)((u - 1) * (uint32_t)kProgUnit + i + (((U.pmask[fu + u - 1] >> i) & 1u) ? 0u : 1u)); }
+                    if (m) {
+                        uint32_t a0, a1, ib, ie;
+                        map.span(u - 1, &a0, &a1, &ib, &ie);
+                        const uint32_t i = 31u - (uint32_t)__builtin_clz(m);
+                        b = (int)(a0 + i + (((U.pmask[fu + u - 1] >> i) & 1u) ? 0u : 1u));
+                    }
                 }
                 L(v) = b;
             }
@@ -366,8 +425,11 @@ WDEV void prog_simt_place(const ProgScan* scans, ProgSimtScan* psp, ProgSimtUnit
             LANES(l) {
                 const uint32_t u = base + (uint32_t)l;
                 if (u < nunits) {
-                    const uint32_t B = (uint32_t)L(pm) > bcarry ? (uint32_t)L(pm) : bcarry;
-                    U.cin[fu + u] = (u * (uint32_t)kProgUnit - B) % max;
+                    uint32_t a0, a1, ib, ie;
+                    map.span(u, &a0, &a1, &ib, &ie);
+                    uint32_t B = (uint32_t)L(pm) > bcarry ? (uint32_t)L(pm) : bcarry;
+                    if (B < ib) B = ib;
+                    U.cin[fu + u] = (a0 - B) % max;
                 }
             }
             const uint32_t last = lepwave::wave_read((const uint32_t*)pm, 63);
@@ -375,8 +437,10 @@ WDEV void prog_simt_place(const ProgScan* scans, ProgSimtScan* psp, ProgSimtUnit
         }
         LSYNC();
     }
-    // (c) the EOBn codes' bits, then the exclusive prefix sum of the units' bits
-    uint32_t run = 0;
+    // (c) the EOBn codes' bits, then the exclusive prefix sum of the units' bits without pads and markers -- which is the unit's bit position
+    //     where the scan has no interval
+    uint32_t* const sums = ps.rsti ? U.plain : U.bits;
+    uint64_t run = 0;
     for (uint32_t base = 0; base < nunits; base += 64) {
         LV(int, nb); LV(int, ex);
         LANES(l) {
@@ -385,8 +449,9 @@ WDEV void prog_simt_place(const ProgScan* scans, ProgSimtScan* psp, ProgSimtUnit
             if (u < nunits) {
                 b = U.bits[fu + u];
                 if (ac) {
-                    const uint32_t b0 = u * (uint32_t)kProgUnit, n = ps.nblocks - b0 < (uint32_t)kProgUnit ? ps.nblocks - b0 : (uint32_t)kProgUnit;
-                    const uint32_t nonE = U.nonE[fu + u], pmask = U.pmask[fu + u], la = U.la[fu + u];
+                    uint32_t a0, a1, ib, ie;
+                    map.span(u, &a0, &a1, &ib, &ie);
+                    const uint32_t n = a1 - a0, nonE = U.nonE[fu + u], pmask = U.pmask[fu + u], la = U.la[fu + u];
                     uint32_t c = U.cin[fu + u];
                     for (uint32_t i = 0; i < n; ++i) {
                         const int type = (nonE >> i) & 1u ? (((pmask >> i) & 1u) ? 1 : 2) : 0;
@@ -405,10 +470,37 @@ WDEV void prog_simt_place(const ProgScan* scans, ProgSimtScan* psp, ProgSimtUnit
             L(nb) = (int)b;
         }
         const int t = lepwave::wave_excl_scan(nb, ex);
-        LANES(l) { const uint32_t u = base + (uint32_t)l; if (u < nunits) U.bits[fu + u] = run + (uint32_t)L(ex); }
-        run += (uint32_t)t;
+        LANES(l) { const uint32_t u = base + (uint32_t)l; if (u < nunits) sums[fu + u] = (uint32_t)run + (uint32_t)L(ex); }
+        run += (uint64_t)(uint32_t)t;
     }
-    LANES(l) if (l == 0) psp->total_bits = run;
+    const uint64_t plain_total = run;
+    LSYNC();
+    // (d) scans with an interval: ... plus, behind every interval that ends inside the scan, its pad bits and the sixteen of its marker.
+    //     (Modulo 2^32 as long as nothing is known; a scan whose total does not fit is refused below and nothing of it is written.)
+    uint64_t extra = 0;
+    for (uint32_t base = 0; ps.rsti && base < nunits; base += 64) {
+        LV(int, xb); LV(int, ex); LV(uint32_t, plain);
+        LANES(l) {
+            const uint32_t u = base + (uint32_t)l;
+            int x = 0;
+            uint32_t p = 0;
+            if (u < nunits) {
+                p = U.plain[fu + u];
+                uint32_t a0, a1, ib, ie;
+                map.span(u, &a0, &a1, &ib, &ie);
+                if (a1 == ie && ie < ps.nblocks) {
+                    const uint32_t next = u + 1 < nunits ? U.plain[fu + u + 1] : (uint32_t)plain_total;
+                    x = (int)((0u - (next - U.plain[fu + map.interval_first_unit(u)])) & 7u) + 16;
+                }
+            }
+            L(xb) = x; L(plain) = p;
+        }
+        const int t = lepwave::wave_excl_scan(xb, ex);
+        LANES(l) { const uint32_t u = base + (uint32_t)l; if (u < nunits) U.bits[fu + u] = L(plain) + (uint32_t)extra + (uint32_t)L(ex); }
+        extra += (uint64_t)(uint32_t)t;
+    }
+    const uint64_t total = plain_total + extra;
+    LANES(l) if (l == 0) { psp->total_bits = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total; psp->refused = total > 0xffffffffull ? 1u : 0u; }
 }
 
 // between pass 2 and pass 3: one thread per image hands the image's region out to its scans
@@ -424,7 +516,7 @@ WDEV void prog_simt_assign(const ProgSimtRegion& r, ProgSimtScan* ps) {
 }
 
 // pass 4: one wavefront per scan (abitwriter::pad, then the FF00 rule of the JPEG byte stream -- but for the FFs the marker map names:
-// the restart markers the code pass of lep_huffprog_simt_rst.h put into the buffer)
+// the restart markers the code pass put into the buffer)
 WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const ProgSimtScan& ps, uint8_t* scratch, uint8_t* arena, uint32_t* out_len) {
     const ProgScan* sc = scans + ps.scan;
     const ProgImage* pim = images + sc->image;
@@ -488,16 +580,23 @@ WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const 
     LANES(l) if (l == 0) out_len[ps.scan] = (written < cap ? written : cap) | ((over || written > cap) ? 0x80000000u : 0u);
 }
 
-// which scans this form takes, and how many units it cuts one into (scans with a restart interval: prog_simt_rst_takes, lep_huffprog_simt_rst.h)
-inline bool prog_simt_takes(const ProgImage& im, const ProgScan& sc, uint32_t* nblocks, uint32_t* nunits) {
-    if (prog_scan_rsti(im, sc) != 0 || prog_is_sequential(sc)) return false;
+// which scans this form takes, how many units it cuts one into, and the scan's restart interval (0: none).  Whether a scan with an interval
+// is taken is the caller's to say: one that asks for no interval takes none.
+inline bool prog_simt_takes(const ProgImage& im, const ProgScan& sc, uint32_t* nblocks, uint32_t* nunits, uint32_t* rsti = nullptr) {
+    const int r = prog_scan_rsti(im, sc);
+    if (r < 0 || (r > 0 && !rsti) || prog_is_sequential(sc)) return false;
     const bool dc = sc.to == 0;
     if (sc.cmpc < 1 || sc.cmpc > 4 || (!dc && (sc.cmpc != 1 || sc.max_eobrun < 1))) return false;
-    uint64_t n, per;
-    if (sc.cmpc == 1) { const int c = sc.cmp[0]; if (c < 0 || c > 3 || im.nch[c] <= 0 || im.ncv[c] <= 0) return false; n = (uint64_t)im.nch[c] * (uint64_t)im.ncv[c]; per = kProgUnit; }
-    else { if (im.mcuc <= 0 || im.mcuh <= 0) return false; n = (uint64_t)im.mcuc; per = kProgDcMcus; }
+    uint64_t n;
+    if (sc.cmpc == 1) { const int c = sc.cmp[0]; if (c < 0 || c > 3 || im.nch[c] <= 0 || im.ncv[c] <= 0) return false; n = (uint64_t)im.nch[c] * (uint64_t)im.ncv[c]; }
+    else { if (im.mcuc <= 0 || im.mcuh <= 0) return false; n = (uint64_t)im.mcuc; }
     if (n == 0 || n > 0x3fffffffu) return false;
-    *nblocks = (uint32_t)n; *nunits = (uint32_t)((n + per - 1) / per);
+    ProgUnitMap map;
+    map.set((uint32_t)n, r ? (uint32_t)r : (uint32_t)n, sc.cmpc > 1);
+    const uint64_t units = map.count();
+    if (units == 0 || units > 0x3fffffffu) return false;
+    *nblocks = (uint32_t)n; *nunits = (uint32_t)units;
+    if (rsti) *rsti = (uint32_t)r;
     return true;
 }
 

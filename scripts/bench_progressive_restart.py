@@ -28,7 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CORPORA = {"rows_1": dict(restart_marker_rows=1), "blocks_516": dict(restart_marker_blocks=516),
-           "blocks_5": dict(restart_marker_blocks=5)}    # (blocks_5: a marker per five blocks, about 26,000 units per luma scan; not part of "both")
+           "blocks_5": dict(restart_marker_blocks=5),    # (blocks_5: a marker per five blocks, about 26,000 units per luma scan; not part of "both")
+           "none": dict()}                               # (none: the same pictures without an interval, for --write-only; not part of "both")
 BOTH = ["blocks_516", "rows_1"]
 
 

@@ -1,4 +1,4 @@
-"""Progressive files with restart intervals WRITTEN on the MI355X: lep_huffprog_simt_rst.h (one lane per run of blocks, units cut at the
+"""Progressive files with restart intervals WRITTEN on the MI355X: lep_huffprog_simt.h (one lane per run of blocks, units cut at the
 intervals' ends) through the batch decompressor, the round-trip check of the batch compressor and the device entry, against the original
 files and against the same build with LEP_HUFFPROG_SIMT_RST=0 (the wavefront form, lep_huffprog.h).  Every call is a finite number of
 launches; nothing is tried again after a failure."""

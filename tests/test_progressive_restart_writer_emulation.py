@@ -1,4 +1,4 @@
-"""lep_huffprog_simt_rst.h -- progressive scans with a restart interval written with one lane per run of blocks -- as a lane-loop emulation
+"""lep_huffprog_simt.h on progressive scans with a restart interval -- written with one lane per run of blocks -- as a lane-loop emulation
 (tests/emu/prog_simt_rst_emu.cc: every pass one emulated wavefront after the other, over garbage-filled scratch) against the wavefront
 form (lep_huffprog.h through core_emu.cc's emu_huffman_progressive_encode) and against the original files.  No file is skipped: a file the
 planner does not take fails its test."""
@@ -126,7 +126,7 @@ def test_fixture_and_phone_images(core, lanes, name):
     jpg, lep = golden(name) if name.startswith("prog_") else ref_golden(name)
     took, markers = _three_assertions(core, lanes, jpg, lep, name)
     assert markers > 0
-    print("%s: %d scans, %d markers through lep_huffprog_simt_rst.h" % (name, took, markers))
+    print("%s: %d scans with an interval, %d markers through lep_huffprog_simt.h" % (name, took, markers))
 
 
 def _pillow(w, h, mode, sub, quality, noise, seed, **restart):
@@ -357,6 +357,12 @@ def test_unit_map_is_a_closed_form(lanes):
                 spans = (C.c_uint32 * (4 * len(want) + 4))()
                 assert lanes.emu_prog_rst_unit_map(n, r, mcus, spans, len(want)) == len(want), (mcus, n, r)
                 assert [tuple(spans[4 * u: 4 * u + 4]) for u in range(len(want))] == want, (mcus, n, r)
+            # a scan without an interval is a scan with one interval as long as the scan (or longer): units of `per` from the scan's first
+            for r in (n, n + 1, n + per, 2 * n + 7):
+                want = [(u * per, min((u + 1) * per, n), 0, n) for u in range((n + per - 1) // per)]
+                spans = (C.c_uint32 * (4 * len(want) + 4))()
+                assert lanes.emu_prog_rst_unit_map(n, r, mcus, spans, len(want)) == len(want), (mcus, n, r)
+                assert [tuple(spans[4 * u: 4 * u + 4]) for u in range(len(want))] == want, (mcus, n, r)
 
 
 def _place_made_up(lanes, nblocks, rsti, bits, region):
@@ -397,7 +403,11 @@ def test_place_pass_sums_in_64_bits(lanes):
     assert total_exact > 0xffffffff
     pos, total, refused, buf_bytes, out_len = _place_made_up(lanes, nblocks, rsti, bits, 1 << 40)
     assert refused == 1 and buf_bytes == 0 and out_len == 0x80000000
-    # ... and the same scan cut short of it
+    # the same bit counts on a scan without an interval: no markers, and 2^32 is still passed
+    assert sum(bits) > 0xffffffff
+    pos, total, refused, buf_bytes, out_len = _place_made_up(lanes, nblocks, 0, bits, 1 << 40)
+    assert refused == 1 and buf_bytes == 0 and out_len & 0x80000000
+    # ... and the scan with an interval cut short of it
     k = 0xffffffff // (61440 + 16) - 1
     pos, total, refused, buf_bytes, _ = _place_made_up(lanes, k * 32, rsti, bits[:k], 1 << 40)
     want_pos, want_total = serial(k * 32, rsti, bits[:k])
