@@ -1148,40 +1148,15 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
     const int set = g->cur & 1;                            // (the arena set the caller chose: two launches on two streams never share descriptors or scratch)
     Workspace &huff = g->ws[lep_gpu::W_HUFF + set], &huffenc = g->ws[lep_gpu::W_HUFFENC + set];
     if (int rc = ensure(g, huff, D.bytes())) return rc;
-    // which segments the lane-per-unit kernels take (lep_huff_simt.h); the wavefront-per-segment kernel keeps the others
+    // which segments the lane-per-unit kernels take, and what they need: lep_huff_simt.h's plan; the wavefront-per-segment kernel keeps the others
     std::vector<lep_huff_segment> sv(segs, segs + nseg);
-    std::vector<lephuff::SimtEncSeg> es;
-    std::vector<lephuff::SimtEncWave> waves;
-    size_t nunits = 0, scratch_bytes = 0;
-    for (int i = 0; i < nseg; ++i) {   // (a truncated file's segments are the lane-per-unit kernels' or nobody's: the wavefront kernel knows no cut)
-        sv[(size_t)i].pad = 0;
-        if (sv[(size_t)i].image < 0 || sv[(size_t)i].image >= nimg) continue;
-        const lep_huff_image& im = images[sv[(size_t)i].image];
-        if (im.trunc_bc[0] | im.trunc_bc[1] | im.trunc_bc[2] | im.trunc_bc[3]) sv[(size_t)i].pad = lephuff::kHuffSegRefuse;
-    }
-    if (g->huffenc_simt)
-        for (int i = 0; i < nseg; ++i) {
-            if (sv[(size_t)i].image < 0 || sv[(size_t)i].image >= nimg) continue;
-            const lephuff::HuffImage& im = reinterpret_cast<const lephuff::HuffImage&>(images[sv[(size_t)i].image]);
-            if (!lephuff::simt_enc_takes(im, reinterpret_cast<const lephuff::HuffSegment&>(sv[(size_t)i]))) continue;
-            lephuff::SimtEncSeg e;
-            memset(&e, 0, sizeof e);
-            if ((int64_t)sv[(size_t)i].mcu_row1 * im.mcuh > 0x7fffffff) continue;
-            lephuff::SimtUnitMap map;
-            map.set(sv[(size_t)i].mcu_row0 * im.mcuh, sv[(size_t)i].mcu_row1 * im.mcuh, im.rsti);
-            e.seg = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = map.count();
-            e.buf_off = scratch_bytes; e.buf_bytes = (uint32_t)std::min<size_t>(((size_t)sv[(size_t)i].out_cap + 64 + 15) & ~(size_t)15, 0xfffffff0u);
-            e.map_bytes = im.rsti > 0 ? ((e.buf_bytes >> 3) + 15u) & ~15u : 0u;   // restart intervals: which bytes of the bit buffer are markers
-            if (nunits + e.nunits > 0x7fffffffu) continue;
-            for (uint32_t f = 0; f < e.nunits; f += 64) waves.push_back(lephuff::SimtEncWave{(uint32_t)es.size(), f});
-            nunits += e.nunits; scratch_bytes += (size_t)e.buf_bytes + e.map_bytes;
-            sv[(size_t)i].pad = lephuff::kHuffSegSimt;
-            es.push_back(e);
-        }
+    lephuff::SimtEncPlan plan;
+    lephuff::simt_enc_plan(reinterpret_cast<const lephuff::HuffImage*>(images), nimg, reinterpret_cast<lephuff::HuffSegment*>(sv.data()), nseg, g->huffenc_simt != 0, &plan);
+    const auto& es = plan.es; const auto& waves = plan.waves;
     lepbuf::Layout L;
     const size_t o_es = L.add<lephuff::SimtEncSeg>(es.size()), o_wv = L.add<lephuff::SimtEncWave>(waves.size()),
-                 o_ub = L.add<uint32_t>(nunits * 2),   // (units: bit counts / positions, and the plain prefix sum of scans with restart intervals)
-                 o_sc = L.add<uint8_t>(scratch_bytes);
+                 o_ub = L.add<uint32_t>(plan.nunits * 2),   // (units: bit counts / positions, and the plain prefix sum of scans with restart intervals)
+                 o_sc = L.add<uint8_t>(plan.scratch_bytes);
     if (!es.empty()) { if (int rc = ensure(g, huffenc, L.padded())) return rc; }
     if (int rc = upload(g, huff, images, nimg * sizeof(lep_huff_image), st)) return rc;           // (the caller's arrays and ours may go away)
     if (int rc = upload(g, huff.at<char>(o_seg), sv.data(), nseg * sizeof(lep_huff_segment), st)) return rc;
@@ -1189,7 +1164,7 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
     if (!es.empty()) {
         if (int rc = upload(g, eb + o_es, es.data(), es.size() * sizeof(lephuff::SimtEncSeg), st)) return rc;
         if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::SimtEncWave), st)) return rc;
-        hipLaunchKernelGGL(lep_zero_kernel, dim3(8192), dim3(256), 0, st, (uint4*)(eb + o_sc), scratch_bytes / 16);   // (buf_bytes are multiples of 16)
+        hipLaunchKernelGGL(lep_zero_kernel, dim3(8192), dim3(256), 0, st, (uint4*)(eb + o_sc), plan.scratch_bytes / 16);   // (buf_bytes are multiples of 16)
     }
     const lephuff::HuffImage* di = huff.at<lephuff::HuffImage>(0);
     const lephuff::HuffSegment* ds = huff.at<lephuff::HuffSegment>(o_seg);
@@ -1200,7 +1175,7 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
         uint32_t* dub = (uint32_t*)(eb + o_ub);
         uint8_t* dsc = (uint8_t*)(eb + o_sc);
         hipLaunchKernelGGL((lep_huffman_simt_encode_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, des, dwv, dub, dsc);
-        hipLaunchKernelGGL(lep_huffman_simt_encode_place_kernel, dim3((unsigned)es.size()), dim3(64), 0, st, di, ds, des, dub, dub + nunits);
+        hipLaunchKernelGGL(lep_huffman_simt_encode_place_kernel, dim3((unsigned)es.size()), dim3(64), 0, st, di, ds, des, dub, dub + plan.nunits);
         hipLaunchKernelGGL((lep_huffman_simt_encode_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, des, dwv, dub, dsc);
         hipLaunchKernelGGL(lep_huffman_simt_encode_stuff_kernel, dim3((unsigned)es.size()), dim3(64), 0, st, di, ds, (const lephuff::SimtEncSeg*)des, dsc, d_out, d_out_len,
                            (lephuff::HuffEnd*)d_ends);
@@ -1422,14 +1397,8 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     char* const h_desc = g->h_huffprog[turn];
     memcpy(h_desc, images, nimg * sizeof(lep_huffprog_image));
     memcpy(h_desc + o_scan, scans, nscan * sizeof(lep_huffprog_scan));
-    // which scans the lane-per-unit kernels take (lep_huffprog_simt.h); the wavefront-per-scan kernel keeps the others
     lephuff::ProgScan* hs = reinterpret_cast<lephuff::ProgScan*>(h_desc + o_scan);
-    std::vector<lephuff::ProgSimtScan> ps;
-    std::vector<lephuff::ProgSimtWave> waves;
-    bool intervals = false;   // a scan with a restart interval among them: the unit arrays' sixth word
-    std::vector<lephuff::ProgSimtRegion> regions;
     for (uint32_t& c : g->huffprog_forms) c = 0;
-    size_t nunits = 0, scratch_bytes = 0;
     std::vector<uint32_t> file_bound((size_t)nscan);
     for (int i = 0; i < nscan; ++i) { file_bound[(size_t)i] = hs[i].pad; hs[i].pad = 0; }   // (the caller's field; on the device it says which kernel owns the scan)
     // scans of SEQUENTIAL frames coded in several scans (lep_huffprog.h sequential_scan_segment): the sequential scan encoders write them,
@@ -1464,50 +1433,14 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         g->huffprog_forms[3] = (uint32_t)n;
         if ((int)n == nscan) { HIPCHK(g, hipGetLastError()); return 0; }
     }
-    if (g->huffprog_simt) {
-        // scans grouped by image (a region of bit buffers per image): the caller lists them file by file, but nothing here relies on it
-        std::vector<int> order((size_t)nscan);
-        for (int i = 0; i < nscan; ++i) order[(size_t)i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hs[a].image < hs[b].image; });
-        for (size_t a = 0; a < order.size();) {
-            size_t b = a;
-            while (b < order.size() && hs[order[b]].image == hs[order[a]].image) ++b;
-            const int im = hs[order[a]].image;
-            lephuff::ProgSimtRegion r{(uint32_t)ps.size(), 0u, scratch_bytes, 0};
-            uint64_t sum_cap = 0, bound = 0;
-            bool maps = false;
-            for (size_t k = a; k < b && im >= 0 && im < nimg; ++k) {
-                const int i = order[k];
-                uint32_t nb = 0, nu = 0, interval = 0;
-                const lephuff::ProgImage& pim = reinterpret_cast<const lephuff::ProgImage&>(images[im]);
-                if (!lephuff::prog_simt_takes(pim, hs[i], &nb, &nu, &interval) || (interval && !g->huffprog_simt_rst)) continue;
-                if (nunits + nu > 0x7fffffffu) continue;
-                lephuff::ProgSimtScan e;
-                memset(&e, 0, sizeof e);
-                e.scan = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = nu; e.nblocks = nb; e.rsti = interval;
-                for (uint32_t f = 0; f < nu; f += 64) waves.push_back(lephuff::ProgSimtWave{(uint32_t)ps.size(), f});
-                if (interval) maps = intervals = true;
-                ++g->huffprog_forms[interval ? 1 : 0];
-                nunits += nu;
-                sum_cap += (uint64_t)hs[i].out_cap + 96; bound = std::max<uint64_t>(bound, file_bound[(size_t)i]);
-                hs[i].pad = lephuff::kProgScanSimt;
-                ps.push_back(e);
-                ++r.nps;
-            }
-            if (r.nps) {
-                // the file's scans together are shorter than the file (lep_huffprog_scan.file_bound, where the caller said); a region
-                // that turns out too small leaves scans without a buffer, and the host re-coder takes the file
-                r.bytes = ((bound ? std::min<uint64_t>(sum_cap, bound + 96ull * r.nps + 4096) : sum_cap) + 15) & ~(uint64_t)15;
-                if (maps) r.bytes += ((r.bytes >> 3) + 16ull * r.nps + 15) & ~(uint64_t)15;   // the marker maps behind the buffers of the scans with an interval
-                scratch_bytes += r.bytes;
-                regions.push_back(r);
-            }
-            a = b;
-        }
-    }
+    // which scans the lane-per-unit kernels take, and what they need: lep_huffprog_simt.h's plan; the wavefront-per-scan kernel keeps the others
+    lephuff::ProgSimtPlan plan;
+    lephuff::prog_simt_plan(reinterpret_cast<const lephuff::ProgImage*>(images), nimg, hs, nscan, file_bound.data(), g->huffprog_simt != 0, g->huffprog_simt_rst != 0, &plan);
+    const auto& ps = plan.ps; const auto& waves = plan.waves; const auto& regions = plan.regions;
+    g->huffprog_forms[0] = plan.forms[0]; g->huffprog_forms[1] = plan.forms[1];
     lepbuf::Layout L;
     const size_t o_ps = L.add<lephuff::ProgSimtScan>(ps.size()), o_wv = L.add<lephuff::ProgSimtWave>(waves.size()), o_rg = L.add<lephuff::ProgSimtRegion>(regions.size()),
-                 o_un = L.add<uint32_t>(nunits * lephuff::prog_simt_unit_words(intervals)), o_sc = L.add<uint8_t>(scratch_bytes);
+                 o_un = L.add<uint32_t>(plan.nunits * lephuff::prog_simt_unit_words(plan.intervals)), o_sc = L.add<uint8_t>(plan.scratch_bytes);
     g->huffprog_forms[2] = (uint32_t)((size_t)nscan - ps.size() - seq_seg.size());
     if (!ps.empty()) { if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGSIMT + turn], L.padded())) return rc; }
     HIPCHK(g, hipMemcpyAsync(d_desc, h_desc, total, hipMemcpyHostToDevice, st));
@@ -1528,11 +1461,11 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
         uint32_t longest = 0;
         for (const lephuff::ProgSimtRegion& r : regions) longest = (uint32_t)std::max<uint64_t>(longest, r.bytes);
         const uint32_t chunk16 = 4096;   // 64 KB of a bit buffer per workgroup of the clearing kernel
-        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
-        hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, nunits);
+        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, plan.nunits, dsc);
+        hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, plan.nunits);
         hipLaunchKernelGGL(lep_huffprog_simt_assign_kernel, dim3((unsigned)(regions.size() + 63) / 64), dim3(64), 0, st, (const lephuff::ProgSimtRegion*)(eb + o_rg), (int)regions.size(), dps);
         hipLaunchKernelGGL(lep_huffprog_simt_zero_kernel, dim3((unsigned)ps.size(), (longest / 16 + chunk16 - 1) / chunk16 + 1), dim3(256), 0, st, (const lephuff::ProgSimtScan*)dps, dsc, chunk16);
-        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, nunits, dsc);
+        hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, plan.nunits, dsc);
         hipLaunchKernelGGL(lep_huffprog_simt_stuff_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dsc, d_out, d_out_len);
     }
     if (ps.size() + seq_seg.size() < (size_t)nscan)

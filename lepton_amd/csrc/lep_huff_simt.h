@@ -14,6 +14,9 @@
 //   4  stuff   one wavefront per segment: the pad bits where the scan ends, then the bit buffer's whole bytes to the output
 //              with the 00 behind every FF (16 bytes per lane and step, positions from a prefix sum of the FFs), clipped to
 //              the segment's byte bound; the partial byte, its bit count and the last DCs are the segment's end state.
+// The bit buffer's back end -- its size and its marker map's, the pad-bit pattern, the end of a restart interval in pass 3, the pads and
+// markers in pass 2's prefix sum, pass 4's pad and stuffing loop -- stands behind LaneSink (simt_buf_bytes .. simt_stuff_bytes) and is
+// lep_huffprog_simt.h's too.  Which segments a launch gives to these kernels is simt_enc_plan: host code, the launch's and tests/emu's.
 //
 // Restart intervals (round 5): a unit never straddles an interval's end (SimtUnitMap); the unit an interval ends with appends the pad
 // bits and the two marker bytes to its own bits, a unit an interval starts with begins from zero predictors; pass 2 adds those bits
@@ -24,6 +27,9 @@
 // lep_huff.h's kernel (HuffSegment.pad bit 0 says which kernel owns a segment).  Same bytes, same end states as that kernel
 // (tests/emu, GPU parity tests); recoder.cc:245-412 is what both restate.
 #pragma once
+#include <string.h>
+#include <algorithm>
+#include <vector>
 #include "lep_huff.h"
 
 namespace lephuff {
@@ -137,6 +143,103 @@ struct LaneSink {
         return rem ? (((uint32_t)(acc >> (64 - fill)) & ((1u << rem) - 1u)) << (8 - rem)) : 0u;
     }
 };
+
+// ---- the bit buffer's back end, for this writer and lep_huffprog_simt.h's alike ----
+// a bit buffer for `payload_bytes` of stream (the stuffing pass reads 16 bytes per lane), and the marker map behind it: a bit per buffer byte
+LEPH_BOTH uint64_t simt_buf_bytes(uint64_t payload_bytes) { return (payload_bytes + 64 + 15) & ~(uint64_t)15; }
+LEPH_BOTH uint64_t simt_marker_map_bytes(uint64_t buf_bytes) { return ((buf_bytes >> 3) + 15) & ~(uint64_t)15; }
+
+// abitwriter::pad: n < 8 bits of the pad-bit pattern, LSB of the pattern first
+WDEV uint32_t simt_pad_pattern(int padbit, uint32_t n) { uint32_t v = 0; for (uint32_t j = 0; j < n; ++j) v = (v << 1) | (uint32_t)((padbit >> j) & 1); return v; }
+// pass 4, wave-uniform: the stream of `total` bits in `buf` padded to a byte; returns the new total
+WDEV uint32_t simt_pad_to_byte(uint32_t* buf, uint32_t total, int padbit) {
+    const uint32_t n = (0u - total) & 7u;
+    if (!n) return total;
+    const uint32_t v = simt_pad_pattern(padbit, n);
+    LANES(l) if (l == 0) buf[total >> 5] |= v << (32u - (total & 31u) - n);
+    LSYNC();
+    return total + n;
+}
+// pass 3, one lane: a restart interval ends with this lane's unit -- abitwriter::pad, then (write_marker) FF D0+(marker_index & 7), its FF
+// named in the marker map (map_words: behind the bit buffer of buf_bytes; nullptr where the scan has none)
+WDEV void simt_end_interval(LaneSink<true>& sink, int padbit, uint32_t marker_index, uint32_t* map_words, uint32_t buf_bytes, bool write_marker) {
+    const uint32_t n = (0u - sink.bitpos()) & 7u;
+    sink.put(simt_pad_pattern(padbit, n), n);
+    if (write_marker) {
+        const uint32_t q = sink.bitpos() >> 3;                     // the buffer byte the marker's FF becomes
+        if (q < buf_bytes && map_words) simt_or_word(map_words + (q >> 5), 1u << (q & 31u));
+        sink.put(0xffd0u | (marker_index & 7u), 16);
+    }
+}
+// pass 2, second stage, restart intervals: positions[u] = plain[u] (the prefix sum of the units' own bits) plus, behind every interval that
+// ends in front of unit u, its pad bits -- an interval starts on a byte, so they are minus its own bit count modulo eight -- and its marker's.
+// ends(u, &start, &marker_bits): an interval ends with unit u inside the scan; then where in `plain` it starts and its marker's bits (16 or 0).
+template <class Ends>
+WDEV uint64_t simt_place_interval_extras(uint32_t nunits, const uint32_t* plain, uint32_t plain_total, uint32_t* positions, Ends ends) {
+    uint64_t extra = 0;
+    for (uint32_t base = 0; base < nunits; base += 64) {
+        LV(int, xb); LV(int, ex); LV(uint32_t, own);
+        LANES(l) {
+            const uint32_t u = base + (uint32_t)l;
+            int x = 0;
+            uint32_t p = 0, start = 0, marker_bits = 0;
+            if (u < nunits) {
+                p = plain[u];
+                if (ends(u, &start, &marker_bits)) {
+                    const uint32_t next = u + 1 < nunits ? plain[u + 1] : plain_total;
+                    x = (int)((0u - (next - start)) & 7u) + (int)marker_bits;
+                }
+            }
+            L(xb) = x; L(own) = p;
+        }
+        const int t = lepwave::wave_excl_scan(xb, ex);
+        LANES(l) { const uint32_t u = base + (uint32_t)l; if (u < nunits) positions[u] = L(own) + (uint32_t)extra + (uint32_t)L(ex); }
+        extra += (uint64_t)(uint32_t)t;
+    }
+    return extra;
+}
+// pass 4, one wavefront: the nb whole bytes of `buf` to `out`, a 00 behind every FF that marker_map (nullptr: none) does not name as a restart
+// marker's -- 16 bytes per lane and step, positions from a prefix sum of the FFs -- clipped to cap.  Returns the stream's bytes, clipped or not.
+WDEV uint32_t simt_stuff_bytes(const uint32_t* buf, uint32_t nb, const uint32_t* marker_map, uint8_t* out, uint32_t cap) {
+    uint32_t written = 0;
+    for (uint32_t base = 0; base < nb; base += 1024) {
+        LV(int, nff); LV(int, before);
+        LV(uint32_t, w0); LV(uint32_t, w1); LV(uint32_t, w2); LV(uint32_t, w3); LV(uint32_t, mk);
+        LANES(l) {
+            const uint32_t i = base + 16u * (uint32_t)l;
+            uint32_t a = 0, b = 0, c = 0, d = 0, markers = 0;
+            int n = 0;
+            if (i < nb) {
+                const uint32_t* p = buf + (i >> 2);
+                a = p[0]; b = p[1]; c = p[2]; d = p[3];
+                if (marker_map) markers = (marker_map[i >> 5] >> (i & 16u)) & 0xffffu;   // bit k: byte i + k is a restart marker's FF
+                const uint32_t have = nb - i < 16u ? nb - i : 16u;
+                for (uint32_t k = 0; k < have; ++k) {
+                    const uint32_t word = k < 4 ? a : (k < 8 ? b : (k < 12 ? c : d));
+                    n += (((word >> (24 - 8 * (k & 3))) & 255u) == 0xffu) & (~markers >> k & 1u);
+                }
+            }
+            L(w0) = a; L(w1) = b; L(w2) = c; L(w3) = d; L(nff) = n; L(mk) = markers;
+        }
+        const int ffs = lepwave::wave_excl_scan(nff, before);
+        LANES(l) {
+            const uint32_t i = base + 16u * (uint32_t)l;
+            if (i < nb) {
+                const uint32_t have = nb - i < 16u ? nb - i : 16u;
+                uint32_t pos = written + 16u * (uint32_t)l + (uint32_t)L(before);
+                for (uint32_t k = 0; k < have; ++k) {
+                    const uint32_t word = k < 4 ? L(w0) : (k < 8 ? L(w1) : (k < 12 ? L(w2) : L(w3)));
+                    const uint32_t byte = (word >> (24 - 8 * (k & 3))) & 255u;
+                    if (pos < cap) out[pos] = (uint8_t)byte;
+                    ++pos;
+                    if (byte == 0xffu && !(L(mk) >> k & 1u)) { if (pos < cap) out[pos] = 0; ++pos; }
+                }
+            }
+        }
+        written += (nb - base < 1024u ? nb - base : 1024u) + (uint32_t)ffs;
+    }
+    return written;
+}
 
 // the coefficient at zig-zag position K of a block held as 32 dwords in aligned order
 template <int K>
@@ -271,16 +374,10 @@ WDEV void simt_enc_units(const HuffImage* images, const HuffSegment* segs, SimtE
             if (!(WRITE && at == kUnitDead)) {   // (a unit behind the cut of a truncated file writes nothing)
                 d.sink.start(at, buf, es.buf_bytes >> 2);
                 const bool met_cut = d.code_mcus(m0, m1);
-                if (WRITE && simt_interval_ends_at(img, m1)) {   // the interval ends with this unit: abitwriter::pad, then the marker
-                    const uint32_t n = (0u - d.sink.bitpos()) & 7u;
-                    uint32_t v = 0;
-                    for (uint32_t j = 0; j < n; ++j) v = (v << 1) | (uint32_t)((img->padbit >> j) & 1);
-                    d.sink.put(v, n);
-                    if (simt_marker_written(img, m1)) {
-                        const uint32_t q = d.sink.bitpos() >> 3;                     // the buffer byte the marker's FF becomes
-                        if (q < es.buf_bytes && es.map_bytes) simt_or_word(reinterpret_cast<uint32_t*>(scratch + es.buf_off + es.buf_bytes) + (q >> 5), 1u << (q & 31u));
-                        d.sink.put(0xff00u | 0xd0u | (((uint32_t)(m1 / img->rsti) - 1u) & 7u), 16);
-                    }
+                if constexpr (WRITE) {               // (the COUNT instantiation holds none of this: pass 2 adds these bits)
+                    if (simt_interval_ends_at(img, m1))   // the interval ends with this unit: abitwriter::pad, then the marker
+                        simt_end_interval(d.sink, img->padbit, (uint32_t)(m1 / img->rsti) - 1u, es.map_bytes ? reinterpret_cast<uint32_t*>(scratch + es.buf_off + es.buf_bytes) : nullptr,
+                                          es.buf_bytes, simt_marker_written(img, m1));
                 }
                 d.sink.finish();
                 if (!WRITE) unit_bits[es.first_unit + u] = d.sink.total | (met_cut ? kUnitMetCut : 0u);
@@ -300,9 +397,8 @@ WDEV void simt_enc_units(const HuffImage* images, const HuffSegment* segs, SimtE
     }
 }
 
-// pass 2 with restart intervals: the units' positions are the prefix sum of their bits (`unit_plain`, kept) plus, behind every interval
-// that ends in front of them, its pad bits -- an interval starts on a byte, so they are minus its own bit count modulo eight -- and
-// the sixteen of its marker
+// pass 2 with restart intervals: the units' positions are the prefix sum of their bits (`unit_plain`, kept) plus the pad bits and
+// markers in front of them (simt_place_interval_extras)
 WDEV void simt_enc_place_intervals(const HuffImage* img, const HuffSegment& seg, SimtEncSeg* es, uint32_t* unit_bits, uint32_t* unit_plain) {
     SimtUnitMap map;
     map.set(seg.mcu_row0 * img->mcuh, seg.mcu_row1 * img->mcuh, img->rsti);
@@ -317,31 +413,17 @@ WDEV void simt_enc_place_intervals(const HuffImage* img, const HuffSegment& seg,
     }
     const uint32_t plain_total = run;
     LSYNC();
-    uint32_t extra = 0;
-    for (uint32_t base = 0; base < nunits; base += 64) {
-        LV(int, xb); LV(int, ex); LV(uint32_t, plain);
-        LANES(l) {
-            const uint32_t u = base + (uint32_t)l;
-            int x = 0;
-            uint32_t p = 0;
-            if (u < nunits) {
-                p = unit_plain[fu + u];
-                int m0, m1;
-                uint32_t f;
-                map.span(u, &m0, &m1, &f);
-                if (simt_interval_ends_at(img, m1)) {
-                    const uint32_t next = u + 1 < nunits ? unit_plain[fu + u + 1] : plain_total;
-                    const uint32_t start = f ? unit_plain[fu + f] : 0u;      // (the segment's first interval holds the overhang bits too)
-                    x = (int)((0u - (next - start)) & 7u) + (simt_marker_written(img, m1) ? 16 : 0);
-                }
-            }
-            L(xb) = x; L(plain) = p;
-        }
-        const int t = lepwave::wave_excl_scan(xb, ex);
-        LANES(l) { const uint32_t u = base + (uint32_t)l; if (u < nunits) unit_bits[fu + u] = L(plain) + extra + (uint32_t)L(ex); }
-        extra += (uint32_t)t;
-    }
-    LANES(l) if (l == 0) { es->total_bits = plain_total + extra; es->cut = 0u; }
+    const uint32_t* plain = unit_plain + fu;
+    const uint64_t extra = simt_place_interval_extras(nunits, plain, plain_total, unit_bits + fu, [&](uint32_t u, uint32_t* start, uint32_t* marker_bits) {
+        int m0, m1;
+        uint32_t f;
+        map.span(u, &m0, &m1, &f);
+        if (!simt_interval_ends_at(img, m1)) return false;
+        *start = f ? plain[f] : 0u;      // (the segment's first interval starts at bit 0: it holds the overhang bits too)
+        *marker_bits = simt_marker_written(img, m1) ? 16u : 0u;
+        return true;
+    });
+    LANES(l) if (l == 0) { es->total_bits = plain_total + (uint32_t)extra; es->cut = 0u; }
 }
 
 // pass 2: one wavefront per segment (`unit_plain`: a second array of the units' size, used for scans with restart intervals)
@@ -378,54 +460,11 @@ WDEV void simt_enc_stuff(const HuffImage* images, const HuffSegment* segs, const
     const uint32_t room = es.buf_bytes * 8u;
     if (total > room) total = room;                       // the segment overran its bound: what is kept is what the bound keeps
     const bool scan_ends = seg.mcu_row1 * img->mcuh >= img->mcuc && !es.cut;   // (a stream that stops at a cut has no end to pad)
-    if (scan_ends && (total & 7u)) {                      // abitwriter::pad: the pad-bit pattern, LSB of the pattern first
-        const uint32_t pend = total & 7u, n = 8u - pend;
-        uint32_t v = 0;
-        for (uint32_t j = 0; j < n; ++j) v = (v << 1) | (uint32_t)((img->padbit >> j) & 1);
-        LANES(l) if (l == 0) buf[total >> 5] |= v << (32u - (total & 31u) - n);
-        LSYNC();
-        total += n;
-    }
+    if (scan_ends) total = simt_pad_to_byte(buf, total, img->padbit);
     const uint32_t nb = total >> 3, cap = seg.out_cap;
     uint8_t* out = arena + seg.out_off;
     const uint32_t* marker_map = es.map_bytes ? reinterpret_cast<const uint32_t*>(scratch + es.buf_off + es.buf_bytes) : nullptr;
-    uint32_t written = 0;
-    for (uint32_t base = 0; base < nb; base += 1024) {
-        LV(int, nff); LV(int, before);
-        LV(uint32_t, w0); LV(uint32_t, w1); LV(uint32_t, w2); LV(uint32_t, w3); LV(uint32_t, mk);
-        LANES(l) {
-            const uint32_t i = base + 16u * (uint32_t)l;
-            uint32_t a = 0, b = 0, c = 0, d = 0, markers = 0;
-            int n = 0;
-            if (i < nb) {
-                const uint32_t* p = buf + (i >> 2);
-                a = p[0]; b = p[1]; c = p[2]; d = p[3];
-                if (marker_map) markers = (marker_map[i >> 5] >> (i & 16u)) & 0xffffu;   // bit k: byte i + k is a restart marker's FF
-                const uint32_t have = nb - i < 16u ? nb - i : 16u;
-                for (uint32_t k = 0; k < have; ++k) {
-                    const uint32_t word = k < 4 ? a : (k < 8 ? b : (k < 12 ? c : d));
-                    n += (((word >> (24 - 8 * (k & 3))) & 255u) == 0xffu) & (~markers >> k & 1u);
-                }
-            }
-            L(w0) = a; L(w1) = b; L(w2) = c; L(w3) = d; L(nff) = n; L(mk) = markers;
-        }
-        const int ffs = lepwave::wave_excl_scan(nff, before);
-        LANES(l) {
-            const uint32_t i = base + 16u * (uint32_t)l;
-            if (i < nb) {
-                const uint32_t have = nb - i < 16u ? nb - i : 16u;
-                uint32_t pos = written + 16u * (uint32_t)l + (uint32_t)L(before);
-                for (uint32_t k = 0; k < have; ++k) {
-                    const uint32_t word = k < 4 ? L(w0) : (k < 8 ? L(w1) : (k < 12 ? L(w2) : L(w3)));
-                    const uint32_t byte = (word >> (24 - 8 * (k & 3))) & 255u;
-                    if (pos < cap) out[pos] = (uint8_t)byte;
-                    ++pos;
-                    if (byte == 0xffu && !(L(mk) >> k & 1u)) { if (pos < cap) out[pos] = 0; ++pos; }
-                }
-            }
-        }
-        written += (nb - base < 1024u ? nb - base : 1024u) + (uint32_t)ffs;
-    }
+    const uint32_t written = simt_stuff_bytes(buf, nb, marker_map, out, cap);
     const uint32_t rem = scan_ends ? 0u : (es.total_bits & 7u);     // (of the whole stream, whatever the buffer kept of it)
     LANES(l) if (l == 0) {
         out_len[es.seg] = written < cap ? written : cap;
@@ -463,6 +502,34 @@ WDEV void simt_enc_stuff(const HuffImage* images, const HuffSegment* segs, const
 inline bool simt_enc_takes(const HuffImage& img, const HuffSegment& seg) {
     return (img.rsti == 0 || (img.rsti > 0 && !(img.trunc_bc[0] | img.trunc_bc[1] | img.trunc_bc[2] | img.trunc_bc[3]))) && img.interleaved == 1 && img.mcuc == img.mcuh * img.mcuv && seg.mcu_row0 >= 0 && seg.mcu_row1 > seg.mcu_row0 && seg.mcu_row1 <= img.mcuv &&
            ((seg.overhang >> 8) & 255u) < 8u;
+}
+
+// The launch plan: which of a launch's segments these kernels take (segs[i].pad: kHuffSegSimt; kHuffSegRefuse -- a truncated file's segments
+// are the lane-per-unit kernels' or nobody's, the wavefront kernel knows no cut; 0 -- the wavefront kernel's), with their descriptors, wave
+// list, units and scratch (bit buffers and marker maps).  enabled = false: this form takes none.  The launch and tests/emu call the same.
+struct SimtEncPlan { std::vector<SimtEncSeg> es; std::vector<SimtEncWave> waves; size_t nunits = 0, scratch_bytes = 0; };
+inline void simt_enc_plan(const HuffImage* images, int nimg, HuffSegment* segs, int nseg, bool enabled, SimtEncPlan* out) {
+    *out = SimtEncPlan();
+    for (int i = 0; i < nseg; ++i) {
+        HuffSegment& seg = segs[i];
+        seg.pad = 0;
+        if (seg.image < 0 || seg.image >= nimg) continue;
+        const HuffImage& im = images[seg.image];
+        if (im.trunc_bc[0] | im.trunc_bc[1] | im.trunc_bc[2] | im.trunc_bc[3]) seg.pad = kHuffSegRefuse;
+        if (!enabled || !simt_enc_takes(im, seg) || (int64_t)seg.mcu_row1 * im.mcuh > 0x7fffffff) continue;
+        SimtEncSeg e;
+        memset(&e, 0, sizeof e);
+        SimtUnitMap map;
+        map.set(seg.mcu_row0 * im.mcuh, seg.mcu_row1 * im.mcuh, im.rsti);
+        e.seg = (uint32_t)i; e.first_unit = (uint32_t)out->nunits; e.nunits = map.count();
+        if (out->nunits + e.nunits > 0x7fffffffu) continue;
+        e.buf_off = out->scratch_bytes; e.buf_bytes = (uint32_t)std::min<uint64_t>(simt_buf_bytes(seg.out_cap), 0xfffffff0u);
+        e.map_bytes = im.rsti > 0 ? (uint32_t)simt_marker_map_bytes(e.buf_bytes) : 0u;   // restart intervals: which bytes of the bit buffer are markers
+        for (uint32_t f = 0; f < e.nunits; f += 64) out->waves.push_back(SimtEncWave{(uint32_t)out->es.size(), f});
+        out->nunits += e.nunits; out->scratch_bytes += (size_t)e.buf_bytes + e.map_bytes;
+        seg.pad = kHuffSegSimt;
+        out->es.push_back(e);
+    }
 }
 
 }  // namespace lephuff

@@ -25,6 +25,9 @@
 //              more than 2^32 - 1 bits gets no buffer and answers "outgrew" (ProgSimtScan.refused)
 //   3  code    lane = unit: the same walk, bits OR-ed into the scan's zero-filled bit buffer (lep_huff_simt.h's LaneSink)
 //   4  stuff   one wavefront per scan: pad bits, FF -> FF 00, clipped to the scan's slot
+// The bit buffer's back end is lep_huff_simt.h's, shared with the writer of sequential scans: simt_buf_bytes / simt_marker_map_bytes,
+// simt_end_interval (pass 3), simt_place_interval_extras (pass 2), simt_pad_to_byte and simt_stuff_bytes (pass 4).  Which scans a launch
+// gives to these kernels is prog_simt_plan at the end of this file: host code, the launch's (lep_gpu.hip) and tests/emu's.
 //
 // A restart interval makes the lane form easier, not harder: where an interval ends the end-of-band run is written, the correction bits
 // it held back are out, the stream is padded to a byte, the marker FF D0+(k & 7) follows (k counts the scan's intervals from 0; none behind
@@ -342,14 +345,9 @@ WDEV void prog_simt_units(const ProgImage* images, const ProgScan* scans, const 
             d.sink.start(WRITE ? U.bits[gu] : 0u, reinterpret_cast<uint32_t*>(scratch + ps.buf_off), ps.buf_bytes >> 2);
             uint32_t nonE = 0, pmask = 0;
             prog_simt_walk<WRITE>(d, a0, a1, a0 == ibegin, U, gu, &nonE, &pmask);
-            if (WRITE && a1 == iend && iend < ps.nblocks) {   // the interval ends with this unit, inside the scan: abitwriter::pad, then the marker
-                const uint32_t n = (0u - d.sink.bitpos()) & 7u;
-                uint32_t v = 0;
-                for (uint32_t j = 0; j < n; ++j) v = (v << 1) | (uint32_t)((pim->padbit >> j) & 1);
-                d.sink.put(v, n);
-                const uint32_t q = d.sink.bitpos() >> 3;   // the buffer byte the marker's FF becomes
-                if (q < ps.buf_bytes && ps.map_bytes) simt_or_word(reinterpret_cast<uint32_t*>(scratch + ps.buf_off + ps.buf_bytes) + (q >> 5), 1u << (q & 31u));
-                d.sink.put(0xffd0u | ((ibegin / map.rsti) & 7u), 16);
+            if constexpr (WRITE) {
+                if (a1 == iend && iend < ps.nblocks)   // the interval ends with this unit, inside the scan: abitwriter::pad, then the marker
+                    simt_end_interval(d.sink, pim->padbit, ibegin / map.rsti, ps.map_bytes ? reinterpret_cast<uint32_t*>(scratch + ps.buf_off + ps.buf_bytes) : nullptr, ps.buf_bytes, true);
             }
             d.sink.finish();
             if (!WRITE) { U.bits[gu] = d.sink.total; U.nonE[gu] = nonE; U.pmask[gu] = pmask; }
@@ -478,26 +476,15 @@ WDEV void prog_simt_place(const ProgScan* scans, ProgSimtScan* psp, ProgSimtUnit
     // (d) scans with an interval: ... plus, behind every interval that ends inside the scan, its pad bits and the sixteen of its marker.
     //     (Modulo 2^32 as long as nothing is known; a scan whose total does not fit is refused below and nothing of it is written.)
     uint64_t extra = 0;
-    for (uint32_t base = 0; ps.rsti && base < nunits; base += 64) {
-        LV(int, xb); LV(int, ex); LV(uint32_t, plain);
-        LANES(l) {
-            const uint32_t u = base + (uint32_t)l;
-            int x = 0;
-            uint32_t p = 0;
-            if (u < nunits) {
-                p = U.plain[fu + u];
-                uint32_t a0, a1, ib, ie;
-                map.span(u, &a0, &a1, &ib, &ie);
-                if (a1 == ie && ie < ps.nblocks) {
-                    const uint32_t next = u + 1 < nunits ? U.plain[fu + u + 1] : (uint32_t)plain_total;
-                    x = (int)((0u - (next - U.plain[fu + map.interval_first_unit(u)])) & 7u) + 16;
-                }
-            }
-            L(xb) = x; L(plain) = p;
-        }
-        const int t = lepwave::wave_excl_scan(xb, ex);
-        LANES(l) { const uint32_t u = base + (uint32_t)l; if (u < nunits) U.bits[fu + u] = L(plain) + (uint32_t)extra + (uint32_t)L(ex); }
-        extra += (uint64_t)(uint32_t)t;
+    if (ps.rsti) {
+        const uint32_t* plain = U.plain + fu;
+        extra = simt_place_interval_extras(nunits, plain, (uint32_t)plain_total, U.bits + fu, [&](uint32_t u, uint32_t* start, uint32_t* marker_bits) {
+            uint32_t a0, a1, ib, ie;
+            map.span(u, &a0, &a1, &ib, &ie);
+            if (a1 != ie || ie >= ps.nblocks) return false;
+            *start = plain[map.interval_first_unit(u)]; *marker_bits = 16u;
+            return true;
+        });
     }
     const uint64_t total = plain_total + extra;
     LANES(l) if (l == 0) { psp->total_bits = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total; psp->refused = total > 0xffffffffull ? 1u : 0u; }
@@ -508,8 +495,8 @@ WDEV void prog_simt_assign(const ProgSimtRegion& r, ProgSimtScan* ps) {
     uint64_t off = r.off;
     for (uint32_t k = 0; k < r.nps; ++k) {
         ProgSimtScan* s = ps + r.first_ps + k;
-        const uint64_t need = ((((uint64_t)s->total_bits + 7) >> 3) + 64 + 15) & ~(uint64_t)15;
-        const uint64_t map = s->rsti ? ((need >> 3) + 15) & ~(uint64_t)15 : 0;   // (scans with a restart interval: the marker map behind the buffer)
+        const uint64_t need = simt_buf_bytes(((uint64_t)s->total_bits + 7) >> 3);
+        const uint64_t map = s->rsti ? simt_marker_map_bytes(need) : 0;   // (scans with a restart interval: the marker map behind the buffer)
         if (off + need + map <= r.off + r.bytes && need < 0xfffffff0ull && !s->refused) { s->buf_off = off; s->buf_bytes = (uint32_t)need; s->map_bytes = (uint32_t)map; off += need + map; }
         else { s->buf_off = r.off; s->buf_bytes = 0; s->map_bytes = 0; }
     }
@@ -529,54 +516,11 @@ WDEV void prog_simt_stuff(const ProgImage* images, const ProgScan* scans, const 
     const uint32_t room = ps.buf_bytes * 8u - 64u;
     const bool over = total > room;
     if (over) total = room;
-    if (total & 7u) {
-        const uint32_t pend = total & 7u, n = 8u - pend;
-        uint32_t v = 0;
-        for (uint32_t j = 0; j < n; ++j) v = (v << 1) | (uint32_t)((pim->padbit >> j) & 1);
-        LANES(l) if (l == 0) buf[total >> 5] |= v << (32u - (total & 31u) - n);
-        LSYNC();
-        total += n;
-    }
+    total = simt_pad_to_byte(buf, total, pim->padbit);
     const uint32_t nb = total >> 3, cap = sc->out_cap;
     uint8_t* out = arena + sc->out_off;
     const uint32_t* marker_map = ps.map_bytes ? reinterpret_cast<const uint32_t*>(scratch + ps.buf_off + ps.buf_bytes) : nullptr;
-    uint32_t written = 0;
-    for (uint32_t base = 0; base < nb; base += 1024) {
-        LV(int, nff); LV(int, before);
-        LV(uint32_t, w0); LV(uint32_t, w1); LV(uint32_t, w2); LV(uint32_t, w3); LV(uint32_t, mk);
-        LANES(l) {
-            const uint32_t i = base + 16u * (uint32_t)l;
-            uint32_t a = 0, b = 0, c = 0, d = 0, markers = 0;
-            int n = 0;
-            if (i < nb) {
-                const uint32_t* p = buf + (i >> 2);
-                a = p[0]; b = p[1]; c = p[2]; d = p[3];
-                if (marker_map) markers = (marker_map[i >> 5] >> (i & 16u)) & 0xffffu;   // bit k: byte i + k is a restart marker's FF
-                const uint32_t have = nb - i < 16u ? nb - i : 16u;
-                for (uint32_t k = 0; k < have; ++k) {
-                    const uint32_t word = k < 4 ? a : (k < 8 ? b : (k < 12 ? c : d));
-                    n += (((word >> (24 - 8 * (k & 3))) & 255u) == 0xffu) & (~markers >> k & 1u);
-                }
-            }
-            L(w0) = a; L(w1) = b; L(w2) = c; L(w3) = d; L(nff) = n; L(mk) = markers;
-        }
-        const int ffs = lepwave::wave_excl_scan(nff, before);
-        LANES(l) {
-            const uint32_t i = base + 16u * (uint32_t)l;
-            if (i < nb) {
-                const uint32_t have = nb - i < 16u ? nb - i : 16u;
-                uint32_t pos = written + 16u * (uint32_t)l + (uint32_t)L(before);
-                for (uint32_t k = 0; k < have; ++k) {
-                    const uint32_t word = k < 4 ? L(w0) : (k < 8 ? L(w1) : (k < 12 ? L(w2) : L(w3)));
-                    const uint32_t byte = (word >> (24 - 8 * (k & 3))) & 255u;
-                    if (pos < cap) out[pos] = (uint8_t)byte;
-                    ++pos;
-                    if (byte == 0xffu && !(L(mk) >> k & 1u)) { if (pos < cap) out[pos] = 0; ++pos; }
-                }
-            }
-        }
-        written += (nb - base < 1024u ? nb - base : 1024u) + (uint32_t)ffs;
-    }
+    const uint32_t written = simt_stuff_bytes(buf, nb, marker_map, out, cap);
     LANES(l) if (l == 0) out_len[ps.scan] = (written < cap ? written : cap) | ((over || written > cap) ? 0x80000000u : 0u);
 }
 
@@ -598,6 +542,61 @@ inline bool prog_simt_takes(const ProgImage& im, const ProgScan& sc, uint32_t* n
     *nblocks = (uint32_t)n; *nunits = (uint32_t)units;
     if (rsti) *rsti = (uint32_t)r;
     return true;
+}
+
+// The launch plan: which of a launch's scans these kernels take (scans[i].pad = kProgScanSimt; the caller has cleared the field and kept the
+// file's byte count it held in file_bound[i]), with their descriptors, wave list, a region of bit buffers per image, units and scratch.
+// enabled / rst_enabled = false: this form takes no scan / none with a restart interval.  region_bytes > 0 stands in for every region's
+// size (tests: a region that does not suffice).  The launch and tests/emu call the same.
+struct ProgSimtPlan {
+    std::vector<ProgSimtScan> ps; std::vector<ProgSimtWave> waves; std::vector<ProgSimtRegion> regions;
+    size_t nunits = 0, scratch_bytes = 0;
+    bool intervals = false;       // a scan with a restart interval among them: the unit arrays' sixth word
+    uint32_t forms[2] = {0, 0};   // scans taken without / with a restart interval
+};
+inline void prog_simt_plan(const ProgImage* images, int nimg, ProgScan* scans, int nscan, const uint32_t* file_bound, bool enabled, bool rst_enabled, ProgSimtPlan* out,
+                           uint64_t region_bytes = 0) {
+    *out = ProgSimtPlan();
+    if (!enabled) return;
+    // scans grouped by image (a region of bit buffers per image): the caller lists them file by file, but nothing here relies on it
+    std::vector<int> order((size_t)nscan);
+    for (int i = 0; i < nscan; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return scans[a].image < scans[b].image; });
+    for (size_t a = 0; a < order.size();) {
+        size_t b = a;
+        while (b < order.size() && scans[order[b]].image == scans[order[a]].image) ++b;
+        const int im = scans[order[a]].image;
+        ProgSimtRegion r{(uint32_t)out->ps.size(), 0u, out->scratch_bytes, 0};
+        uint64_t sum_cap = 0, bound = 0;
+        bool maps = false;
+        for (size_t k = a; k < b && im >= 0 && im < nimg; ++k) {
+            const int i = order[k];
+            uint32_t nb = 0, nu = 0, interval = 0;
+            if (!prog_simt_takes(images[im], scans[i], &nb, &nu, &interval) || (interval && !rst_enabled)) continue;
+            if (out->nunits + nu > 0x7fffffffu) continue;
+            ProgSimtScan e;
+            memset(&e, 0, sizeof e);
+            e.scan = (uint32_t)i; e.first_unit = (uint32_t)out->nunits; e.nunits = nu; e.nblocks = nb; e.rsti = interval;
+            for (uint32_t f = 0; f < nu; f += 64) out->waves.push_back(ProgSimtWave{(uint32_t)out->ps.size(), f});
+            if (interval) maps = out->intervals = true;
+            ++out->forms[interval ? 1 : 0];
+            out->nunits += nu;
+            sum_cap += (uint64_t)scans[i].out_cap + 96; bound = std::max<uint64_t>(bound, file_bound[i]);
+            scans[i].pad = kProgScanSimt;
+            out->ps.push_back(e);
+            ++r.nps;
+        }
+        if (r.nps) {
+            // the file's scans together are shorter than the file (lep_huffprog_scan.file_bound, where the caller said); a region
+            // that turns out too small leaves scans without a buffer, and the host re-coder takes the file
+            r.bytes = ((bound ? std::min<uint64_t>(sum_cap, bound + 96ull * r.nps + 4096) : sum_cap) + 15) & ~(uint64_t)15;
+            if (maps) r.bytes += simt_marker_map_bytes(r.bytes) + 16ull * r.nps;   // the marker maps behind the buffers of the scans with an interval
+            if (region_bytes) r.bytes = region_bytes & ~(uint64_t)15;
+            out->scratch_bytes += r.bytes;
+            out->regions.push_back(r);
+        }
+        a = b;
+    }
 }
 
 }  // namespace lephuff

@@ -164,16 +164,12 @@ extern "C" int emu_huffman_encode_segment_simt(const lep_huff_image* img, const 
     lephuff::HuffSegment s;
     memcpy(&s, seg, sizeof s);
     s.out_off = 0; s.image = 0;
-    if (!lephuff::simt_enc_takes(*im, s)) return 1;
-    lephuff::SimtEncSeg es;
-    memset(&es, 0, sizeof es);
-    lephuff::SimtUnitMap map;
-    map.set(s.mcu_row0 * im->mcuh, s.mcu_row1 * im->mcuh, im->rsti);
-    es.seg = 0; es.first_unit = 0; es.nunits = map.count();
-    es.buf_off = 0; es.buf_bytes = (uint32_t)(((size_t)s.out_cap + 64 + 15) & ~(size_t)15);
-    es.map_bytes = im->rsti > 0 ? ((es.buf_bytes >> 3) + 15u) & ~15u : 0u;
+    lephuff::SimtEncPlan plan;   // (the launch code's own: lep_gpu_huffman_encode_device)
+    lephuff::simt_enc_plan(im, 1, &s, 1, true, &plan);
+    if (plan.es.empty()) return 1;
+    lephuff::SimtEncSeg es = plan.es[0];
     std::vector<uint32_t> unit_bits(es.nunits), unit_plain(es.nunits);
-    std::vector<uint32_t> scratch(((size_t)es.buf_bytes + es.map_bytes) / 4 + 4, 0u);
+    std::vector<uint32_t> scratch(plan.scratch_bytes / 4 + 4, 0u);
     uint8_t* sc = reinterpret_cast<uint8_t*>(scratch.data());
     for (uint32_t f = 0; f < es.nunits; f += 64) lephuff::simt_enc_units<false>(im, &s, &es, &sh, unit_bits.data(), sc, f);
     lephuff::simt_enc_place(im, &s, &es, unit_bits.data(), unit_plain.data());
@@ -214,53 +210,17 @@ extern "C" int emu_huffman_progressive_encode(const lep_huffprog_image* img, con
     return 0;
 }
 
-// ... with one lane per run of blocks (lep_huffprog_simt.h): count, place, assign, code, stuff, every pass one emulated wavefront
-// after the other.  taken[i]: 1 when that form took scan i (the others are written by the wavefront form above, as on the GPU).
+// ... with one lane per run of blocks (lep_huffprog_simt.h; prog_simt_driver.h steps the passes over the launch code's plan), scans with
+// a restart interval left to the wavefront form.  taken[i]: 1 when the lane form -- or, for a scan of a sequential frame, the sequential
+// scan encoders -- took scan i (the others are written by the wavefront form above, as on the GPU).
 // region_bytes: > 0 stands in for the launch code's region size (tests: a region that does not suffice)
-#include "../../lepton_amd/csrc/lep_huffprog_simt.h"
+#include "prog_simt_driver.h"
 extern "C" int emu_huffman_progressive_encode_simt(const lep_huffprog_image* img, const lep_huffprog_scan* scans, int nscan, uint8_t* out, uint32_t* corr, uint32_t* out_len,
                                                    int32_t* taken, uint64_t region_bytes) {
-    static lephuff::ProgSimtShared sh;
-    static lephuff::ProgShared shw;
-    const lephuff::ProgImage* im = reinterpret_cast<const lephuff::ProgImage*>(img);
-    std::vector<lephuff::ProgScan> sv((size_t)nscan);
-    memcpy(sv.data(), scans, sizeof(lephuff::ProgScan) * (size_t)nscan);
-    std::vector<lephuff::ProgSimtScan> ps;
-    size_t nunits = 0;
-    uint64_t sum_cap = 0, bound = 0;
-    for (int i = 0; i < nscan; ++i) {
-        bound = std::max<uint64_t>(bound, sv[(size_t)i].pad);   // (lep_huffprog_scan.file_bound)
-        sv[(size_t)i].pad = 0; sv[(size_t)i].image = 0; taken[i] = 0;
-        if (lephuff::prog_is_sequential(sv[(size_t)i])) { out_len[i] = emu_sequential_scan(im, sv[(size_t)i], out, true); taken[i] = 1; continue; }
-        uint32_t nb = 0, nu = 0;
-        if (!lephuff::prog_simt_takes(*im, sv[(size_t)i], &nb, &nu)) continue;
-        lephuff::ProgSimtScan e;
-        memset(&e, 0, sizeof e);
-        e.scan = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = nu; e.nblocks = nb;
-        nunits += nu;
-        sum_cap += (uint64_t)sv[(size_t)i].out_cap + 96;
-        sv[(size_t)i].pad = lephuff::kProgScanSimt; taken[i] = 1;
-        ps.push_back(e);
-    }
-    lephuff::ProgSimtRegion r{0u, (uint32_t)ps.size(), 0, 0};
-    r.bytes = region_bytes ? region_bytes : ((bound ? std::min<uint64_t>(sum_cap, bound + 96ull * r.nps + 4096) : sum_cap) + 15) & ~(uint64_t)15;
-    std::vector<uint32_t> words(nunits * lephuff::kProgSimtUnitWords + 1, 0xdeadbeefu);
-    std::vector<uint32_t> scratch((size_t)r.bytes / 4 + 8, 0xa5a5a5a5u);   // (garbage: the clearing pass has to do its work)
-    uint8_t* scb = reinterpret_cast<uint8_t*>(scratch.data());
-    lephuff::ProgSimtUnits U;
-    U.set(words.data(), nunits);
-    for (auto& e : ps) for (uint32_t f = 0; f < e.nunits; f += 64) lephuff::prog_simt_units<false>(im, sv.data(), &e, &sh, U, scb, f);
-    for (auto& e : ps) lephuff::prog_simt_place(sv.data(), &e, U);
-    if (!ps.empty()) lephuff::prog_simt_assign(r, ps.data());
-    for (auto& e : ps) {   // (lep_huffprog_simt_zero_kernel)
-        const uint64_t need16 = std::min<uint64_t>(((uint64_t)e.total_bits + 7) / 8 / 16 + 2, e.buf_bytes / 16);
-        memset(scb + e.buf_off, 0, (size_t)need16 * 16);
-    }
-    for (auto& e : ps) for (uint32_t f = 0; f < e.nunits; f += 64) lephuff::prog_simt_units<true>(im, sv.data(), &e, &sh, U, scb, f);
-    for (auto& e : ps) lephuff::prog_simt_stuff(im, sv.data(), e, scb, out, out_len);
-    for (int i = 0; i < nscan; ++i)
-        if (!taken[i]) { lephuff::ProgWave w; out_len[i] = w.run_scan(im, &sv[(size_t)i], &shw, out, corr); }
-    return 0;
+    int32_t intact = 0;
+    const int rc = emu_prog_simt_drive(img, scans, nscan, out, corr, out_len, taken, region_bytes, false,
+                                       [](const lephuff::ProgImage* im, const lephuff::ProgScan& sc, uint8_t* o) { return emu_sequential_scan(im, sc, o, true); }, &intact);
+    return rc ? rc : (intact ? 0 : -1);   // (-1: a pass wrote outside the region or the unit arrays)
 }
 
 // GPU Huffman scan decoder (lep_huffdec.h) as a 64-lane loop emulation: one image

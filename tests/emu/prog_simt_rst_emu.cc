@@ -8,65 +8,17 @@
 #define LEP_DEV inline
 #include "../../lepton_amd/csrc/lep_derive.h"
 #include "../../lepton_amd/csrc/lep_huffprog_simt.h"
+#include "prog_simt_driver.h"
 
 // The scans of one image as lep_gpu_huffman_progressive_encode_device routes them: lep_huffprog_simt.h's form where it takes the scan
 // (one with a restart interval: where rst_on says so), the wavefront form (lep_huffprog.h) for the rest; all lane-form scans share one
-// region of bit buffers.  Every pass one emulated wavefront after the other, unit arrays and region filled with garbage first.
+// region of bit buffers.  Every pass one emulated wavefront after the other, unit arrays and region filled with garbage first
+// (prog_simt_driver.h, over the launch code's own plan).
 // taken[i]: 0 wavefront form, 1 lane form, 2 lane form with restart intervals.  region_bytes > 0 stands in for the launch code's region size.
 // *guards_intact: the words in front of and behind the region (and behind the unit arrays) still hold what they were filled with.
 extern "C" int emu_huffman_progressive_encode_lanes(const lep_huffprog_image* img, const lep_huffprog_scan* scans, int nscan, uint8_t* out, uint32_t* corr, uint32_t* out_len,
                                                     int32_t* taken, uint64_t region_bytes, int rst_on, int32_t* guards_intact) {
-    static lephuff::ProgSimtShared sh;
-    static lephuff::ProgShared shw;
-    const lephuff::ProgImage* im = reinterpret_cast<const lephuff::ProgImage*>(img);
-    std::vector<lephuff::ProgScan> sv((size_t)nscan);
-    memcpy(sv.data(), scans, sizeof(lephuff::ProgScan) * (size_t)nscan);
-    std::vector<lephuff::ProgSimtScan> ps;
-    size_t nunits = 0;
-    uint64_t sum_cap = 0, bound = 0;
-    bool maps = false;
-    for (int i = 0; i < nscan; ++i) {
-        bound = std::max<uint64_t>(bound, sv[(size_t)i].pad);   // (lep_huffprog_scan.file_bound)
-        sv[(size_t)i].pad = 0; sv[(size_t)i].image = 0; taken[i] = 0;
-        if (lephuff::prog_is_sequential(sv[(size_t)i])) return 2;   // (scans of sequential frames are not this file's subject)
-        uint32_t nb = 0, nu = 0, interval = 0;
-        if (!lephuff::prog_simt_takes(*im, sv[(size_t)i], &nb, &nu, &interval) || (interval && !rst_on)) continue;
-        lephuff::ProgSimtScan e;
-        memset(&e, 0, sizeof e);
-        e.scan = (uint32_t)i; e.first_unit = (uint32_t)nunits; e.nunits = nu; e.nblocks = nb; e.rsti = interval;
-        nunits += nu;
-        sum_cap += (uint64_t)sv[(size_t)i].out_cap + 96;
-        sv[(size_t)i].pad = lephuff::kProgScanSimt; taken[i] = interval ? 2 : 1;
-        maps = maps || interval != 0;
-        ps.push_back(e);
-    }
-    const size_t guard = 64;   // dwords
-    lephuff::ProgSimtRegion r{0u, (uint32_t)ps.size(), guard * 4, 0};
-    r.bytes = ((bound ? std::min<uint64_t>(sum_cap, bound + 96ull * r.nps + 4096) : sum_cap) + 15) & ~(uint64_t)15;
-    if (maps) r.bytes += ((r.bytes >> 3) + 16ull * r.nps + 15) & ~(uint64_t)15;
-    if (region_bytes) r.bytes = region_bytes & ~(uint64_t)15;
-    const size_t unit_words = nunits * (size_t)lephuff::prog_simt_unit_words(maps);
-    std::vector<uint32_t> words(unit_words + guard, 0xdeadbeefu);
-    std::vector<uint32_t> scratch(guard + (size_t)r.bytes / 4 + guard, 0xa5a5a5a5u);   // (garbage: the clearing pass has to do its work)
-    uint8_t* scb = reinterpret_cast<uint8_t*>(scratch.data());
-    lephuff::ProgSimtUnits U;
-    U.set(words.data(), nunits);
-    for (auto& e : ps) for (uint32_t f = 0; f < e.nunits; f += 64) lephuff::prog_simt_units<false>(im, sv.data(), &e, &sh, U, scb, f);
-    for (auto& e : ps) lephuff::prog_simt_place(sv.data(), &e, U);
-    if (!ps.empty()) lephuff::prog_simt_assign(r, ps.data());
-    for (auto& e : ps) {   // (lep_huffprog_simt_zero_kernel)
-        const uint64_t need16 = std::min<uint64_t>(((uint64_t)e.total_bits + 7) / 8 / 16 + 2, e.buf_bytes / 16);
-        memset(scb + e.buf_off, 0, (size_t)need16 * 16);
-        memset(scb + e.buf_off + e.buf_bytes, 0, e.map_bytes);
-    }
-    for (auto& e : ps) for (uint32_t f = 0; f < e.nunits; f += 64) lephuff::prog_simt_units<true>(im, sv.data(), &e, &sh, U, scb, f);
-    for (auto& e : ps) lephuff::prog_simt_stuff(im, sv.data(), e, scb, out, out_len);
-    for (int i = 0; i < nscan; ++i)
-        if (!taken[i]) { lephuff::ProgWave w; out_len[i] = w.run_scan(im, &sv[(size_t)i], &shw, out, corr); }
-    bool intact = true;
-    for (size_t k = 0; k < guard; ++k) intact = intact && scratch[k] == 0xa5a5a5a5u && scratch[guard + (size_t)r.bytes / 4 + k] == 0xa5a5a5a5u && words[unit_words + k] == 0xdeadbeefu;
-    *guards_intact = intact ? 1 : 0;
-    return 0;
+    return emu_prog_simt_drive(img, scans, nscan, out, corr, out_len, taken, region_bytes, rst_on != 0, nullptr, guards_intact);   // (scans of sequential frames are not this file's subject)
 }
 
 // The unit map alone: unit u of a scan of n restart units with interval rsti -> a0, a1, first restart unit and end of its interval.
@@ -104,5 +56,31 @@ extern "C" int emu_prog_simt_rst_place_made_up(uint32_t nblocks, uint32_t rsti, 
     *buf_bytes = e.buf_bytes;
     *out_len = 0;
     if (e.buf_bytes == 0) { uint8_t none[16]; lephuff::prog_simt_stuff(&im, &sc, e, none, none, out_len); }
+    return 0;
+}
+
+// The back end both lane writers share (lep_huff_simt.h), on made-up buffers: the stuffing loop alone ...
+extern "C" uint32_t emu_simt_stuff_bytes(const uint32_t* buf, uint32_t nb, const uint32_t* marker_map, uint8_t* out, uint32_t cap) {
+    return lephuff::simt_stuff_bytes(buf, nb, marker_map, out, cap);
+}
+// ... and the sequential writer's pass 2 on MADE-UP bit counts: MCU rows [row0, row1) of an image mcuh MCUs wide and mcuv high, the segment
+// starting with overhang_bits bits of a byte.  Returns 1 when the unit map does not come to nunits units.
+extern "C" int emu_simt_enc_place_made_up(int mcuh, int mcuv, int rsti, uint32_t rst_limit, int row0, int row1, uint32_t overhang_bits, const uint32_t* unit_bits, uint32_t nunits,
+                                          uint32_t* positions, uint32_t* total_bits) {
+    static lephuff::HuffImage im;
+    lephuff::HuffSegment seg;
+    memset(&im, 0, sizeof im); memset(&seg, 0, sizeof seg);
+    im.mcuh = mcuh; im.mcuv = mcuv; im.mcuc = mcuh * mcuv; im.rsti = rsti; im.rst_limit = rst_limit;
+    seg.mcu_row0 = row0; seg.mcu_row1 = row1; seg.overhang = overhang_bits << 8;
+    lephuff::SimtUnitMap map;
+    map.set(row0 * mcuh, row1 * mcuh, rsti);
+    if (map.count() != nunits) return 1;
+    lephuff::SimtEncSeg es;
+    memset(&es, 0, sizeof es);
+    es.nunits = nunits;
+    std::vector<uint32_t> plain(nunits, 0xdeadbeefu);
+    memcpy(positions, unit_bits, (size_t)nunits * 4);
+    lephuff::simt_enc_place(&im, &seg, &es, positions, plain.data());
+    *total_bits = es.total_bits;
     return 0;
 }

@@ -412,3 +412,74 @@ def test_place_pass_sums_in_64_bits(lanes):
     pos, total, refused, buf_bytes, _ = _place_made_up(lanes, k * 32, rsti, bits[:k], 1 << 40)
     want_pos, want_total = serial(k * 32, rsti, bits[:k])
     assert refused == 0 and total == want_total and pos == want_pos and buf_bytes > 0
+
+
+def _serial(units, at=0):
+    """[(bits, interval ends here, marker written)] -> the units' positions and the total: pad to the byte and the marker's 16 behind an interval"""
+    pos = []
+    for bits, ends, marker in units:
+        pos.append(at); at += bits
+        if ends:
+            at += (-at) % 8 + (16 if marker else 0)
+    return pos, at
+
+
+def _with_interval_sums(rng, lens, residues):
+    """bit counts for intervals of lens[k] units whose sums are residues[k] modulo eight"""
+    bits = []
+    for n, r in zip(lens, residues):
+        b = [int(x) for x in rng.integers(1, 3000, n)]
+        b[-1] += (r - sum(b)) % 8
+        bits += b
+    return bits
+
+
+def test_place_pass_pads_and_markers_of_both_writers(lanes):
+    """the second stage of the place pass (simt_place_interval_extras) through both writers, on made-up bit counts against a prefix sum: intervals
+    that end exactly on a byte (no pad bit) and one bit past one (seven); the sequential writer's first interval with 1..7 overhang bits in it,
+    a segment that starts inside an interval, and rst_limit cutting the markers off half way"""
+    rng = np.random.default_rng(11)
+    # progressive, one-component scan: intervals of 70 blocks = 3 units (32, 32, 6), the last one short; every residue, 0 and 1 first
+    nblocks, rsti = 70 * 9 + 40, 70
+    lens = [3] * 9 + [2]
+    for residues in ([0] * 10, [1] * 10, [0, 1, 7, 2, 0, 0, 1, 1, 5, 3]):
+        bits = _with_interval_sums(rng, lens, residues)
+        shape = [(b, k % 3 == 2 and k < 27, True) for k, b in enumerate(bits)]
+        want_pos, want_total = _serial(shape)
+        pos, total, refused, _, _ = _place_made_up(lanes, nblocks, rsti, bits, 1 << 30)
+        assert (pos, total, refused) == (want_pos, want_total, 0), residues
+        pads = [(-(sum(bits[3 * k: 3 * k + 3]))) % 8 for k in range(9)]
+        assert pads == [(-r) % 8 for r in residues[:9]]
+    # sequential: an image 5 MCUs wide and 40 high, intervals of 12 MCUs = 2 units (8, 4)
+    lanes.emu_simt_enc_place_made_up.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    mcuh, mcuv, rsti = 5, 40, 12
+
+    def sequential(row0, row1, overhang, rst_limit, residue_of):
+        m, end, shape, k = row0 * mcuh, row1 * mcuh, [], 0
+        while m < end:       # units of 8 MCUs that stop where an interval does
+            stop = min(end, (m // rsti + 1) * rsti, m + 8)
+            ends = stop % rsti == 0 and stop < mcuh * mcuv
+            shape.append([int(rng.integers(1, 3000)), ends, ends and stop // rsti - 1 < rst_limit])
+            if ends:         # the interval's bits (the first one's with the overhang bits) come to residue_of(k) modulo eight
+                first = next((j + 1 for j in range(len(shape) - 2, -1, -1) if shape[j][1]), 0)
+                have = sum(s[0] for s in shape[first:]) + (overhang if first == 0 else 0)
+                shape[-1][0] += (residue_of(k) - have) % 8
+                k += 1
+            m = stop
+        bits = (C.c_uint32 * len(shape))(*[s[0] for s in shape])
+        pos, total = (C.c_uint32 * len(shape))(), C.c_uint32(0)
+        assert lanes.emu_simt_enc_place_made_up(mcuh, mcuv, rsti, rst_limit, row0, row1, overhang, bits, len(shape), pos, C.byref(total)) == 0
+        want_pos, want_total = _serial(shape, overhang)
+        assert (list(pos), total.value) == (want_pos, want_total), (row0, row1, overhang, rst_limit)
+        return sum(1 for s in shape if s[1]), sum(1 for s in shape if s[2])
+
+    for overhang in range(8):
+        for residue_of in (lambda k: 0, lambda k: 1, lambda k: (3 * k + 5) % 8):
+            ends, markers = sequential(0, 40, overhang, 0xffffffff, residue_of)     # the whole scan: 16 intervals end inside it, none behind the last
+            assert ends == markers == 16
+            ends, markers = sequential(0, 40, overhang, 8, residue_of)              # markers cut off half way: pads go on, the 16 bits do not
+            assert (ends, markers) == (16, 8)
+            ends, markers = sequential(7, 23, overhang, 0xffffffff, residue_of)     # MCUs 35..114: starts 11 MCUs into an interval, ends 6 into one
+            assert ends == markers == 7
+            ends, markers = sequential(7, 23, overhang, 5, residue_of)              # ... with the limit falling inside the segment (markers 2, 3, 4 of 2..8)
+            assert (ends, markers) == (7, 3)
