@@ -263,6 +263,8 @@ int lep_gpu_huffman_progressive_decode_device(lep_gpu *g, const lep_huffprogdec_
  * a prefix sum, a write pass into the ZERO-FILLED frame.  Same records, same frame, same status semantics as the single-wave
  * kernel (bit-exact against it on MI355X and in the lane-loop emulation); scans with restart intervals are taken when the image
  * carries LEP_HUFFDEC_RST_TABLE (lane = restart interval) and refused otherwise (LEP_ASSERTION_FAILURE: the single-wave kernel's).
+ * Scans whose blocks all use one DC and one AC table -- the bits do not say which block of the MCU a lane stands on -- are settled
+ * through DC sums per MCU slot, for 2 .. 16 blocks per MCU (4:2:0 with one table pair is six): status 0 like any other whole scan.
  * LEP_HUFFDEC_SIMT_BITS forces the subsequence length (tests). */
 int lep_gpu_huffman_decode_simt_device(lep_gpu *g, const lep_huffdec_image *images, int nimg, lep_huffdec_row *d_rows, void *hip_stream);
 /* plain device memory helpers so non-torch callers need no HIP binding */
@@ -468,6 +470,10 @@ int lep_batch_plan(const size_t *file_bytes, const size_t *frame_bytes, int n, c
 /* progressive files on the GPU scan decoder: scans of its one-launch form that gave up waiting for a scan in front of them since
  * the process started (their files went to the host parser; expected 0 -- the wait cannot deadlock, the count is the safety net's) */
 uint64_t lep_jpeg_gpu_scan_wait_timeouts(void);
+/* sequential scans that lep_compress_batch handed to the single-wave kernel since the process started, after the lane-per-subsequence
+ * decoder had answered with a status (subsequences that did not fall into step, or an irregular scan): each costs the lane passes and
+ * the slowest scan decoder there is.  Whole files of every layout the parser takes are expected to count 0. */
+uint64_t lep_batch_scan_second_chances(void);
 void lep_batch_release(void);   /* frees the staging buffers the two calls above keep between invocations (not re-entrant) */
 /* what the batch calls keep between invocations: pinned host bytes / device bytes of the large staging arenas (either pointer may be NULL) */
 void lep_batch_footprint(size_t *pinned_bytes, size_t *device_bytes);

@@ -228,6 +228,8 @@ def lib():
         L.lep_file_open_next.argtypes = [vp, C.c_size_t, vp, P(vp)]
         L.lep_jpeg_gpu_scan_wait_timeouts.argtypes = []
         L.lep_jpeg_gpu_scan_wait_timeouts.restype = C.c_uint64
+        L.lep_batch_scan_second_chances.argtypes = []
+        L.lep_batch_scan_second_chances.restype = C.c_uint64
         L.lep_batch_debug_poison.argtypes = [C.c_int]
         L.lep_batch_debug_poison.restype = None
         L.lep_jpeg_plan_handoffs.argtypes = [vp, C.c_int, P(Handoff), C.c_int]
@@ -248,7 +250,7 @@ EXPORTS = [
     "lep_file_segments", "lep_file_jpeg_size", "lep_file_recode", "lep_compress", "lep_decompress", "lep_free",
     "lep_version", "lep_jpeg_open_into", "lep_jpeg_peek_frame_bytes", "lep_file_describe_into", "lep_file_frame_bytes", "lep_jpeg_is_progressive", "lep_compress_batch", "lep_decompress_batch", "lep_batch_release", "lep_batch_footprint", "lep_file_recode_plan", "lep_file_recode_finish", "lep_gpu_huffman_encode_device", "lep_jpeg_open_gpu", "lep_jpeg_scan_bytes", "lep_jpeg_scan_restarts", "lep_jpeg_finish_gpu", "lep_gpu_huffman_decode_device", "lep_handoffs_serialize", "lep_handoffs_parse", "lep_mux", "lep_demux",
     "lep_serve_start", "lep_serve_get_stats", "lep_serve_stop", "lep_zlib0_wrap", "lep_jpeg_open_slice", "lep_compress_slice", "lep_jpeg_open_embedded", "lep_compress_embedded", "lep_gpu_use_arena", "lep_gpu_expect_company", "lep_gpu_settle_uploads", "lep_batch_plan", "lep_jpeg_set_encode_options", "lep_gpu_huffman_decode_simt_device",
-    "lep_jpeg_check_restores", "lep_jpeg_gpu_scan_wait_timeouts", "lep_batch_debug_poison", "lep_jpeg_plan_handoffs", "lep_file_consumed", "lep_chained_file_follows", "lep_file_open_next",
+    "lep_jpeg_check_restores", "lep_jpeg_gpu_scan_wait_timeouts", "lep_batch_scan_second_chances", "lep_batch_debug_poison", "lep_jpeg_plan_handoffs", "lep_file_consumed", "lep_chained_file_follows", "lep_file_open_next",
     "lep_file_recode_plan_progressive", "lep_file_recode_finish_progressive", "lep_gpu_huffman_progressive_encode_device",
     "lep_jpeg_open_gpu_progressive", "lep_jpeg_finish_gpu_progressive", "lep_jpeg_scan_restarts_of", "lep_gpu_huffman_progressive_decode_device",
     "lep_jpeg_plan_progressive_check", "lep_gpu_last_stage_ms", "lep_jpeg_set_container_version", "lep_container_can_write_version", "lep_jpeg_plan_scan_check", "lep_jpeg_scan_file_range",

@@ -257,6 +257,11 @@ class GpuCodec:
         on the GPU for eligible files unless host_huffman is set"""
         return self._batch(self._L.lep_decompress_batch, leps, False, threads, chunk_bytes, chunk_images, host_huffman)
 
+    def scan_second_chances(self):
+        """sequential scans the batch compressor handed to the single-wave kernel since the process started, after the
+        lane-per-subsequence scan decoder had answered with a status (process-wide, not per codec object)"""
+        return int(self._L.lep_batch_scan_second_chances())
+
     def close(self):
         if self.handle:
             self._L.lep_gpu_destroy(self.handle)

@@ -31,6 +31,8 @@
 
 namespace {
 
+std::atomic<uint64_t> g_scan_second_chances(0);   // lep_batch_scan_second_chances
+
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // CPUs this process may really use: affinity mask, capped by the cgroup CPU quota (a container can see 256 CPUs and be
@@ -299,6 +301,8 @@ size_t frame_bytes_of(const lep_image_desc& d) { return lepbuf::round_up(frame_e
 }  // namespace
 
 extern "C" {
+
+uint64_t lep_batch_scan_second_chances(void) { return g_scan_second_chances.load(std::memory_order_relaxed); }
 
 // frees the pinned / device staging buffers the batch calls keep between invocations
 void lep_batch_release(void) { for (Slot& s : g_slots) s.release(); }
@@ -599,6 +603,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                     again.push_back(hi);
                 }
                 if (!again.empty()) {
+                    g_scan_second_chances.fetch_add((uint64_t)again.size(), std::memory_order_relaxed);
                     if (int rc = lep_gpu_huffman_decode_device(g, again.data(), (int)again.size(), s->d_rows, s_huff)) return rc;
                     HIPOK(hipMemcpyAsync(rows.data(), s->d_rows, rows_total * sizeof(lep_huffdec_row), hipMemcpyDeviceToHost, s_huff));
                     HIPOK(hipStreamSynchronize(s_huff));

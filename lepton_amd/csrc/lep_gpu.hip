@@ -461,15 +461,20 @@ __global__ __launch_bounds__(64, 8) void lep_huffman_decode_kernel(const lephuff
 // One lane per subsequence (lep_huffdec_simt.h): guess / settle / place / write; a wavefront's 64 lanes are 64 consecutive
 // subsequences of one image, whose tables the wavefront keeps in LDS.
 __global__ __launch_bounds__(64) void lep_huffman_simt_settle_kernel(const lephuff::HuffDecImage* __restrict__ images, lephuff::SimtImage* si, const lephuff::SimtWave* waves,
-                                                                     const lephuff::SimtSub* in, lephuff::SimtSub* out, int settle) {
+                                                                     const lephuff::SimtSub* in, lephuff::SimtSub* out, int settle, lephuff::SimtSlots* slots) {
     __shared__ lephuff::SimtShared sh;
+    // (the lanes' slot columns of blind images with more than four blocks per MCU: dynamic, so that a launch without such an image
+    // asks for no more LDS than it ever did -- the launch code puts those images' wavefronts into launches of their own, with
+    // sizeof(SimtColumns) of it)
+    extern __shared__ __attribute__((aligned(16))) unsigned char simt_columns[];
     const lephuff::SimtWave w = waves[blockIdx.x];
-    lephuff::simt_guess_or_settle(images + w.image, &sh, si + w.image, in + si[w.image].first, out + si[w.image].first, w.first_sub, settle);
+    lephuff::simt_guess_or_settle(images + w.image, &sh, si + w.image, in + si[w.image].first, out + si[w.image].first, w.first_sub, settle, slots,
+                                  reinterpret_cast<lephuff::SimtColumns*>(simt_columns));
 }
 __global__ __launch_bounds__(64) void lep_huffman_simt_place_kernel(const lephuff::HuffDecImage* __restrict__ images, lephuff::SimtImage* si, const lephuff::SimtSub* sub,
-                                                                    lephuff::SimtPlace* place, int passes, lephuff::HuffDecRow* rows) {
+                                                                    lephuff::SimtPlace* place, int passes, lephuff::HuffDecRow* rows, const lephuff::SimtSlots* slots) {
     const int i = (int)blockIdx.x;
-    lephuff::simt_place(images + i, si + i, sub + si[i].first, place + si[i].first, passes, rows);
+    lephuff::simt_place(images + i, si + i, sub + si[i].first, place + si[i].first, passes, rows, slots);
 }
 __global__ __launch_bounds__(64) void lep_huffman_simt_write_kernel(const lephuff::HuffDecImage* __restrict__ images, lephuff::SimtImage* si, const lephuff::SimtWave* waves,
                                                                     const lephuff::SimtSub* sub, const lephuff::SimtPlace* place, lephuff::HuffDecRow* rows) {
@@ -1510,8 +1515,8 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
     // needs to fall into step
     const uint32_t L = g->simt_sub_bits ? (uint32_t)((g->simt_sub_bits + 31) & ~31) : lephuff::simt_sub_bits(bits, (uint64_t)64 * 8192 * 2);
     std::vector<lephuff::SimtImage> si((size_t)nimg);
-    std::vector<lephuff::SimtWave> waves;
-    size_t nsub_all = 0;
+    std::vector<lephuff::SimtWave> waves, wide_waves;
+    size_t nsub_all = 0, nslots = 0;                        // (nslots: entries of the side array, which only wide blind images have)
     for (int i = 0; i < nimg; ++i) {
         memset(&si[(size_t)i], 0, sizeof(lephuff::SimtImage));
         const uint64_t b = (uint64_t)images[i].scan_len * 8u;
@@ -1528,13 +1533,19 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
             si[(size_t)i].changed[0] = 0xff;
         }
         si[(size_t)i].first = (uint32_t)nsub_all; si[(size_t)i].nsub = n; si[(size_t)i].sub_bits = Li;
-        for (uint32_t f = 0; f < n; f += 64) waves.push_back(lephuff::SimtWave{(uint32_t)i, f});
+        // (wide blind images: their wavefronts stand behind all others', in settle launches of their own -- those ask for the lanes' slot
+        // columns in LDS and run six wavefronts to the SIMD, the launches of everything else keep their eight)
+        const bool wide = lephuff::simt_blind_wide(reinterpret_cast<const lephuff::HuffDecImage*>(&images[i]));
+        for (uint32_t f = 0; f < n; f += 64) (wide ? wide_waves : waves).push_back(lephuff::SimtWave{(uint32_t)i, f});
         nsub_all += n;
+        if (wide) { si[(size_t)i].slots = (uint32_t)nslots; nslots += n; }
     }
     if (nsub_all > 0x7fffffffu) return LEP_ASSERTION_FAILURE;
+    const int nw_plain = (int)waves.size(), nw_wide = (int)wide_waves.size();
+    waves.insert(waves.end(), wide_waves.begin(), wide_waves.end());
     lepbuf::Layout P;
     const size_t o_si = P.add<lephuff::SimtImage>(si.size()), o_wv = P.add<lephuff::SimtWave>(waves.size()), o_s0 = P.add<lephuff::SimtSub>(nsub_all),
-                 o_s1 = P.add<lephuff::SimtSub>(nsub_all), o_pl = P.add<lephuff::SimtPlace>(nsub_all);
+                 o_s1 = P.add<lephuff::SimtSub>(nsub_all), o_pl = P.add<lephuff::SimtPlace>(nsub_all), o_sl = P.add<lephuff::SimtSlots>(nslots);
     Workspace& huffdec = g->ws[lep_gpu::W_HUFFDEC];
     if (int rc = ensure(g, huffdec, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
     if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPAR], P.padded())) return rc;
@@ -1548,13 +1559,17 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
     const lephuff::SimtWave* dwv = (const lephuff::SimtWave*)(base + o_wv);
     lephuff::SimtSub* buf[2] = {(lephuff::SimtSub*)(base + o_s0), (lephuff::SimtSub*)(base + o_s1)};
     lephuff::SimtPlace* dpl = (lephuff::SimtPlace*)(base + o_pl);
+    lephuff::SimtSlots* dsl = (lephuff::SimtSlots*)(base + o_sl);
     const int nw = (int)waves.size();
     HIPCHK(g, hipEventRecord(g->ev0, st));
-    hipLaunchKernelGGL(lep_huffman_simt_settle_kernel, dim3(nw), dim3(64), 0, st, di, dsi, dwv, (const lephuff::SimtSub*)buf[1], buf[0], 0);
-    for (int k = 1; k <= lephuff::kSimtSettle; ++k)
-        hipLaunchKernelGGL(lep_huffman_simt_settle_kernel, dim3(nw), dim3(64), 0, st, di, dsi, dwv, (const lephuff::SimtSub*)buf[(k - 1) & 1], buf[k & 1], k);
+    for (int k = 0; k <= lephuff::kSimtSettle; ++k) {       // pass A (k = 0: nothing is read), then the settle passes
+        const lephuff::SimtSub* in = buf[(k + 1) & 1];
+        if (nw_plain) hipLaunchKernelGGL(lep_huffman_simt_settle_kernel, dim3(nw_plain), dim3(64), 0, st, di, dsi, dwv, in, buf[k & 1], k, dsl);
+        if (nw_wide) hipLaunchKernelGGL(lep_huffman_simt_settle_kernel, dim3(nw_wide), dim3(64), sizeof(lephuff::SimtColumns), st, di, dsi, dwv + nw_plain, in, buf[k & 1], k, dsl);
+    }
     const lephuff::SimtSub* fin = buf[lephuff::kSimtSettle & 1];
-    hipLaunchKernelGGL(lep_huffman_simt_place_kernel, dim3(nimg), dim3(64), 0, st, di, dsi, fin, dpl, lephuff::kSimtSettle, (lephuff::HuffDecRow*)d_rows);
+    hipLaunchKernelGGL(lep_huffman_simt_place_kernel, dim3(nimg), dim3(64), 0, st, di, dsi, fin, dpl, lephuff::kSimtSettle, (lephuff::HuffDecRow*)d_rows,
+                       (const lephuff::SimtSlots*)dsl);
     hipLaunchKernelGGL(lep_huffman_simt_write_kernel, dim3(nw), dim3(64), 0, st, di, dsi, dwv, fin, (const lephuff::SimtPlace*)dpl, (lephuff::HuffDecRow*)d_rows);
     hipLaunchKernelGGL(lep_huffman_simt_finish_kernel, dim3((nimg + 255) / 256), dim3(256), 0, st, di, nimg, (lephuff::HuffDecRow*)d_rows, (const lephuff::SimtImage*)dsi);
     HIPCHK(g, hipGetLastError());

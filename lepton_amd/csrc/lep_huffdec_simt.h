@@ -27,6 +27,12 @@
 
 namespace lephuff {
 
+#if LEP_ON_GPU
+#define LEP_SIMT_BOTH __host__ __device__ __forceinline__   // (the launch code sizes the side array with the same functions)
+#else
+#define LEP_SIMT_BOTH inline
+#endif
+
 constexpr int kSimtSettle = 3;          // settle passes at most
 constexpr uint32_t kSimtMinBits = 8192; // a subsequence shorter than this rarely falls into step before it ends
 
@@ -35,6 +41,19 @@ struct SimtSub {            // per (image, subsequence); two copies, read / writ
     uint32_t end_phase;
     uint32_t nblocks;       // blocks between the state the lane started from and E_i
     int16_t dcsum[4];       // sums of their DC differences per component (int16 wrap, like the predictor)
+};
+// Blind images (simt_blind_phases) of MORE than four blocks per MCU -- 4:2:0 written with one pair of tables is six -- have more slot sums
+// than SimtSub::dcsum holds.  Theirs go to a side array that only such images have entries in (SimtImage::slots), so the records of
+// every other image stay as small as they were.  During a guess / settle pass a lane keeps its sums in a column of LDS (SimtColumns: a
+// slot that is only known at run time indexes memory there, not registers); behind the pass they leave as eight dwords of two sums.
+// The columns are dynamic LDS of a settle launch that holds ONLY such images (the launch code sorts their wavefronts behind the others'):
+// 2048 bytes beside the 4592 of SimtShared, six wavefronts per SIMD where the launch of every other image keeps its eight.  A caller that
+// passes no side array (slots == nullptr) gets such an image decoded as before there were any: not blind, status 3 unless one lane holds it.
+constexpr int kSimtBlindSlots = 16;     // slots of an MCU a blind image may have: what SimtShared::ph_cmp holds
+struct SimtSlots { uint32_t pair[kSimtBlindSlots / 2]; };   // per (wide blind image, subsequence): the sum of slot 2k (low half) and 2k + 1, mod 2^16
+struct SimtColumns {        // guess / settle passes: the sum of slot p of lane l, mod 2^16; lanes l and l + 32 share a dword (the two halves of a
+    uint16_t c[kSimtBlindSlots * 64];                      // wavefront are served one after the other, so every lane of a half has a bank of its own)
+    static LEP_SIMT_BOTH int at(int p, int l) { return p * 64 + ((l & 31) << 1) + (l >> 5); }
 };
 struct SimtPlace {          // per (image, subsequence), pass P
     uint32_t before;        // blocks of the image in front of the region
@@ -46,6 +65,7 @@ struct SimtImage {          // per image
     uint32_t sub_bits;      // multiple of 32
     int32_t status;         // OR of what the passes found (0 = fine)
     int32_t changed[kSimtSettle + 1];   // [k]: settle pass k saw an end state move ([0] is set by pass A: the first settle pass always runs)
+    uint32_t slots;         // its first entry in the SimtSlots array (simt_blind_wide images only)
 };
 struct SimtWave { uint32_t image, first_sub; };   // lane l = subsequence first_sub + l of that image
 
@@ -209,31 +229,38 @@ WDEV int simt_setup(const HuffDecImage* img, SimtShared* sh) {
 // An image whose blocks ALL use the same DC and the same AC table (Cb + Cr coded together in a scan of their own; files written with one
 // pair of tables for every component): the lanes fall into step with the block boundaries like any others, but WHICH block of the MCU a
 // lane stands on is not in the bits -- a block decodes the same whatever component it is taken for -- so a guessed position inside the
-// MCU never corrects itself, and the true one would travel one lane per settle pass.  For such an image (2 .. 4 blocks per MCU) the
-// passes do without it: a lane counts its blocks from SLOT 0 of an MCU it does not know and sums the DC differences per slot
-// (SimtSub::dcsum by slot, not by component); pass P learns every lane's true slot from the prefix sum of the block counts and only then
-// turns slot sums into component sums; pass C starts from that slot.  Returns the blocks per MCU of such an image, else 0.
-WDEV int simt_blind_phases(const HuffDecImage* img) {
+// MCU never corrects itself, and the true one would travel one lane per settle pass.  For such an image (2 .. kSimtBlindSlots blocks per
+// MCU: every layout the parser lets through, two by two blocks of three components are twelve) the passes do without it: a lane counts
+// its blocks from SLOT 0 of an MCU it does not know and sums the DC differences per slot (SimtSub::dcsum by slot, not by component, up
+// to four slots; SimtSlots beyond); pass P learns every lane's true slot from the prefix sum of the block counts and only then turns slot
+// sums into component sums; pass C starts from that slot.  Returns the blocks per MCU of such an image, else 0.
+LEP_SIMT_BOTH int simt_blind_phases(const HuffDecImage* img) {
     int nphase = 0;
     bool same = true;
-    const int c0 = img->scan_cmp[0];
-    for (int ci = 0; ci < img->ncomp; ++ci) {
-        const int cmp = img->scan_cmp[ci];
+    const int c0 = img->scan_cmp[0] & 3;                   // (bounded: the launch code asks this of whatever struct a caller passed in)
+    for (int ci = 0; ci < img->ncomp && ci < 4; ++ci) {
+        const int cmp = img->scan_cmp[ci] & 3;
         nphase += img->hs[cmp] * img->vs[cmp];
         same = same && img->dc_tbl[cmp] == img->dc_tbl[c0] && img->ac_tbl[cmp] == img->ac_tbl[c0];
     }
-    return (same && nphase >= 2 && nphase <= 4 && !(img->flags & kHuffDecRstTable)) ? nphase : 0;
+    return (same && nphase >= 2 && nphase <= kSimtBlindSlots && !(img->flags & kHuffDecRstTable)) ? nphase : 0;
+}
+// ... and whether its slot sums live in the side array
+LEP_SIMT_BOTH bool simt_blind_wide(const HuffDecImage* img) { return simt_blind_phases(img) > 4; }
+// ... and what the guess / settle / place passes take the image for: a wide blind image is one only to a caller that brought the side array
+WDEV int simt_blind_phases_with(const HuffDecImage* img, const SimtSlots* slots) {
+    const int n = simt_blind_phases(img);
+    return (n > 4 && !slots) ? 0 : n;
 }
 
-// passes A (settle = 0) and S (settle = 1..): `in` is read (S), `out` written
-WDEV void simt_guess_or_settle(const HuffDecImage* img, SimtShared* sh, SimtImage* si, const SimtSub* in, SimtSub* out, uint32_t first_sub, int settle) {
-    if (img->flags & kHuffDecRstTable) return;             // restart intervals: every piece's start is known (simt_write_intervals)
-    if (settle > 0 && !si->changed[settle - 1]) {          // the pass before this one moved nothing: its states are the answer
-        LANES(l) { const uint32_t i = first_sub + (uint32_t)l; if (i < si->nsub) out[i] = in[i]; }
-        return;
-    }
+// passes A (settle = 0) and S (settle = 1..): `in` is read (S), `out` written.  Wide: a blind image whose slot sums go through the
+// lane's LDS column into `slots` (one copy: no pass reads it, and a pass that only copies `in` to `out` leaves the sums of the pass
+// that made `in`); every other image runs the loop it always ran.
+template <bool Wide>
+WDEV void simt_guess_or_settle_lanes(const HuffDecImage* img, SimtShared* sh, SimtImage* si, const SimtSub* in, SimtSub* out, uint32_t first_sub, int settle,
+                                     SimtSlots* slots, SimtColumns* cols) {
     const int nphase = simt_setup(img, sh);
-    const bool blind = simt_blind_phases(img) != 0;
+    const bool blind = simt_blind_phases_with(img, slots) != 0;
     const uint32_t scan_bits = img->scan_len * 8u, L = si->sub_bits, nsub = si->nsub;
     LV(int, moved);
     LANES(l) {
@@ -243,7 +270,9 @@ WDEV void simt_guess_or_settle(const HuffDecImage* img, SimtShared* sh, SimtImag
             SimtSub r;
             r.end_bitpos = 0xffffffffu; r.end_phase = 0; r.nblocks = 0;
             r.dcsum[0] = r.dcsum[1] = r.dcsum[2] = r.dcsum[3] = 0;
-            if (settle > 0 && (i == 0 || i + 1 >= nsub)) r = in[i];             // lane 0's guess was no guess; the last region is pass C's
+            const bool kept = settle > 0 && (i == 0 || i + 1 >= nsub);
+            if (Wide && !kept) for (int p = 0; p < kSimtBlindSlots; ++p) cols->c[SimtColumns::at(p, l)] = 0;
+            if (kept) r = in[i];                                                // lane 0's guess was no guess; the last region is pass C's
             else if (i + 1 < nsub) {
                 uint32_t bp = i * L;
                 int phase = 0;
@@ -261,9 +290,12 @@ WDEV void simt_guess_or_settle(const HuffDecImage* img, SimtShared* sh, SimtImag
                         int diff = 0;
                         const int at = sh->ph_cmp[phase];
                         d.skip_block(img->dc_tbl[at], 2 + img->ac_tbl[at], &diff);
+                        if (Wide) { uint16_t* c = &cols->c[SimtColumns::at(phase, l)]; *c = (uint16_t)(*c + (uint32_t)diff); }
+                        else {
                         const int cmp = blind ? phase : at;            // (blind: the sums go by slot, counted from the lane's first block)
                         if (cmp == 0) sum[0] = (int16_t)(sum[0] + diff); else if (cmp == 1) sum[1] = (int16_t)(sum[1] + diff);
                         else if (cmp == 2) sum[2] = (int16_t)(sum[2] + diff); else sum[3] = (int16_t)(sum[3] + diff);
+                        }
                         ++count;
                         phase = phase + 1 == nphase ? 0 : phase + 1;
                     }
@@ -273,15 +305,30 @@ WDEV void simt_guess_or_settle(const HuffDecImage* img, SimtShared* sh, SimtImag
                 if (settle > 0 && (r.end_bitpos != in[i].end_bitpos || r.end_phase != in[i].end_phase)) L(moved) = 1;
             }
             out[i] = r;
+            if (Wide && !kept) {                            // (the column of a lane that decoded nothing is all zeros)
+                SimtSlots* w = slots + si->slots + i;
+                for (int k = 0; k < kSimtBlindSlots / 2; ++k) w->pair[k] = (uint32_t)cols->c[SimtColumns::at(2 * k, l)] | ((uint32_t)cols->c[SimtColumns::at(2 * k + 1, l)] << 16);
+            }
         }
     }
     if (lepwave::wave_ballot(moved) || settle == 0) { LANES(l) if (l == 0) si->changed[settle] = 1; }
+}
+WDEV void simt_guess_or_settle(const HuffDecImage* img, SimtShared* sh, SimtImage* si, const SimtSub* in, SimtSub* out, uint32_t first_sub, int settle,
+                               SimtSlots* slots = nullptr, SimtColumns* cols = nullptr) {
+    if (img->flags & kHuffDecRstTable) return;             // restart intervals: every piece's start is known (simt_write_intervals)
+    if (settle > 0 && !si->changed[settle - 1]) {          // the pass before this one moved nothing: its states are the answer
+        LANES(l) { const uint32_t i = first_sub + (uint32_t)l; if (i < si->nsub) out[i] = in[i]; }
+        return;
+    }
+    if (simt_blind_wide(img) && slots) simt_guess_or_settle_lanes<true>(img, sh, si, in, out, first_sub, settle, slots, cols);
+    else simt_guess_or_settle_lanes<false>(img, sh, si, in, out, first_sub, settle, slots, cols);
 }
 
 // pass P: one wavefront per image
 // (... and, before the write pass runs, marks the image's final record as not written: the record array is reused from call to call,
 // and a write pass in which no lane gets to it must not leave an older image's record standing there with status 0 -- ADVICE round 5)
-WDEV void simt_place(const HuffDecImage* img, SimtImage* si, const SimtSub* sub, SimtPlace* place, int passes, HuffDecRow* rows_arena = nullptr) {
+WDEV void simt_place(const HuffDecImage* img, SimtImage* si, const SimtSub* sub, SimtPlace* place, int passes, HuffDecRow* rows_arena = nullptr,
+                     const SimtSlots* slots = nullptr) {
     if (rows_arena) { LANES(l) if (l == 0) { HuffDecRow* fin = rows_arena + img->rows_off + img->mcuv; fin->bitpos = 0; fin->aux = kHuffDecRowUnwritten; } }
     if (img->flags & kHuffDecRstTable) return;
     int nphase = 0;
@@ -291,12 +338,17 @@ WDEV void simt_place(const HuffDecImage* img, SimtImage* si, const SimtSub* sub,
     uint32_t run = 0;
     int dc[4] = {0, 0, 0, 0};
     // (blind images, simt_blind_phases: component of every slot of the MCU)
-    const int blind = simt_blind_phases(img);
+    const int blind = simt_blind_phases_with(img, slots);
     int slot_cmp[4] = {0, 0, 0, 0};
+    uint32_t slot_cmps = 0;                                // (more than four slots: two bits each, slot p at bit 2p)
     if (blind) {
         int p = 0;
         for (int ci = 0; ci < img->ncomp; ++ci)
-            for (int k = img->hs[img->scan_cmp[ci]] * img->vs[img->scan_cmp[ci]]; k > 0; --k) { if (p < 4) slot_cmp[p] = img->scan_cmp[ci] & 3; ++p; }
+            for (int k = img->hs[img->scan_cmp[ci]] * img->vs[img->scan_cmp[ci]]; k > 0; --k) {
+                if (p < 4) slot_cmp[p] = img->scan_cmp[ci] & 3;
+                if (p < kSimtBlindSlots) slot_cmps |= (uint32_t)(img->scan_cmp[ci] & 3) << (2 * p);
+                ++p;
+            }
     }
     for (uint32_t base = 0; base < nsub; base += 64) {
         LV(int, nb); LV(int, ex);
@@ -309,6 +361,23 @@ WDEV void simt_place(const HuffDecImage* img, SimtImage* si, const SimtSub* sub,
             L(d0) = in ? sub[i].dcsum[0] : 0; L(d1) = in ? sub[i].dcsum[1] : 0; L(d2) = in ? sub[i].dcsum[2] : 0; L(d3) = in ? sub[i].dcsum[3] : 0;
         }
         const int tn = lepwave::wave_excl_scan(nb, ex);
+        if (blind > 4) {                                   // the same from the side array: slot sums mod 2^16, two to a dword
+            LANES(l) {
+                const uint32_t i = base + (uint32_t)l;
+                uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+                if (i < nsub) {
+                    const SimtSlots* w = slots + si->slots + i;
+                    uint32_t slot = (run + (uint32_t)L(ex)) % (uint32_t)blind;
+                    for (int r = 0; r < blind; ++r) {
+                        const uint32_t pr = w->pair[r >> 1], v = (r & 1) ? pr >> 16 : pr & 0xffffu;
+                        const uint32_t cmp = (slot_cmps >> (2u * slot)) & 3u;
+                        if (cmp == 0) c0 += v; else if (cmp == 1) c1 += v; else if (cmp == 2) c2 += v; else c3 += v;
+                        slot = slot + 1 == (uint32_t)blind ? 0u : slot + 1;
+                    }
+                }
+                L(d0) = (int16_t)c0; L(d1) = (int16_t)c1; L(d2) = (int16_t)c2; L(d3) = (int16_t)c3;
+            }
+        } else
         if (blind) {                                       // slot sums -> component sums, now that the lane's first slot is known
             LANES(l) {
                 const uint32_t first = (run + (uint32_t)L(ex)) % (uint32_t)blind;
