@@ -213,7 +213,8 @@ typedef struct lep_huffdec_image {
     uint32_t scan_len;
     int32_t ncomp, mcuh, mcuv, mcuc, rsti;
     int32_t flags;                       /* LEP_HUFFDEC_EARLY_EOF: the file ends inside its scan (no EOI): the scan may stop in mid-image */
-    int32_t reserved0;
+    int32_t first_mcu_row;               /* > 0: blocks of the MCU rows in front of it are decoded (records, status, DC chain) but not stored: their part of the
+                                          * frame stays zero.  One-component images: block rows (the planned mcuv).  0 = the whole frame */
     int32_t hs[4], vs[4], bch[4], dc_tbl[4], ac_tbl[4], scan_cmp[4];
     int16_t *blocks[4];                  /* device: zero-filled coefficient frame */
     uint64_t rows_off;
@@ -426,7 +427,8 @@ int lep_compress(lep_gpu *g, const uint8_t *jpg, size_t len, lep_bytes *out);
  * restores bytes [start_byte, trunc) of the JPEG (trunc 0 = to the end) -- how a JPEG stored as fixed-size blocks is
  * compressed block by block.  Format flag 'Y': header segments reduced to the ones the scan needs, hand-off rows in front of
  * start_byte dropped, the bytes up to the first remaining MCU row kept verbatim.  lep_decompress reads such files like any
- * other.  Progressive files cannot be sliced (PROGRESSIVE_UNSUPPORTED), as in the reference. */
+ * other.  Progressive files cannot be sliced (PROGRESSIVE_UNSUPPORTED), as in the reference.
+ * One file per call, on the host parser; lep_compress_batch_slices takes many slices through the batch pipeline and gives the same bytes. */
 int lep_compress_slice(lep_gpu *g, const uint8_t *jpg, size_t len, size_t start_byte, size_t trunc, lep_bytes *out);
 int lep_decompress(lep_gpu *g, const uint8_t *lepdata, size_t len, lep_bytes *out);
 
@@ -462,6 +464,14 @@ typedef struct lep_batch_stats {
 } lep_batch_stats;
 int lep_compress_batch(lep_gpu *g, const lep_bytes *jpgs, int n, lep_bytes *outs, int32_t *status,
                        const lep_batch_options *opt, lep_batch_stats *stats);
+/* The same pipeline for `-startbyte / -trunc` slices: jpgs[i] is the file from its first byte, slices[i] what lep_compress_slice takes as
+ * start_byte / trunc ({0, 0} = the whole file; slices == NULL = lep_compress_batch).  outs[i] / status[i] are byte for byte what
+ * lep_compress_slice returns for the same arguments, its refusal codes included.  Slices of the layouts the GPU scan decoder takes whole
+ * are decoded there (stats->gpu_huffman_files counts them); with opt->verify their scan is written again on the GPU from the first kept
+ * hand-off on and held to the file's bytes.  Everything else goes to the host parser inside the pipeline. */
+typedef struct lep_slice { size_t start_byte, trunc; } lep_slice;
+int lep_compress_batch_slices(lep_gpu *g, const lep_bytes *jpgs, const lep_slice *slices, int n, lep_bytes *outs, int32_t *status,
+                              const lep_batch_options *opt, lep_batch_stats *stats);
 int lep_decompress_batch(lep_gpu *g, const lep_bytes *leps, int n, lep_bytes *outs, int32_t *status,
                          const lep_batch_options *opt, lep_batch_stats *stats);
 /* the chunking lep_compress_batch will apply: file_bytes[i] / frame_bytes[i] (lep_jpeg_peek_frame_bytes; 0 = not a usable file)

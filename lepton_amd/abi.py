@@ -80,7 +80,7 @@ class HuffProgScan(C.Structure):
 
 class HuffDecImage(C.Structure):
     _fields_ = [("scan", C.c_void_p), ("scan_len", C.c_uint32), ("ncomp", C.c_int32), ("mcuh", C.c_int32), ("mcuv", C.c_int32), ("mcuc", C.c_int32),
-                ("rsti", C.c_int32), ("flags", C.c_int32), ("reserved0", C.c_int32), ("hs", C.c_int32 * 4), ("vs", C.c_int32 * 4), ("bch", C.c_int32 * 4), ("dc_tbl", C.c_int32 * 4),
+                ("rsti", C.c_int32), ("flags", C.c_int32), ("first_mcu_row", C.c_int32), ("hs", C.c_int32 * 4), ("vs", C.c_int32 * 4), ("bch", C.c_int32 * 4), ("dc_tbl", C.c_int32 * 4),
                 ("ac_tbl", C.c_int32 * 4), ("scan_cmp", C.c_int32 * 4), ("blocks", C.c_void_p * 4), ("rows_off", C.c_uint64),
                 ("lut", (C.c_uint16 * 512) * 4), ("maxcode", (C.c_int32 * 8) * 4), ("valoff", (C.c_int32 * 8) * 4), ("longsym", (C.c_uint8 * 256) * 4)]
 
@@ -98,6 +98,10 @@ class HuffDecRow(C.Structure):
 
 class BatchOptions(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("verify", C.c_int32), ("chunk_frame_bytes", C.c_size_t), ("host_huffman", C.c_int32), ("chunk_images", C.c_int32), ("overlap_launches", C.c_int32)]
+
+
+class Slice(C.Structure):
+    _fields_ = [("start_byte", C.c_size_t), ("trunc", C.c_size_t)]
 
 
 class BatchStats(C.Structure):
@@ -198,6 +202,8 @@ def lib():
         L.lep_decompress.argtypes = [vp, vp, C.c_size_t, P(Bytes)]
         L.lep_jpeg_is_progressive.argtypes = [vp]
         L.lep_compress_batch.argtypes = [vp, P(Bytes), C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(BatchStats)]
+        if hasattr(L, "lep_compress_batch_slices"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_compress_batch_slices.argtypes = [vp, P(Bytes), P(Slice), C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(BatchStats)]
         L.lep_decompress_batch.argtypes = [vp, P(Bytes), C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(BatchStats)]
         L.lep_jpeg_open_gpu.argtypes = [vp, C.c_size_t, P(vp), P(HuffDecImage), P(C.c_int)]
         L.lep_jpeg_scan_bytes.argtypes = [vp, P(vp), P(C.c_size_t)]
@@ -254,5 +260,5 @@ EXPORTS = [
     "lep_file_recode_plan_progressive", "lep_file_recode_finish_progressive", "lep_gpu_huffman_progressive_encode_device",
     "lep_jpeg_open_gpu_progressive", "lep_jpeg_finish_gpu_progressive", "lep_jpeg_scan_restarts_of", "lep_gpu_huffman_progressive_decode_device",
     "lep_jpeg_plan_progressive_check", "lep_gpu_last_stage_ms", "lep_jpeg_set_container_version", "lep_container_can_write_version", "lep_jpeg_plan_scan_check", "lep_jpeg_scan_file_range",
-    "lep_gpu_huffman_progressive_encode_forms",
+    "lep_gpu_huffman_progressive_encode_forms", "lep_compress_batch_slices",
 ]

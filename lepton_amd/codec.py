@@ -247,10 +247,20 @@ class GpuCodec:
                 self._L.lep_free(outs[i].data)
         return res, list(status), {k: getattr(stats, k) for k, _ in abi.BatchStats._fields_}
 
-    def compress_batch(self, jpgs, verify=False, threads=0, chunk_bytes=0, chunk_images=0, host_huffman=False):
+    def compress_batch(self, jpgs, verify=False, threads=0, chunk_bytes=0, chunk_images=0, host_huffman=False, slices=None):
         """[jpeg bytes] -> ([.lep bytes or None], [exit code per file], pipeline statistics); the JPEG Huffman scan decode runs
-        on the GPU for eligible files unless host_huffman is set"""
-        return self._batch(self._L.lep_compress_batch, jpgs, verify, threads, chunk_bytes, chunk_images, host_huffman)
+        on the GPU for eligible files unless host_huffman is set.  slices: one (start_byte, trunc) per file, `lepton -startbyte
+        -trunc` ((0, 0) = the whole file); the results are compress_slice's, file by file"""
+        if slices is None:
+            return self._batch(self._L.lep_compress_batch, jpgs, verify, threads, chunk_bytes, chunk_images, host_huffman)
+        if len(slices) != len(jpgs):
+            raise ValueError("one (start_byte, trunc) pair per file")
+        arr = (abi.Slice * max(1, len(slices)))(*[abi.Slice(int(s), int(t)) for s, t in slices])
+
+        def fn(handle, ins, n, outs, status, opt, stats):
+            return self._L.lep_compress_batch_slices(handle, ins, arr, n, outs, status, opt, stats)
+
+        return self._batch(fn, jpgs, verify, threads, chunk_bytes, chunk_images, host_huffman)
 
     def decompress_batch(self, leps, threads=0, chunk_bytes=0, chunk_images=0, host_huffman=False):
         """[.lep bytes] -> ([jpeg bytes or None], [exit code per file], pipeline statistics); the JPEG Huffman re-encode runs

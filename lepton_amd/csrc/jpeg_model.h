@@ -94,6 +94,10 @@ struct JpegFile {
     // parse_jpeg.  prefix_garbage = the raw bytes from start_byte up to the first MCU row that starts at or after it.
     uint32_t start_byte = 0;
     std::vector<uint8_t> prefix_garbage;
+    // a slice on the GPU parse path: the file's bytes as parse_jpeg_prepare_gpu saw them (the caller's memory, alive until
+    // parse_jpeg_finish_gpu has taken the prefix garbage from it)
+    const uint8_t* slice_src = nullptr;
+    size_t slice_src_len = 0;
     // -embedding=<n> (jpgcoder.cc:365, 1135-1137, 2275-2282): the JPEG sits n bytes into a larger blob; those n bytes are kept as
     // prefix garbage ('PGE' section), what follows EOI as ordinary garbage, and the .lep restores the whole blob
     bool embedded = false;
@@ -150,7 +154,7 @@ struct ScanDecodePlan {
     const uint8_t* scan;
     uint32_t scan_len;
     int32_t ncomp, mcuh, mcuv, mcuc, rsti;
-    int32_t flags, reserved0;              /* flags: kScanEarlyEof */
+    int32_t flags, first_mcu_row;          /* flags: kScanEarlyEof; first_mcu_row: the kernels store no block of the rows in front of it */
     int32_t hs[4], vs[4], bch[4], dc_tbl[4], ac_tbl[4], scan_cmp[4];
     int16_t* blocks[4];
     uint64_t rows_off;
@@ -164,6 +168,9 @@ struct ScanDecodeRow {
     int32_t aux;
 };
 int parse_jpeg_prepare_gpu(const uint8_t* data, size_t size, JpegFile* jf, ScanDecodePlan* plan, bool* eligible);
+// -startbyte, once the hand-off rows exist (parse_jpeg and parse_jpeg_finish_gpu both end in it): rows in front of jf->start_byte dropped,
+// the bytes from there to the first kept row as prefix garbage; EX_ONLY_GARBAGE_NO_JPEG when no row is left
+int apply_start_byte(JpegFile* jf, const uint8_t* data, size_t size);
 int parse_jpeg_finish_gpu(JpegFile* jf, const ScanDecodeRow* rows);
 
 // Progressive files on the GPU scan decoder (lep_huffprogdec.h).  ProgScanDecodePlan is laid out exactly like

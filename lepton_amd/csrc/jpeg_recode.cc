@@ -133,7 +133,12 @@ int recode_prepare(LepFile* lf, RecodePlan* plan) {
     JpegFile& jf = lf->jpeg;
     plan->gpu_ok = false;
     plan->segs.clear();
-    if (lf->flag != 'Z') return 0;   // progressive / multi-scan files: recode_progressive (jpeg_progressive.cc), host only
+    // 'Z' and 'Y' (a -startbyte slice) take the baseline re-coder (recode_jpeg below); everything else is recode_progressive's
+    // (jpeg_progressive.cc).  A slice is planned like a whole file: its head is the prefix garbage alone (below), its first hand-off
+    // starts at the first MCU row the slice keeps -- with that row's DC predictors and, where the row starts inside a byte, that byte's
+    // leading bits as the writer's seed, exactly as a later segment of a whole file starts -- and its bounds are the slice's
+    // (jpeg_size = the slice's length).
+    if (!(lf->flag == 'Z' || (lf->flag & 1) == ('Y' & 1))) return 0;
     const size_t max_file_size = lf->jpeg_size;
     if ((int32_t)lf->jpeg_size <= (int32_t)jf.garbage.size()) return EX_ASSERTION_FAILURE;   // always_assert(max_file_size > grbs), both ints
     plan->scan_bound = max_file_size - jf.garbage.size();

@@ -629,6 +629,9 @@ int parse_jpeg_prepare_gpu(const uint8_t* data, size_t size, JpegFile* jf, ScanD
     if (!setup_frame(jf)) return jf->warn < 0 ? -jf->warn : EX_UNSUPPORTED_JPEG;
     if (jf->ncomp > 3) return EX_UNSUPPORTED_4_COLORS;
     if (jf->jpegtype != 1) return 0;
+    // (a slice, start_byte != 0: the same layouts as a whole file -- the scan is decoded from its first block whatever the slice keeps,
+    // the DC predictors of the first kept row are sums from there; parse_jpeg_finish_gpu drops the rows in front of start_byte)
+    jf->slice_src = jf->start_byte ? data : nullptr; jf->slice_src_len = jf->start_byte ? size : 0;
     // (a file that ends inside its scan -- no EOI -- is eligible: the kernels decode up to the block that reads the data's last bit and
     // say how far they came; anything odd in that last block is left to the host parser, which knows the reference's rules there)
     const uint8_t* h = jf->hdr.data();
@@ -792,6 +795,13 @@ int parse_jpeg_finish_gpu(JpegFile* jf, const ScanDecodeRow* all_rows) {
     }
     if (jf->early_eof) note_truncation(jf);
     jf->progressive_needed = false;
+    if (jf->start_byte) {
+        // a slice: what parse_jpeg does behind decode_scans.  A warning level (the host parser refuses the file before it looks at
+        // start_byte) and a slice that holds no row are the host parser's to name: the caller parses the file again there.
+        if (jf->warn > 0 || !jf->slice_src) return -1;
+        if (apply_start_byte(jf, jf->slice_src, jf->slice_src_len)) return -1;
+        jf->slice_src = nullptr; jf->slice_src_len = 0;
+    }
     return 0;
 }
 
@@ -1112,8 +1122,13 @@ int parse_jpeg(const uint8_t* data, size_t size, bool allow_progressive, JpegFil
     // byte for byte by a canonical re-encoder
     if (!rc && jf->warn > 0) { if (jf->error.empty()) jf->error = "non-canonical JPEG (reference errorlevel 1)"; return EX_UNSUPPORTED_JPEG; }
     if (rc || !jf->start_byte) return rc;
-    // -startbyte: drop the hand-off rows that lie in front of start_byte (the last record always stays) and keep the raw
-    // bytes between start_byte and the first remaining row as prefix garbage (write_ujpg, jpgcoder.cc:3801-3843)
+    return apply_start_byte(jf, data, size);
+}
+
+// -startbyte: drop the hand-off rows that lie in front of start_byte (the last record always stays) and keep the raw
+// bytes between start_byte and the first remaining row as prefix garbage (write_ujpg, jpgcoder.cc:3801-3843).  The rows are
+// decode_scans' or, for a file whose scan the GPU decoded, parse_jpeg_finish_gpu's: the same records either way.
+int apply_start_byte(JpegFile* jf, const uint8_t* data, size_t size) {
     std::vector<Handoff> kept;
     for (size_t i = 0; i < jf->rows.size(); ++i)
         if (i + 1 == jf->rows.size() || jf->rows[i].segment_size >= jf->start_byte) kept.push_back(jf->rows[i]);

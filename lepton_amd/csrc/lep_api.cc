@@ -10,6 +10,7 @@
 
 #include "jpeg_model.h"
 #include "lep_container.h"
+#include "lep_slice.h"
 
 struct lep_jpeg {
     lep::JpegFile jf;
@@ -107,14 +108,7 @@ int lep_jpeg_open_into(const uint8_t* jpg, size_t len, int allow_progressive, vo
     return 0;
 }
 int lep_jpeg_open_slice(const uint8_t* jpg, size_t len, size_t start_byte, lep_jpeg** out) {
-    if (start_byte > 0xffffffffu) return LEP_ASSERTION_FAILURE;
-    std::unique_ptr<lep_jpeg> j(new lep_jpeg);
-    j->jf.start_byte = (uint32_t)start_byte;
-    j->opt.allow_progressive = start_byte == 0;
-    int rc = lep::parse_jpeg(jpg, len, start_byte == 0, &j->jf);
-    if (rc) return rc;
-    *out = j.release();
-    return 0;
+    return lep_jpeg_open_slice_into(jpg, len, start_byte, nullptr, 0, out);
 }
 int lep_jpeg_open_embedded(const uint8_t* blob, size_t len, size_t offset, lep_jpeg** out) {
     if (offset + 4 > len || len > 0xffffffffu) return LEP_UNSUPPORTED_JPEG;
@@ -131,14 +125,7 @@ int lep_jpeg_open_embedded(const uint8_t* blob, size_t len, size_t offset, lep_j
     return 0;
 }
 int lep_jpeg_open_gpu(const uint8_t* jpg, size_t len, lep_jpeg** out, lep_huffdec_image* image, int* eligible) {
-    std::unique_ptr<lep_jpeg> j(new lep_jpeg);
-    j->opt.allow_progressive = true;
-    bool ok = false;
-    int rc = lep::parse_jpeg_prepare_gpu(jpg, len, &j->jf, reinterpret_cast<lep::ScanDecodePlan*>(image), &ok);
-    if (rc) return rc;
-    *eligible = ok ? 1 : 0;
-    *out = j.release();
-    return 0;
+    return lep_jpeg_open_gpu_slice(jpg, len, 0, out, image, eligible);
 }
 int lep_jpeg_open_gpu_progressive(lep_jpeg* j, lep_huffprogdec_scan* scans, int cap, int* nscan, int* rows_needed, int* eligible) {
     *eligible = 0; *nscan = 0; *rows_needed = 0;
@@ -261,11 +248,18 @@ int lep_jpeg_plan_handoffs(const lep_jpeg* j, int max_threads, lep_handoff* out,
 int lep_jpeg_plan_scan_check(lep_jpeg* j, size_t jpeg_len, lep_huff_image* image, lep_huff_segment* segs, uint32_t* file_first, uint32_t* file_len, int cap,
                              int* nseg, int* eligible) {
     *eligible = 0; *nseg = 0;
-    if (!j || j->jf.scan_file_range.size() != 1 || j->jf.progressive_needed || j->jf.start_byte || j->jf.embedded || j->jf.early_eof) return 0;
+    if (!j || j->jf.scan_file_range.size() != 1 || j->jf.progressive_needed || j->jf.embedded || j->jf.early_eof) return 0;
+    // A slice ('Y'): the writer is held to the bytes from its first kept hand-off on -- the partial byte that record carries included, which
+    // is why the prefix garbage ends one byte in front of the record's position.  A slice whose first kept record stands exactly AT
+    // start_byte (no prefix, so that byte lies in front of the slice), or that keeps the final record alone, has no such tiling: the
+    // per-file check restores it on the host and decides.
+    const uint32_t start = j->jf.start_byte;
+    if (start && (j->jf.rows.size() < 2 || j->jf.rows[0].segment_size <= start || jpeg_len <= start)) return 0;
     std::vector<lep::Handoff> hs = lep::plan_segments(j->jf, j->opt);
     if (hs.empty() || (int)hs.size() > cap) return 0;
     lep::LepFile lf;
-    lf.version = j->opt.format_version; lf.flag = 'Z'; lf.nthreads = (int)hs.size(); lf.jpeg_size = (uint32_t)jpeg_len;
+    lf.version = j->opt.format_version; lf.flag = start ? 'Y' : 'Z'; lf.nthreads = (int)hs.size(); lf.jpeg_size = (uint32_t)(jpeg_len - start);
+    if (start) { lf.has_prefix = true; lf.prefix_garbage = j->jf.prefix_garbage; }
     lf.segs = hs;
     lf.rst_cnt_set = !j->jf.rst_cnt.empty();
     // the parsed JPEG is lent to the plan (recode_prepare re-reads the tables in front of the scan from the same header bytes)
@@ -283,7 +277,8 @@ int lep_jpeg_plan_scan_check(lep_jpeg* j, size_t jpeg_len, lep_huff_image* image
     }
     if (rc || !plan.gpu_ok || plan.segs.size() != hs.size()) return 0;
     const auto& r = j->jf.scan_file_range[0];
-    uint64_t at = r.first;
+    uint64_t at = start ? (uint64_t)j->jf.rows[0].segment_size - 1 : r.first;
+    if (at < r.first) return 0;                         // (a first record in front of the scan's first byte: not a row of this scan)
     for (size_t q = 0; q < hs.size(); ++q) {
         file_first[q] = (uint32_t)at; file_len[q] = hs[q].segment_size;
         at += hs[q].segment_size;
@@ -410,6 +405,36 @@ int lep_file_segments(const lep_file* f, lep_segment* segs, lep_bytes* streams, 
 }
 
 }  // extern "C"
+
+// ---- `-startbyte` slices inside the library (lep_slice.h): C++ linkage, not part of the C ABI ---------------------------------------
+int lep_jpeg_open_slice_into(const uint8_t* jpg, size_t len, size_t start_byte, void* frame_mem, size_t frame_cap, lep_jpeg** out) {
+    if (start_byte > 0xffffffffu) return LEP_ASSERTION_FAILURE;
+    std::unique_ptr<lep_jpeg> j(new lep_jpeg);
+    j->jf.ext_mem = (int16_t*)frame_mem; j->jf.ext_cap = frame_mem ? frame_cap : 0;
+    j->jf.start_byte = (uint32_t)start_byte;
+    j->opt.allow_progressive = start_byte == 0;
+    int rc = lep::parse_jpeg(jpg, len, start_byte == 0, &j->jf);
+    if (rc) return rc;
+    *out = j.release();
+    return 0;
+}
+int lep_jpeg_open_gpu_slice(const uint8_t* jpg, size_t len, size_t start_byte, lep_jpeg** out, lep_huffdec_image* image, int* eligible) {
+    if (start_byte > 0xffffffffu) return LEP_ASSERTION_FAILURE;
+    std::unique_ptr<lep_jpeg> j(new lep_jpeg);
+    j->jf.start_byte = (uint32_t)start_byte;
+    j->opt.allow_progressive = start_byte == 0;
+    bool ok = false;
+    int rc = lep::parse_jpeg_prepare_gpu(jpg, len, &j->jf, reinterpret_cast<lep::ScanDecodePlan*>(image), &ok);
+    if (rc) return rc;
+    *eligible = ok ? 1 : 0;
+    *out = j.release();
+    return 0;
+}
+int lep_jpeg_slice_tiles(const lep_jpeg* j) {
+    return !j->jf.start_byte || (j->jf.rows.size() >= 2 && j->jf.rows[0].segment_size > j->jf.start_byte) ? 1 : 0;
+}
+int lep_jpeg_first_kept_luma_row(const lep_jpeg* j) { return j->jf.start_byte && !j->jf.rows.empty() ? j->jf.rows[0].luma_y_start : 0; }
+
 namespace lep {
 // jpeg_recode.cc: the planned segments' scan bytes and end states from host threads (one per segment); recode_finish takes them like the GPU's
 int recode_segments_on_threads(LepFile* lf, const RecodePlan& plan, std::vector<std::vector<uint8_t>>* seg_bytes, std::vector<lep_huff_end>* ends);

@@ -28,6 +28,7 @@
 #include "jpeg_model.h"
 #include "lep_buffers.h"
 #include "lep_container.h"
+#include "lep_slice.h"
 
 namespace {
 
@@ -333,8 +334,24 @@ void lep_batch_debug_poison(int value) {
 // ---- JPEG -> .lep, batch ---------------------------------------------------------------------------------------------
 int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs, int32_t* status, const lep_batch_options* o,
                        lep_batch_stats* stats) {
+    return lep_compress_batch_slices(g, jpgs, nullptr, n, outs, status, o, stats);
+}
+
+// slices[i] = {start_byte, trunc} of files[i] (`lepton -startbyte -trunc`; NULL: whole files): -trunc bounds the reader, so everything
+// below sees the file as its first `trunc` bytes; start_byte travels to the parsers, which drop the hand-off rows in front of it, and to
+// whatever holds the result against the input -- bytes [start_byte, len).
+int lep_compress_batch_slices(lep_gpu* g, const lep_bytes* files, const lep_slice* slices, int n, lep_bytes* outs, int32_t* status,
+                              const lep_batch_options* o, lep_batch_stats* stats) {
     if (!g || n < 0) return LEP_GPU_ERROR;
     g_batch_gpu = g;
+    std::vector<lep_bytes> bounded(files, files + n);
+    std::vector<size_t> start((size_t)n, 0);
+    if (slices)
+        for (int i = 0; i < n; ++i) {
+            if (slices[i].trunc && slices[i].trunc < bounded[i].len) bounded[i].len = slices[i].trunc;
+            start[i] = slices[i].start_byte;
+        }
+    const lep_bytes* jpgs = bounded.data();
     const int threads = o && o->host_threads > 0 ? o->host_threads : effective_cpus();
     // With the Huffman decode on the GPU, chunk k+1 is decoded (lep_huffdec_simt.h, one lane per piece of the scan, on its own stream)
     // WHILE the split-phase encoder's kernels of chunk k run.  The chunking itself is lep_batch_plan (lep_api.cc).
@@ -348,7 +365,11 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
     // 1. frame sizes from the SOF markers -> the whole batch is cut into chunks before anything is decoded (lep_batch_plan),
     //    so that every image can be Huffman-decoded straight into its place in a staging buffer (no page faults, no second copy)
     std::vector<size_t> fbytes(n, 0), jbytes(n, 0);
-    parallel_for(n, threads, [&](int i) { jbytes[i] = jpgs[i].len; if (int rc = lep_jpeg_peek_frame_bytes(jpgs[i].data, jpgs[i].len, &fbytes[i])) { status[i] = rc; fbytes[i] = 0; } });
+    parallel_for(n, threads, [&](int i) {
+        jbytes[i] = jpgs[i].len;
+        if (start[i] > 0xffffffffu) { status[i] = LEP_ASSERTION_FAILURE; return; }   // (lep_jpeg_open_slice's first refusal)
+        if (int rc = lep_jpeg_peek_frame_bytes(jpgs[i].data, jpgs[i].len, &fbytes[i])) { status[i] = rc; fbytes[i] = 0; }
+    });
     std::vector<int> first((size_t)n + 2, 0);
     const int nchunks = lep_batch_plan(jbytes.data(), fbytes.data(), n, o, first.data(), n + 2);
     if (nchunks < 0) return LEP_ASSERTION_FAILURE;
@@ -393,7 +414,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
         const int i = c->live[k];
         const size_t room = (k + 1 < (int)c->live.size() ? c->frame_off[k + 1] : c->frame_bytes) - c->frame_off[k];
         if (parsed[i]) { lep_jpeg_close(parsed[i]); parsed[i] = nullptr; }
-        int rc = lep_jpeg_open_into(jpgs[i].data, jpgs[i].len, 1, s->h_frames + c->frame_off[k], room, &parsed[i]);
+        int rc = lep_jpeg_open_slice_into(jpgs[i].data, jpgs[i].len, start[i], s->h_frames + c->frame_off[k], room, &parsed[i]);   // (start 0: lep_jpeg_open_into)
         host_parsed[i] = 1;
         if (!rc) {
             lep_jpeg_describe(parsed[i], &c->host_desc[k]);
@@ -435,7 +456,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
             parallel_for(nl, threads, [&](int k) {
                 const int i = c->live[k];
                 int ok = 0;
-                int rc = lep_jpeg_open_gpu(jpgs[i].data, jpgs[i].len, &parsed[i], &himg[k], &ok);
+                int rc = lep_jpeg_open_gpu_slice(jpgs[i].data, jpgs[i].len, start[i], &parsed[i], &himg[k], &ok);
                 if (rc) { status[i] = rc; return; }      // not a JPEG the reference would take either
                 if (ok) { on_gpu[k] = 1; return; }
                 {
@@ -767,6 +788,21 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
             if (int rc = prog_reserve(s, c->pscan_bytes + 256, c->corr_words + 16, c->pscan.size())) return rc;
             HIPOK(hipMemcpyAsync(s->d_pcheck, c->pcheck.data(), c->pcheck.size() * sizeof(ScanCheck), hipMemcpyHostToDevice, s_copy));
         }
+        // A slice's frame rows in front of its first kept hand-off belong to nobody: no thread segment codes them, the decoder leaves them
+        // zero, no writer reads them.  The scan decoders fill them all the same (first_mcu_row = 0: which rows lie in front of start_byte
+        // is only known from the records they leave), so they are wiped here, behind every upload and scan decode of the chunk and in
+        // front of the coder kernels: the frame comparison of `verify` then holds the rows that count and no others.
+        // (only `verify` looks at them: its frame comparison.  Without it they are left as decoded, as the per-file path leaves them.)
+        for (size_t k = 0; verify && k < c->live.size(); ++k) {
+            const int i = c->live[k];
+            if (!start[i]) continue;
+            const lep_image_desc& d = c->host_desc[k];
+            const int y0 = lep_jpeg_first_kept_luma_row(parsed[i]);
+            for (int cc = 0; cc < d.ncomp && y0 > 0 && d.height_blocks[0] > 0; ++cc) {
+                const size_t rows = std::min<size_t>((size_t)y0 * (size_t)d.height_blocks[cc] / (size_t)d.height_blocks[0], (size_t)d.height_blocks[cc]);
+                if (rows) HIPOK(hipMemsetAsync(c->dev_desc[k].blocks[cc], 0, rows * (size_t)d.width_blocks[cc] * 128, s_copy));
+            }
+        }
         HIPOK(hipEventRecord(s->up, s_copy));
         return 0;
     };
@@ -892,11 +928,14 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
                     // it on the host and compares (nothing is released on an argument)
                     else if (!rc && !host_parsed[i] && !c->vchecked[k] && !c->pchecked[k]) rc = LEP_BUFFER_TOO_SMALL;
                 }
+                // a slice at one of the positions the reference's own re-coder does not restore: lep_compress_slice restores every file it
+                // writes and names the refusal, so such a slice takes the per-file path whether or not the caller asked for `verify`
+                if (!rc && !lep_jpeg_slice_tiles(parsed[i])) rc = LEP_BUFFER_TOO_SMALL;
                 if (!rc) rc = lep_jpeg_write_lep(parsed[i], 0, strs, s1 - s0, &outs[i]);
                 // the Huffman half of the reference's round-trip check for the files whose scans the host parser took (their
                 // frame is still in this slot's pinned staging); the files the GPU decoded had theirs on the GPU (flags, above)
                 if (!rc && verify && host_parsed[i]) {
-                    rc = lep_jpeg_check_restores(parsed[i], outs[i].data, outs[i].len, jpgs[i].data, jpgs[i].len);
+                    rc = lep_jpeg_check_restores(parsed[i], outs[i].data, outs[i].len, jpgs[i].data + start[i], jpgs[i].len - start[i]);   // (a slice that parsed: start < len)
                     if (rc) { lep_free(outs[i].data); outs[i].data = nullptr; outs[i].len = outs[i].cap = 0; }
                 }
                 status[i] = rc;
@@ -916,11 +955,11 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
         for (int i = 0; i < n; ++i) {
             if (status[i] != LEP_BUFFER_TOO_SMALL) continue;
             lep_bytes o; o.data = nullptr; o.len = o.cap = 0;
-            int rc = lep_compress(g, jpgs[i].data, jpgs[i].len, &o);
+            int rc = lep_compress_slice(g, jpgs[i].data, jpgs[i].len, start[i], 0, &o);
             if (!rc && verify) {   // the arithmetic-coder half of the round-trip check, through the per-file decoder
                 lep_bytes back; back.data = nullptr; back.len = back.cap = 0;
                 rc = lep_decompress(g, o.data, o.len, &back);
-                if (!rc && (back.len != jpgs[i].len || memcmp(back.data, jpgs[i].data, back.len))) rc = LEP_ROUNDTRIP_FAILURE;
+                if (!rc && (back.len != jpgs[i].len - start[i] || memcmp(back.data, jpgs[i].data + start[i], back.len))) rc = LEP_ROUNDTRIP_FAILURE;
                 lep_free(back.data);
                 if (rc) { lep_free(o.data); o.data = nullptr; o.len = o.cap = 0; }
             }

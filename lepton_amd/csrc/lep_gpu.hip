@@ -545,6 +545,7 @@ struct lep_gpu {
                              // fill them, else 4 / 128 VGPRs, no spills); LEP_DEC_WAVES = 4 | 8 forces one
     std::string err;
     const char* last_kernel = "";   // name of the kernel the most recent launch used
+    char simt_name[112] = "";       // ... of the lane-per-subsequence scan decoder: with the lanes and the subsequence length of that launch
     // Device memory the object owns (round 4): every large grow-only workspace below is a virtual address range of its own (hipMemAddressReserve)
     // into which physical chunks of 512 MB (hipMemCreate) are mapped as it grows -- growing maps more chunks behind what is there, nothing
     // is freed and taken again.  A workspace that is given back (lep_gpu_trim) is unmapped and its chunks go to the object's POOL, from
@@ -1575,7 +1576,10 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
-    g->last_kernel = "lep_huffman_simt_{settle,place,write}_kernel";
+    // (lanes of the launch and the subsequence length it was cut with -- LEP_HUFFDEC_SIMT_BITS or the rule above: tests that force short
+    // subsequences read here that they got them)
+    snprintf(g->simt_name, sizeof g->simt_name, "lep_huffman_simt_{settle,place,write}_kernel (%zu lanes, %u bits)", nsub_all, (unsigned)L);
+    g->last_kernel = g->simt_name;
     return 0;
 }
 

@@ -35,7 +35,8 @@ struct HuffDecImage {       // one image, device-visible
     uint32_t scan_len;
     int32_t ncomp, mcuh, mcuv, mcuc, rsti;
     int32_t flags;          // kHuffDecEarlyEof: the file ends inside its scan
-    int32_t reserved0;
+    int32_t first_mcu_row;  // blocks of MCU rows in front of it are decoded but not stored (their records are written): a -startbyte slice's
+                            // rows in front of its first hand-off, which nobody reads.  0 = every row
     int32_t hs[4], vs[4], bch[4], dc_tbl[4], ac_tbl[4], scan_cmp[4];
     int16_t* blocks[4];     // zero-filled frame (device)
     uint64_t rows_off;      // this image's first record in the row arena (mcuv + 1 records)
@@ -202,7 +203,7 @@ struct HuffDecWave {
         HuffDecRow* rows = rows_arena + img->rows_off;
         int lastdc[4] = {0, 0, 0, 0};
         int padbit = -1;
-        const int ncomp = img->ncomp, mcuh = img->mcuh, mcuv = img->mcuv, rsti = img->rsti;
+        const int ncomp = img->ncomp, mcuh = img->mcuh, mcuv = img->mcuv, rsti = img->rsti, first_row = img->first_mcu_row;
         int rstw = rsti;
         int mcu = 0;
         for (int row = 0; row < mcuv && !status; ++row) {
@@ -227,7 +228,7 @@ struct HuffDecWave {
                             lastdc[cmp] = dc;
                             LSYNC();
                             int16_t* dst = img->blocks[cmp] + (int64_t)((row * vs + v) * bch + mx * hs + h) * 64;
-                            LANES(l) { dst[l] = l == 49 ? (int16_t)dc : sh->blk[l]; sh->blk[l] = 0; }
+                            LANES(l) { if (row >= first_row) dst[l] = l == 49 ? (int16_t)dc : sh->blk[l]; sh->blk[l] = 0; }   // (row: uniform)
                             LSYNC();
                             if (uni(bitpos) > img->scan_len * 8u) status = 2;   // ran out of data inside a block
                         }

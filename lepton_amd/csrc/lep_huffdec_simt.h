@@ -452,6 +452,7 @@ WDEV void simt_write_intervals(const HuffDecImage* img, SimtShared* sh, SimtTile
                             rows[row].aux = 0;
                         }
                         const int cmp = sh->ph_cmp[phase], v = sh->ph_v[phase], h = sh->ph_h[phase];
+                        const bool kept = row >= img->first_mcu_row;
                         int16_t* dst = img->blocks[cmp] + (int64_t)((row * img->vs[cmp] + v) * img->bch[cmp] + mx * img->hs[cmp] + h) * 64;
                         int diff = 0;
                         const bool fine = d.store_block(img->dc_tbl[cmp], 2 + img->ac_tbl[cmp], tile_lane, &diff);
@@ -466,7 +467,7 @@ WDEV void simt_write_intervals(const HuffDecImage* img, SimtShared* sh, SimtTile
                                 Quad v4;
                                 v4[0] = tile->w[(4 * q + 0) * 64 + l]; v4[1] = tile->w[(4 * q + 1) * 64 + l]; v4[2] = tile->w[(4 * q + 2) * 64 + l]; v4[3] = tile->w[(4 * q + 3) * 64 + l];
                                 tile->w[(4 * q + 0) * 64 + l] = 0u; tile->w[(4 * q + 1) * 64 + l] = 0u; tile->w[(4 * q + 2) * 64 + l] = 0u; tile->w[(4 * q + 3) * 64 + l] = 0u;
-                                out[q] = v4;
+                                if (kept) out[q] = v4;
                             }
                         }
                         if (!fine) { bad = 1; break; }
@@ -562,7 +563,7 @@ WDEV void simt_write(const HuffDecImage* img, SimtShared* sh, SimtTile* tile, Si
                 d.img = img; d.sh = sh;
                 d.br.words = reinterpret_cast<const uint32_t*>(img->scan); d.br.nwords = (img->scan_len + 3) >> 2;
                 d.br.seek(bp);
-                const int mcuh = img->mcuh;
+                const int mcuh = img->mcuh, first_row = img->first_mcu_row;
                 int mcu = (int)(before / (uint32_t)nphase);
                 int row = mcu / mcuh, mx = mcu - row * mcuh;
                 for (uint32_t k = 0; k < mine; ++k) {
@@ -572,6 +573,7 @@ WDEV void simt_write(const HuffDecImage* img, SimtShared* sh, SimtTile* tile, Si
                         rows[row].aux = 0;
                     }
                     const int cmp = sh->ph_cmp[phase], v = sh->ph_v[phase], h = sh->ph_h[phase];
+                    const bool kept = row >= first_row;     // (first_mcu_row: the block is decoded -- records, status, DC chain -- and not stored)
                     int16_t* dst = img->blocks[cmp] + (int64_t)((row * img->vs[cmp] + v) * img->bch[cmp] + mx * img->hs[cmp] + h) * 64;
                     int diff = 0;
                     const bool fine = d.store_block(img->dc_tbl[cmp], 2 + img->ac_tbl[cmp], tile_lane, &diff);
@@ -586,7 +588,7 @@ WDEV void simt_write(const HuffDecImage* img, SimtShared* sh, SimtTile* tile, Si
                             Quad v;
                             v[0] = tile->w[(4 * q + 0) * 64 + l]; v[1] = tile->w[(4 * q + 1) * 64 + l]; v[2] = tile->w[(4 * q + 2) * 64 + l]; v[3] = tile->w[(4 * q + 3) * 64 + l];
                             tile->w[(4 * q + 0) * 64 + l] = 0u; tile->w[(4 * q + 1) * 64 + l] = 0u; tile->w[(4 * q + 2) * 64 + l] = 0u; tile->w[(4 * q + 3) * 64 + l] = 0u;
-                            out[q] = v;
+                            if (kept) out[q] = v;
                         }
                     }
                     if (!fine) { bad = 1; break; }             // (also in the block that meets the end: the reference's rules there are the host's)
