@@ -28,6 +28,8 @@
 #include "jpeg_model.h"
 #include "lep_buffers.h"
 #include "lep_container.h"
+#include "lep_scan_routes.h"
+static_assert(LEP_HUFFDEC_RST_TABLE == 2, "lep_scan_routes.h reads the flag by its value");
 #include "lep_slice.h"
 
 namespace {
@@ -586,7 +588,7 @@ int lep_compress_batch_slices(lep_gpu* g, const lep_bytes* files, const lep_slic
             const bool simt = !(getenv("LEP_HUFFDEC_SIMT") && atoi(getenv("LEP_HUFFDEC_SIMT")) == 0);
             if (simt) {
                 std::vector<lep_huffdec_image> many, one;
-                for (const lep_huffdec_image& hi : launch) ((hi.rsti && !(hi.flags & LEP_HUFFDEC_RST_TABLE)) ? one : many).push_back(hi);
+                for (const lep_huffdec_image& hi : launch) (lephuff::simt_dec_takes(hi) ? many : one).push_back(hi);
                 if (!many.empty()) { if (int rc = lep_gpu_huffman_decode_simt_device(g, many.data(), (int)many.size(), s->d_rows, s_huff)) return rc; }
                 if (!one.empty()) { if (int rc = lep_gpu_huffman_decode_device(g, one.data(), (int)one.size(), s->d_rows, s_huff)) return rc; }
             } else
@@ -618,7 +620,7 @@ int lep_compress_batch_slices(lep_gpu* g, const lep_bytes* files, const lep_slic
                 // kernel before the host parser is bothered: its frame is wiped first (pass C may have written part of it)
                 std::vector<lep_huffdec_image> again;
                 for (const lep_huffdec_image& hi : launch) {
-                    if ((hi.rsti && !(hi.flags & LEP_HUFFDEC_RST_TABLE)) || ((rows[hi.rows_off + (size_t)hi.mcuv].aux >> 8) & 0x3fffff) == 0) continue;   // (bit 30: LEP_HUFFDEC_ROW_TRUNCATED, not a status)
+                    if (!lephuff::simt_dec_takes(hi) || ((rows[hi.rows_off + (size_t)hi.mcuv].aux >> 8) & 0x3fffff) == 0) continue;   // (bit 30: LEP_HUFFDEC_ROW_TRUNCATED, not a status)
                     for (int cc = 0; cc < hi.ncomp; ++cc)
                         HIPOK(hipMemsetAsync(hi.blocks[cc], 0, (size_t)hi.bch[cc] * hi.vs[cc] * hi.mcuv * 128, s_huff));
                     again.push_back(hi);

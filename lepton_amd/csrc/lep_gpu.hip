@@ -30,6 +30,7 @@
 #include "lep_huffprogdec.h"
 #include "lep_huffprogdec_win.h"
 #include "lep_huffprogdec_rst.h"
+#include "lep_scan_decode_plan.h"
 
 using namespace lepdev;
 
@@ -485,16 +486,7 @@ __global__ __launch_bounds__(64) void lep_huffman_simt_write_kernel(const lephuf
 }
 __global__ void lep_huffman_simt_finish_kernel(const lephuff::HuffDecImage* __restrict__ images, int nimg, lephuff::HuffDecRow* rows, const lephuff::SimtImage* si) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= nimg) return;
-    lephuff::HuffDecRow* last = rows + images[i].rows_off + images[i].mcuv;
-    int status = si[i].status & 0x3fffff;
-    if (last->aux == lephuff::kHuffDecRowUnwritten) { status |= 2; last->aux = 255; }   // no lane of the write pass got to the final record: irregular
-    if (images[i].flags & lephuff::kHuffDecRstTable) {      // restart intervals: the pad byte is what all intervals agreed on
-        const int pad = lephuff::simt_intervals_pad(si + i, &status);
-        last->aux = pad | (status << 8);
-        return;
-    }
-    last->aux = (last->aux & (255 | lephuff::kHuffDecRowTruncated)) | (status << 8);
+    if (i < nimg) lephuff::simt_finish(images + i, si + i, rows);
 }
 
 }  // namespace
@@ -1197,111 +1189,56 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
 
 static_assert(sizeof(lep_huffprogdec_scan) == sizeof(lephuff::ProgDecScan), "C ABI mirrors");
 
-static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* d_rows, hipStream_t st);
-static int progdec_launch_by_level(lep_gpu* g, const std::vector<lep_huffprogdec_scan>& scans, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here);
+static int progdec_launch_scans(lep_gpu* g, const lephuff::ProgDecPlan::Levels& b, lep_huffdec_row* d_rows, hipStream_t st);
+static int progdec_launch_by_level(lep_gpu* g, const lephuff::ProgDecPlan::Pieces& c, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here);
 
+// Which scans go to which kernels, in which order, with which marks and dependencies: lep_scan_decode_plan.h's plan.  Here: the
+// sequential frames' scans to the sequential decoders, then the files without a scan of the interval form, then those with one.
 int lep_gpu_huffman_progressive_decode_device(lep_gpu* g, const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* d_rows, void* hip_stream) {
     if (!g) return LEP_GPU_ERROR;
     if (nscan <= 0) return 0;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    // scans of SEQUENTIAL frames coded in several scans (lep_huffprogdec.h sequential_scan_image): no scan depends on another, each is an image
-    // of its own to the sequential kernels -- one lane per subsequence, or the single-wave kernel where there are restart intervals
-    std::vector<lep_huffprogdec_scan> progressive_only;
-    {
-        std::vector<lep_huffdec_image> many, one;
-        const bool simt = !(getenv("LEP_HUFFDEC_SIMT") && atoi(getenv("LEP_HUFFDEC_SIMT")) == 0);
-        for (int i = 0; i < nscan; ++i) {
-            const lephuff::ProgDecScan& sc = reinterpret_cast<const lephuff::ProgDecScan&>(scans[i]);
-            if (!lephuff::progdec_is_sequential(sc)) continue;
-            if (sc.cmpc < 1 || sc.cmpc > 4) return LEP_ASSERTION_FAILURE;
-            const lephuff::HuffDecImage im = lephuff::sequential_scan_image(sc);
-            lep_huffdec_image out;
-            static_assert(sizeof out == sizeof im, "C ABI mirrors");
-            memcpy(&out, &im, sizeof out);
-            ((simt && lephuff::sequential_scan_for_lanes(im)) ? many : one).push_back(out);
-        }
-        if (!many.empty() || !one.empty()) {
-            if (!many.empty()) { if (int rc = lep_gpu_huffman_decode_simt_device(g, many.data(), (int)many.size(), d_rows, st)) return rc; }
-            if (!one.empty()) { if (int rc = lep_gpu_huffman_decode_device(g, one.data(), (int)one.size(), d_rows, st)) return rc; }
-            for (int i = 0; i < nscan; ++i) if (!lephuff::progdec_is_sequential(reinterpret_cast<const lephuff::ProgDecScan&>(scans[i]))) progressive_only.push_back(scans[i]);
-            if (progressive_only.empty()) return 0;
-            scans = progressive_only.data(); nscan = (int)progressive_only.size();
-        }
-    }
-    // Scans of the new form for restart intervals (lep_huffprogdec_rst.h; the caller has put the marker positions behind their slots): a file
-    // with at least one of them goes level by level as a whole, every level of it many wavefronts per scan -- none of its scans waits on a
-    // progress word.  Files without such scans keep the launches below exactly as they were.
-    for (int i = 0; i < nscan; ++i) if (scans[i].level < 0 || scans[i].level > 63) return LEP_ASSERTION_FAILURE;
-    std::vector<lep_huffprogdec_scan> others, by_level;
-    if (g->huffprogdec_rst) {
-        std::vector<const void*> frames;
-        for (int i = 0; i < nscan; ++i)
-            if (lephuff::prog_rst_takes(reinterpret_cast<const lephuff::ProgDecScan&>(scans[i]))) frames.push_back((const void*)scans[i].t.blocks[0]);
-        if (!frames.empty()) {
-            std::sort(frames.begin(), frames.end());
-            for (int i = 0; i < nscan; ++i)
-                (std::binary_search(frames.begin(), frames.end(), (const void*)scans[i].t.blocks[0]) ? by_level : others).push_back(scans[i]);
-        }
-    }
-    if (by_level.empty()) return progdec_launch_scans(g, scans, nscan, d_rows, st);
-    if (!others.empty()) { if (int rc = progdec_launch_scans(g, others.data(), (int)others.size(), d_rows, st)) return rc; }
-    return progdec_launch_by_level(g, by_level, d_rows, st, others.empty());
+    lephuff::ProgDecOptions o;
+    o.lanes = !(getenv("LEP_HUFFDEC_SIMT") && atoi(getenv("LEP_HUFFDEC_SIMT")) == 0);
+    o.win = g->huffprogdec_win != 0; o.rst = g->huffprogdec_rst != 0; o.piece_floor = g->huffprogdec_rst_floor;
+    o.pipeline = g->huffprog_pipeline != 0; o.pipeline_max = g->huffprog_pipeline_max; o.split = g->huffprog_split != 0;
+    lephuff::ProgDecPlan plan;
+    if (lephuff::prog_dec_plan(reinterpret_cast<const lephuff::ProgDecScan*>(scans), nscan, o, &plan)) return LEP_ASSERTION_FAILURE;
+    static_assert(sizeof(lep_huffdec_image) == sizeof(lephuff::HuffDecImage), "C ABI mirrors");
+    const auto &many = plan.seq_lanes, &one = plan.seq_single;
+    if (!many.empty()) { if (int rc = lep_gpu_huffman_decode_simt_device(g, reinterpret_cast<const lep_huffdec_image*>(many.data()), (int)many.size(), d_rows, st)) return rc; }
+    if (!one.empty()) { if (int rc = lep_gpu_huffman_decode_device(g, reinterpret_cast<const lep_huffdec_image*>(one.data()), (int)one.size(), d_rows, st)) return rc; }
+    if (!plan.b.sorted.empty()) { if (int rc = progdec_launch_scans(g, plan.b, d_rows, st)) return rc; }
+    if (plan.c.plain.empty() && plan.c.rst.empty()) return 0;
+    return progdec_launch_by_level(g, plan.c, d_rows, st, plan.b.sorted.empty());
 }
 
 // the scans of files that have a scan of lep_huffprogdec_rst.h's: dependency level after dependency level on the stream -- the pieces of
 // the scans of that form, one launch of the window form's level-by-level kernel for the others -- and the reduce step behind the last
-static int progdec_launch_by_level(lep_gpu* g, const std::vector<lep_huffprogdec_scan>& scans, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here) {
-    std::vector<lep_huffprogdec_scan> plain, rst;
-    std::vector<lephuff::ProgRstScan> plans;
-    std::vector<int> pcut, rcut;
-    uint32_t pieces = 0;
-    bool any_win = false;
-    for (int lv = 0; lv < 64; ++lv) {
-        pcut.push_back((int)plain.size()); rcut.push_back((int)rst.size());
-        for (const lep_huffprogdec_scan& in : scans) {
-            if (in.level != lv) continue;
-            lep_huffprogdec_scan sc = in;
-            const lephuff::ProgDecScan& d = reinterpret_cast<const lephuff::ProgDecScan&>(sc);
-            if (lephuff::prog_rst_takes(d)) {
-                const lephuff::ProgRstScan pl = lephuff::prog_rst_plan(d, g->huffprogdec_rst_floor, pieces);
-                if (pl.npieces > 0x7fffffffu - pieces) return LEP_ASSERTION_FAILURE;
-                pieces += pl.npieces;
-                sc.pad = lephuff::kProgDecRst;
-                rst.push_back(sc); plans.push_back(pl);
-            } else {
-                const bool w = g->huffprogdec_win && lephuff::prog_win_takes(d);
-                sc.pad = w ? lephuff::kProgDecWin : 0;
-                any_win = any_win || w;
-                plain.push_back(sc);
-            }
-        }
-    }
-    pcut.push_back((int)plain.size()); rcut.push_back((int)rst.size());
+static int progdec_launch_by_level(lep_gpu* g, const lephuff::ProgDecPlan::Pieces& c, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here) {
     lepbuf::Layout L;
-    L.add<lep_huffprogdec_scan>(plain.size());
-    const size_t o_rst = L.add<lep_huffprogdec_scan>(rst.size()), o_plan = L.add<lephuff::ProgRstScan>(plans.size()), o_out = L.add<lephuff::ProgRstOut>((size_t)pieces);
+    L.add<lep_huffprogdec_scan>(c.plain.size());
+    const size_t o_rst = L.add<lep_huffprogdec_scan>(c.rst.size()), o_plan = L.add<lephuff::ProgRstScan>(c.plans.size()), o_out = L.add<lephuff::ProgRstOut>((size_t)c.pieces);
     if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGRST], L.padded())) return rc;
     char* base = g->ws[lep_gpu::W_HUFFPROGRST].at<char>(0);
-    if (!plain.empty()) HIPCHK(g, hipMemcpyAsync(base, plain.data(), plain.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_rst, rst.data(), rst.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_plan, plans.data(), plans.size() * sizeof(lephuff::ProgRstScan), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipStreamSynchronize(st));   // (the vectors above are the copies' sources)
+    if (!c.plain.empty()) HIPCHK(g, hipMemcpyAsync(base, c.plain.data(), c.plain.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(base + o_rst, c.rst.data(), c.rst.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(base + o_plan, c.plans.data(), c.plans.size() * sizeof(lephuff::ProgRstScan), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipStreamSynchronize(st));   // (the plan's vectors are the copies' sources)
     if (time_from_here) HIPCHK(g, hipEventRecord(g->ev0, st));
     const lephuff::ProgDecScan* d_plain = (const lephuff::ProgDecScan*)base;
     const lephuff::ProgDecScan* d_rst = (const lephuff::ProgDecScan*)(base + o_rst);
     const lephuff::ProgRstScan* d_plan = (const lephuff::ProgRstScan*)(base + o_plan);
     lephuff::ProgRstOut* d_out = (lephuff::ProgRstOut*)(base + o_out);
     for (int lv = 0; lv < 64; ++lv) {
-        const int np = pcut[lv + 1] - pcut[lv], nr = rcut[lv + 1] - rcut[lv];
+        const int np = c.pcut[lv + 1] - c.pcut[lv], nr = c.rcut[lv + 1] - c.rcut[lv];
         if (np > 0)
-            hipLaunchKernelGGL(any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(np), dim3(64), 0, st, d_plain + pcut[lv], (lephuff::HuffDecRow*)d_rows);
-        if (nr > 0) {
-            const uint32_t n = (rcut[lv + 1] < (int)plans.size() ? plans[(size_t)rcut[lv + 1]].piece0 : pieces) - plans[(size_t)rcut[lv]].piece0;
-            hipLaunchKernelGGL(lep_huffprogdec_rst_kernel, dim3(n), dim3(64), 0, st, d_rst + rcut[lv], d_plan + rcut[lv], nr, d_out, (lephuff::HuffDecRow*)d_rows);
-        }
+            hipLaunchKernelGGL(c.any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(np), dim3(64), 0, st, d_plain + c.pcut[lv], (lephuff::HuffDecRow*)d_rows);
+        if (nr > 0)
+            hipLaunchKernelGGL(lep_huffprogdec_rst_kernel, dim3(c.piece_cut(lv + 1) - c.piece_cut(lv)), dim3(64), 0, st, d_rst + c.rcut[lv], d_plan + c.rcut[lv], nr, d_out, (lephuff::HuffDecRow*)d_rows);
     }
-    hipLaunchKernelGGL(lep_huffprogdec_rst_reduce_kernel, dim3((unsigned)rst.size()), dim3(64), 0, st, d_rst, d_plan, d_out, (lephuff::HuffDecRow*)d_rows);
+    hipLaunchKernelGGL(lep_huffprogdec_rst_reduce_kernel, dim3((unsigned)c.rst.size()), dim3(64), 0, st, d_rst, d_plan, d_out, (lephuff::HuffDecRow*)d_rows);
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
@@ -1309,77 +1246,41 @@ static int progdec_launch_by_level(lep_gpu* g, const std::vector<lep_huffprogdec
     return 0;
 }
 
-// progressive scans without that form: all levels as ONE pipelined launch, or level after level
-static int progdec_launch_scans(lep_gpu* g, const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* d_rows, hipStream_t st) {
-    // scans ordered by dependency level (stable): one launch per level, stream order is the dependency
-    int maxlevel = 0;
-    for (int i = 0; i < nscan; ++i) { if (scans[i].level < 0 || scans[i].level > 63) return LEP_ASSERTION_FAILURE; maxlevel = std::max(maxlevel, (int)scans[i].level); }
-    std::vector<lep_huffprogdec_scan> sorted;
-    sorted.reserve((size_t)nscan);
-    std::vector<int> order;
-    order.reserve((size_t)nscan);
-    // (LEP_HUFFPROG_SPLIT=1, a measurement aid: inside a level the scans of one KIND -- DC / AC, first stage / refinement, component, band --
-    // stand together and get a launch of their own, so that a kernel trace shows what each kind of scan takes)
-    auto kind = [](const lep_huffprogdec_scan& s) { return (s.to == 0 ? 0 : 1) * 100000 + (s.sah ? 1 : 0) * 10000 + (s.cmpc > 1 ? 9 : s.cmp[0]) * 1000 + s.from * 10 + (s.to > 9 ? 9 : s.to); };
-    std::vector<int> cut;   // launch boundaries inside `sorted`
-    for (int lv = 0; lv <= maxlevel; ++lv) {
-        std::vector<int> idx;
-        for (int i = 0; i < nscan; ++i) if (scans[i].level == lv) idx.push_back(i);
-        if (g->huffprog_split) std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return kind(scans[a]) < kind(scans[b]); });
-        for (size_t q = 0; q < idx.size(); ++q) {
-            if (q == 0 || (g->huffprog_split && kind(scans[idx[q]]) != kind(scans[idx[q - 1]]))) cut.push_back((int)sorted.size());
-            sorted.push_back(scans[idx[q]]); order.push_back(idx[q]);
-        }
-    }
-    cut.push_back((int)sorted.size());
-    // Small launches wait for the chain of a file's dependent scans, not for throughput: all levels go out as ONE launch in which
-    // a scan follows the scans in front of it MCU row by MCU row.  (Beyond what is resident at once the levels are launched one
-    // after the other as before: the chip is full either way.)
-    std::vector<lephuff::ProgDeps> deps;
-    bool pipelined = g->huffprog_pipeline && maxlevel > 0 && nscan <= g->huffprog_pipeline_max;
-    if (pipelined) {
-        deps.resize((size_t)nscan);
-        pipelined = lephuff::prog_scan_deps(reinterpret_cast<const lephuff::ProgDecScan*>(sorted.data()), order.data(), nscan, deps.data());
-    }
+// progressive scans of files without that form: all levels as ONE pipelined launch, or level after level (stream order is the dependency)
+static int progdec_launch_scans(lep_gpu* g, const lephuff::ProgDecPlan::Levels& b, lep_huffdec_row* d_rows, hipStream_t st) {
+    const int nscan = (int)b.sorted.size();
     lepbuf::Layout L;
     L.add<lep_huffprogdec_scan>((size_t)nscan);
     const size_t o_deps = L.add<lephuff::ProgDeps>((size_t)nscan), o_prog = L.add<uint32_t>((size_t)nscan + 1);   // (+ the ticket counter behind the progress words)
     Workspace& progdec = g->ws[lep_gpu::W_HUFFPROGDEC];
     if (int rc = ensure(g, progdec, L.bytes())) return rc;
-    // which scans the window of speculative codes decodes (lep_huffprogdec_win.h); lep_huffprogdec.h's uniform vector code keeps the others
-    bool any_win = false;
-    for (lep_huffprogdec_scan& sc : sorted) {
-        const bool w = g->huffprogdec_win && lephuff::prog_win_takes(reinterpret_cast<const lephuff::ProgDecScan&>(sc));
-        sc.pad = w ? lephuff::kProgDecWin : 0;
-        any_win = any_win || w;
-    }
-    HIPCHK(g, hipMemcpyAsync(progdec, sorted.data(), (size_t)nscan * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
-    if (pipelined) {
-        HIPCHK(g, hipMemcpyAsync(progdec.at<char>(o_deps), deps.data(), (size_t)nscan * sizeof(lephuff::ProgDeps), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(progdec, b.sorted.data(), (size_t)nscan * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
+    if (b.pipelined) {
+        HIPCHK(g, hipMemcpyAsync(progdec.at<char>(o_deps), b.deps.data(), (size_t)nscan * sizeof(lephuff::ProgDeps), hipMemcpyHostToDevice, st));
         HIPCHK(g, hipMemsetAsync(progdec.at<char>(o_prog), 0, (size_t)nscan * 4 + 4, st));
     }
     HIPCHK(g, hipStreamSynchronize(st));
     HIPCHK(g, hipEventRecord(g->ev0, st));
-    if (pipelined) {
-        hipLaunchKernelGGL(any_win ? lep_huffprogdec_win_pipelined_kernel : lep_huffman_progressive_pipelined_kernel, dim3(nscan), dim3(64), 0, st,
+    if (b.pipelined) {
+        hipLaunchKernelGGL(b.any_win ? lep_huffprogdec_win_pipelined_kernel : lep_huffman_progressive_pipelined_kernel, dim3(nscan), dim3(64), 0, st,
                            progdec.at<const lephuff::ProgDecScan>(0), (lephuff::HuffDecRow*)d_rows,
                            progdec.at<const lephuff::ProgDeps>(o_deps), progdec.at<uint32_t>(o_prog), progdec.at<uint32_t>(o_prog) + nscan);
         HIPCHK(g, hipGetLastError());
         HIPCHK(g, hipEventRecord(g->ev1, st));
         g->timed = true;
-        g->last_kernel = any_win ? "lep_huffprogdec_win_pipelined_kernel" : "lep_huffman_progressive_pipelined_kernel";
+        g->last_kernel = b.any_win ? "lep_huffprogdec_win_pipelined_kernel" : "lep_huffman_progressive_pipelined_kernel";
         return 0;
     }
-    for (size_t c = 0; c + 1 < cut.size(); ++c) {   // one launch per level (LEP_HUFFPROG_SPLIT: per level and kind of scan)
-        const int n = cut[c + 1] - cut[c];
+    for (size_t q = 0; q + 1 < b.cut.size(); ++q) {   // one launch per level (LEP_HUFFPROG_SPLIT: per level and kind of scan)
+        const int n = b.cut[q + 1] - b.cut[q];
         if (n <= 0) continue;
-        hipLaunchKernelGGL(any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(n), dim3(64), 0, st,
-                           progdec.at<const lephuff::ProgDecScan>(0) + cut[c], (lephuff::HuffDecRow*)d_rows);
+        hipLaunchKernelGGL(b.any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(n), dim3(64), 0, st,
+                           progdec.at<const lephuff::ProgDecScan>(0) + b.cut[q], (lephuff::HuffDecRow*)d_rows);
     }
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
-    g->last_kernel = any_win ? "lep_huffprogdec_win_kernel" : "lep_huffman_progressive_decode_kernel";
+    g->last_kernel = b.any_win ? "lep_huffprogdec_win_kernel" : "lep_huffman_progressive_decode_kernel";
     return 0;
 }
 
@@ -1507,53 +1408,23 @@ int lep_gpu_huffman_decode_device(lep_gpu* g, const lep_huffdec_image* images, i
 int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* images, int nimg, lep_huffdec_row* d_rows, void* hip_stream) {
     if (!g) return LEP_GPU_ERROR;
     if (nimg <= 0) return 0;
-    uint64_t bits = 0;
-    // (restart intervals: only with the markers' positions behind the scan bytes -- LEP_HUFFDEC_RST_TABLE; the others are the single-wave kernel's)
-    for (int i = 0; i < nimg; ++i) { if (images[i].rsti && !(images[i].flags & LEP_HUFFDEC_RST_TABLE)) return LEP_ASSERTION_FAILURE; bits += (uint64_t)images[i].scan_len * 8u; }
+    // subsequences, wavefronts and side array: lep_huffdec_simt.h's plan -- as many lanes as fill the chip a few times over (64 x the
+    // wavefronts it holds, twice) unless LEP_HUFFDEC_SIMT_BITS says how long a subsequence is
+    lephuff::SimtDecPlan plan;
+    if (lephuff::simt_dec_plan(reinterpret_cast<const lephuff::HuffDecImage*>(images), nimg, g->simt_sub_bits, (uint64_t)64 * 8192 * 2, &plan)) return LEP_ASSERTION_FAILURE;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    // subsequences: as many as fill the chip a few times over (lanes = 64 x the wavefronts it holds, twice), but none shorter than a scan
-    // needs to fall into step
-    const uint32_t L = g->simt_sub_bits ? (uint32_t)((g->simt_sub_bits + 31) & ~31) : lephuff::simt_sub_bits(bits, (uint64_t)64 * 8192 * 2);
-    std::vector<lephuff::SimtImage> si((size_t)nimg);
-    std::vector<lephuff::SimtWave> waves, wide_waves;
-    size_t nsub_all = 0, nslots = 0;                        // (nslots: entries of the side array, which only wide blind images have)
-    for (int i = 0; i < nimg; ++i) {
-        memset(&si[(size_t)i], 0, sizeof(lephuff::SimtImage));
-        const uint64_t b = (uint64_t)images[i].scan_len * 8u;
-        // a subsequence has to hold enough blocks to fall into step in: 64 of this image's average block at least (a 4:4:4 file of
-        // noise at quality 98 codes 1.5 kbit per block and does not settle in 16 kbit)
-        uint64_t nblocks = 0;
-        for (int ci = 0; ci < images[i].ncomp && ci < 4; ++ci) { const int cmp = images[i].scan_cmp[ci] & 3; nblocks += (uint64_t)images[i].hs[cmp] * images[i].vs[cmp]; }
-        nblocks *= (uint64_t)std::max(images[i].mcuc, 1);
-        const uint32_t Li = g->simt_sub_bits ? L : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(L, (64 * b / std::max<uint64_t>(nblocks, 1) + 31) & ~(uint64_t)31), 1u << 24);
-        uint32_t n = (uint32_t)std::max<uint64_t>(1, (b + Li - 1) / Li);
-        if (images[i].flags & LEP_HUFFDEC_RST_TABLE) {        // lane = restart interval; the pad patterns' and / or / count start from 0xff / 0 / 0
-            if (images[i].rsti <= 0 || images[i].mcuc <= 0) return LEP_ASSERTION_FAILURE;
-            n = (uint32_t)((images[i].mcuc - 1) / images[i].rsti) + 1u;
-            si[(size_t)i].changed[0] = 0xff;
-        }
-        si[(size_t)i].first = (uint32_t)nsub_all; si[(size_t)i].nsub = n; si[(size_t)i].sub_bits = Li;
-        // (wide blind images: their wavefronts stand behind all others', in settle launches of their own -- those ask for the lanes' slot
-        // columns in LDS and run six wavefronts to the SIMD, the launches of everything else keep their eight)
-        const bool wide = lephuff::simt_blind_wide(reinterpret_cast<const lephuff::HuffDecImage*>(&images[i]));
-        for (uint32_t f = 0; f < n; f += 64) (wide ? wide_waves : waves).push_back(lephuff::SimtWave{(uint32_t)i, f});
-        nsub_all += n;
-        if (wide) { si[(size_t)i].slots = (uint32_t)nslots; nslots += n; }
-    }
-    if (nsub_all > 0x7fffffffu) return LEP_ASSERTION_FAILURE;
-    const int nw_plain = (int)waves.size(), nw_wide = (int)wide_waves.size();
-    waves.insert(waves.end(), wide_waves.begin(), wide_waves.end());
+    const size_t nsub_all = plan.nsub_all;
     lepbuf::Layout P;
-    const size_t o_si = P.add<lephuff::SimtImage>(si.size()), o_wv = P.add<lephuff::SimtWave>(waves.size()), o_s0 = P.add<lephuff::SimtSub>(nsub_all),
-                 o_s1 = P.add<lephuff::SimtSub>(nsub_all), o_pl = P.add<lephuff::SimtPlace>(nsub_all), o_sl = P.add<lephuff::SimtSlots>(nslots);
+    const size_t o_si = P.add<lephuff::SimtImage>(plan.si.size()), o_wv = P.add<lephuff::SimtWave>(plan.waves.size()), o_s0 = P.add<lephuff::SimtSub>(nsub_all),
+                 o_s1 = P.add<lephuff::SimtSub>(nsub_all), o_pl = P.add<lephuff::SimtPlace>(nsub_all), o_sl = P.add<lephuff::SimtSlots>(plan.nslots);
     Workspace& huffdec = g->ws[lep_gpu::W_HUFFDEC];
     if (int rc = ensure(g, huffdec, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
     if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPAR], P.padded())) return rc;
     char* base = g->ws[lep_gpu::W_HUFFPAR].at<char>(0);
     HIPCHK(g, hipMemcpyAsync(huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_si, si.data(), si.size() * sizeof(lephuff::SimtImage), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_wv, waves.data(), waves.size() * sizeof(lephuff::SimtWave), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(base + o_si, plan.si.data(), plan.si.size() * sizeof(lephuff::SimtImage), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(base + o_wv, plan.waves.data(), plan.waves.size() * sizeof(lephuff::SimtWave), hipMemcpyHostToDevice, st));
     HIPCHK(g, hipStreamSynchronize(st));   // the caller's array (and ours) may go away
     const lephuff::HuffDecImage* di = (const lephuff::HuffDecImage*)huffdec.p;
     lephuff::SimtImage* dsi = (lephuff::SimtImage*)(base + o_si);
@@ -1561,7 +1432,7 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
     lephuff::SimtSub* buf[2] = {(lephuff::SimtSub*)(base + o_s0), (lephuff::SimtSub*)(base + o_s1)};
     lephuff::SimtPlace* dpl = (lephuff::SimtPlace*)(base + o_pl);
     lephuff::SimtSlots* dsl = (lephuff::SimtSlots*)(base + o_sl);
-    const int nw = (int)waves.size();
+    const int nw = (int)plan.waves.size(), nw_plain = plan.nw_plain, nw_wide = nw - nw_plain;
     HIPCHK(g, hipEventRecord(g->ev0, st));
     for (int k = 0; k <= lephuff::kSimtSettle; ++k) {       // pass A (k = 0: nothing is read), then the settle passes
         const lephuff::SimtSub* in = buf[(k + 1) & 1];
@@ -1576,9 +1447,9 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
-    // (lanes of the launch and the subsequence length it was cut with -- LEP_HUFFDEC_SIMT_BITS or the rule above: tests that force short
+    // (lanes of the launch and the subsequence length it was cut with -- LEP_HUFFDEC_SIMT_BITS or the plan's rule: tests that force short
     // subsequences read here that they got them)
-    snprintf(g->simt_name, sizeof g->simt_name, "lep_huffman_simt_{settle,place,write}_kernel (%zu lanes, %u bits)", nsub_all, (unsigned)L);
+    snprintf(g->simt_name, sizeof g->simt_name, "lep_huffman_simt_{settle,place,write}_kernel (%zu lanes, %u bits)", nsub_all, (unsigned)plan.L);
     g->last_kernel = g->simt_name;
     return 0;
 }

@@ -24,8 +24,14 @@
 // the scan and pass C counts its blocks down.  Files with restart intervals keep the single-wave kernel.
 #pragma once
 #include "lep_huffdec.h"
+#include "lep_scan_routes.h"
+#include <algorithm>
+#include <cstring>
+#include <vector>
 
 namespace lephuff {
+
+static_assert(kHuffDecRstTable == 2, "lep_scan_routes.h reads the flag by its value");
 
 #if LEP_ON_GPU
 #define LEP_SIMT_BOTH __host__ __device__ __forceinline__   // (the launch code sizes the side array with the same functions)
@@ -513,10 +519,22 @@ WDEV void simt_write_intervals(const HuffDecImage* img, SimtShared* sh, SimtTile
     }
 }
 // what the finish pass makes of a restart-table image's pad patterns: the status bit for patterns that differ, the pad byte of the final record
-WDEV int simt_intervals_pad(const SimtImage* si, int* status_bits) {
+LEP_SIMT_BOTH int simt_intervals_pad(const SimtImage* si, int* status_bits) {
     if (si->changed[2] == 0) return 255;                                    // never determined
     if (si->changed[0] != si->changed[1]) { *status_bits |= 1; return 255; }
     return si->changed[1] & 255;
+}
+// the finish pass, one image: the final record's pad byte and the status the passes collected
+LEP_SIMT_BOTH void simt_finish(const HuffDecImage* img, const SimtImage* si, HuffDecRow* rows_arena) {
+    HuffDecRow* last = rows_arena + img->rows_off + img->mcuv;
+    int status = si->status & 0x3fffff;
+    if (last->aux == kHuffDecRowUnwritten) { status |= 2; last->aux = 255; }   // no lane of the write pass got to the final record: irregular
+    if (img->flags & kHuffDecRstTable) {                    // restart intervals: the pad byte is what all intervals agreed on
+        const int pad = simt_intervals_pad(si, &status);
+        last->aux = pad | (status << 8);
+        return;
+    }
+    last->aux = (last->aux & (255 | kHuffDecRowTruncated)) | (status << 8);
 }
 
 // pass C; the image's status collects what the lanes find
@@ -640,6 +658,57 @@ inline uint32_t simt_sub_bits(uint64_t launch_bits, uint64_t target_lanes) {
     if (L < kSimtMinBits) L = kSimtMinBits;
     if (L > (1u << 20)) L = 1u << 20;
     return (uint32_t)L;
+}
+
+// The launch plan: how a launch's images are cut into subsequences, and which wavefront decodes which 64 of them.  forced_bits: the
+// subsequence length for every image (rounded up to 32 bits), 0 = the rule -- as many subsequences as fill target_lanes lanes
+// (simt_sub_bits), but for every image 64 of ITS average block at least: a subsequence has to hold enough blocks to fall into step in
+// (a 4:4:4 file of noise at quality 98 codes 1.5 kbit per block and does not settle in 16 kbit).  An image flagged kHuffDecRstTable is
+// cut at its markers instead, lane = restart interval; its pad patterns' and / or / count (SimtImage::changed) start from 0xff / 0 / 0.
+// waves: the wavefronts of wide blind images stand behind all others' (nw_plain of them), for settle launches of their own -- those ask
+// for the lanes' slot columns in LDS and run six wavefronts to the SIMD, the launches of everything else keep their eight; only those
+// images have entries in the side array (nslots).  Non-zero: an image the lane decoder does not take (simt_dec_takes), a flagged one
+// without an interval or without MCUs, more subsequences than an int32 counts.  The launch and tests/emu call the same.
+struct SimtDecPlan {
+    std::vector<SimtImage> si;
+    std::vector<SimtWave> waves;
+    int nw_plain = 0;
+    size_t nsub_all = 0, nslots = 0;
+    uint32_t L = 0;             // the launch's subsequence length (an image's own may be longer: SimtImage::sub_bits)
+};
+inline int simt_dec_plan(const HuffDecImage* images, int nimg, uint32_t forced_bits, uint64_t target_lanes, SimtDecPlan* out) {
+    *out = SimtDecPlan();
+    uint64_t bits = 0;
+    for (int i = 0; i < nimg; ++i) { if (!simt_dec_takes(images[i])) return 1; bits += (uint64_t)images[i].scan_len * 8u; }
+    out->L = forced_bits ? (uint32_t)((forced_bits + 31) & ~31) : simt_sub_bits(bits, target_lanes);
+    out->si.resize((size_t)nimg);
+    for (int i = 0; i < nimg; ++i) {
+        const HuffDecImage& im = images[i];
+        SimtImage& si = out->si[(size_t)i];
+        memset(&si, 0, sizeof si);
+        const uint64_t b = (uint64_t)im.scan_len * 8u;
+        uint64_t nblocks = 0;
+        for (int ci = 0; ci < im.ncomp && ci < 4; ++ci) { const int cmp = im.scan_cmp[ci] & 3; nblocks += (uint64_t)im.hs[cmp] * im.vs[cmp]; }
+        nblocks *= (uint64_t)std::max(im.mcuc, 1);
+        si.sub_bits = forced_bits ? out->L : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(out->L, (64 * b / std::max<uint64_t>(nblocks, 1) + 31) & ~(uint64_t)31), 1u << 24);
+        si.nsub = (uint32_t)std::max<uint64_t>(1, (b + si.sub_bits - 1) / si.sub_bits);
+        if (im.flags & kHuffDecRstTable) {
+            if (im.rsti <= 0 || im.mcuc <= 0) return 1;
+            si.nsub = (uint32_t)((im.mcuc - 1) / im.rsti) + 1u;
+            si.changed[0] = 0xff;
+        }
+        si.first = (uint32_t)out->nsub_all;
+        out->nsub_all += si.nsub;
+        if (simt_blind_wide(&im)) { si.slots = (uint32_t)out->nslots; out->nslots += si.nsub; }
+    }
+    if (out->nsub_all > 0x7fffffffu) return 1;
+    for (int wide = 0; wide < 2; ++wide) {
+        for (int i = 0; i < nimg; ++i)
+            if (simt_blind_wide(&images[i]) == (wide != 0))
+                for (uint32_t f = 0; f < out->si[(size_t)i].nsub; f += 64) out->waves.push_back(SimtWave{(uint32_t)i, f});
+        if (!wide) out->nw_plain = (int)out->waves.size();
+    }
+    return 0;
 }
 
 }  // namespace lephuff

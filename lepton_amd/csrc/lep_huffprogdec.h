@@ -17,6 +17,7 @@
 // SPMD layer of lep_wave.h: tests/emu runs it on the CPU against the host parser (frame, hand-off rows, pad bit).
 #pragma once
 #include "lep_huffdec.h"
+#include "lep_scan_routes.h"
 #include <algorithm>
 #include <vector>
 
@@ -58,8 +59,8 @@ inline HuffDecImage sequential_scan_image(const ProgDecScan& s) {
 }
 
 // Whether the lane-per-subsequence decoder (lep_huffdec_simt.h) is the one to send such a scan to: restart intervals come without the
-// table of marker positions here, and those go to the single-wave kernel.
-inline bool sequential_scan_for_lanes(const HuffDecImage& im) { return im.rsti == 0; }
+// table of marker positions here, and those go to the single-wave kernel -- the one rule of lep_scan_routes.h.
+inline bool sequential_scan_for_lanes(const HuffDecImage& im) { return simt_dec_takes(im); }
 
 // Pipelining between the scans of one image (one launch for all dependency levels).  A 4K file of libjpeg's default script is
 // ten scans in three levels, and the longest scan of every level is a luma scan (bytes: 276 k first stage, 348 k and 654 k

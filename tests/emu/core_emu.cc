@@ -235,125 +235,51 @@ extern "C" int emu_huffman_decode_image(const lep_huffdec_image* img, lep_huffde
     return 0;
 }
 
-// progressive scan decoder (lep_huffprogdec.h): the scans of one image, level by level, one emulated wavefront after the other
-#include "../../lepton_amd/csrc/lep_huffprogdec.h"
-// (a scan of a SEQUENTIAL frame coded in several scans goes where the launch code sends it: to the sequential scan decoders, as an image of
-// its own -- lep_huffprogdec.h sequential_scan_image, lep_gpu.hip lep_gpu_huffman_progressive_decode_device; defined at the end of the file)
-static void emu_sequential_scan_decode(const lephuff::ProgDecScan& sc, lephuff::HuffDecRow* rows, bool lanes);
+// The scan decoders (lep_huffprogdec.h, _win.h, _rst.h; lep_huffdec_simt.h) as the launch code runs them: scan_dec_driver.h steps the passes
+// over the launch code's own plans.  The entry points below say which knobs are on.
+#include "scan_dec_driver.h"
+static lephuff::ProgDecOptions emu_prog_dec_options(bool lanes, bool win, bool pipeline) {
+    lephuff::ProgDecOptions o;
+    o.lanes = lanes; o.win = win; o.rst = false; o.pipeline = pipeline; o.pipeline_max = 0x7fffffff; o.split = false;
+    return o;
+}
+// progressive scans on lep_huffprogdec.h: the scans of one image, level by level (a scan of a SEQUENTIAL frame coded in several scans goes where
+// the launch code sends it: to the sequential scan decoders, as an image of its own -- here the single-wave kernel)
 extern "C" int emu_huffman_progressive_decode(const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* rows) {
-    static lephuff::HuffDecShared sh;
-    for (int lv = 0; lv < 64; ++lv)
-        for (int i = 0; i < nscan; ++i)
-            if (scans[i].level == lv && lephuff::progdec_is_sequential(*reinterpret_cast<const lephuff::ProgDecScan*>(scans + i)))
-                emu_sequential_scan_decode(*reinterpret_cast<const lephuff::ProgDecScan*>(scans + i), reinterpret_cast<lephuff::HuffDecRow*>(rows), false);
-            else
-            if (scans[i].level == lv) { lephuff::ProgDecWave w; w.run_scan(reinterpret_cast<const lephuff::ProgDecScan*>(scans + i), &sh, reinterpret_cast<lephuff::HuffDecRow*>(rows)); }
-    return 0;
+    return emu_prog_dec_drive(reinterpret_cast<const lephuff::ProgDecScan*>(scans), nscan, emu_prog_dec_options(false, false, false), reinterpret_cast<lephuff::HuffDecRow*>(rows));
 }
 
 // ... as ONE pipelined launch (all levels; a scan follows the scans of its file in front of it MCU row by MCU row): the launch
-// order, the dependencies the host works out (returned through deps_out[nscan][4], indices into the caller's array) and the
-// waiting / publishing code, run one scan after the other in launch order.  waits_out: how often a scan found the scans in front
-// of it not far enough (0 here by construction; the code path that polls is the GPU's).
+// order, the dependencies the plan works out (returned through deps_out[nscan][4], indices into the caller's array; none where the plan
+// declines to pipeline -- one level, a scan that follows more than four) and the waiting / publishing code, run one scan after the other
+// in launch order (a scan never finds the scans in front of it not far enough here; the code path that polls is the GPU's).
 extern "C" int emu_huffman_progressive_decode_pipelined(const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* rows, int32_t* deps_out) {
-    static lephuff::HuffDecShared sh;
-    std::vector<lephuff::ProgDecScan> sorted;
-    std::vector<int> order;
-    for (int lv = 0; lv < 64; ++lv)
-        for (int i = 0; i < nscan; ++i)
-            if (scans[i].level == lv) { sorted.push_back(*reinterpret_cast<const lephuff::ProgDecScan*>(scans + i)); order.push_back(i); }
-    if ((int)sorted.size() != nscan) return -1;
-    std::vector<lephuff::ProgDeps> deps((size_t)nscan);
-    if (!lephuff::prog_scan_deps(sorted.data(), order.data(), nscan, deps.data())) return -2;
-    std::vector<uint32_t> progress((size_t)nscan, 0u);
-    for (int k = 0; k < nscan; ++k) {
-        for (int d = 0; d < 4; ++d) {
-            const int j = deps[(size_t)k].dep[d];
-            if (j >= k) return -3;                                  // a scan may only follow scans in front of it in the launch
-            deps_out[order[(size_t)k] * 4 + d] = j < 0 ? -1 : order[(size_t)j];
-        }
-        if (lephuff::progdec_is_sequential(sorted[(size_t)k])) { emu_sequential_scan_decode(sorted[(size_t)k], reinterpret_cast<lephuff::HuffDecRow*>(rows), false); progress[(size_t)k] = 0x7fffffffu; continue; }
-        lephuff::ProgDecWave w;
-        w.run_scan<true>(&sorted[(size_t)k], &sh, reinterpret_cast<lephuff::HuffDecRow*>(rows), &deps[(size_t)k], progress.data(), k);
-        if (progress[(size_t)k] != 0x7fffffffu) return -4;          // every scan says when it is done, whatever happened to it
-    }
-    return 0;
+    return emu_prog_dec_drive(reinterpret_cast<const lephuff::ProgDecScan*>(scans), nscan, emu_prog_dec_options(false, false, true), reinterpret_cast<lephuff::HuffDecRow*>(rows), deps_out);
 }
-
-
 
 // ... with the window of speculative codes (lep_huffprogdec_win.h) for the scans that form takes: level by level (pipelined = 0) or
-// in the one launch's order with its waiting / publishing code (pipelined = 1).  taken: how many scans the window form decoded.
-#include "../../lepton_amd/csrc/lep_huffprogdec_win.h"
+// in the one launch's order with its waiting / publishing code (pipelined = 1); sequential frames' scans one lane per subsequence where
+// that decoder takes them.  taken: how many scans the window form decoded.
 extern "C" int emu_huffman_progressive_decode_win(const lep_huffprogdec_scan* scans, int nscan, lep_huffdec_row* rows, int pipelined, int32_t* taken) {
-    static lephuff::HuffDecShared sh;
-    static lephuff::ProgWinShared ws;
-    std::vector<lephuff::ProgDecScan> sorted;
-    std::vector<int> order;
-    for (int lv = 0; lv < 64; ++lv)
-        for (int i = 0; i < nscan; ++i)
-            if (scans[i].level == lv) { sorted.push_back(*reinterpret_cast<const lephuff::ProgDecScan*>(scans + i)); order.push_back(i); }
-    if ((int)sorted.size() != nscan) return -1;
-    std::vector<lephuff::ProgDeps> deps((size_t)nscan);
-    if (pipelined && !lephuff::prog_scan_deps(sorted.data(), order.data(), nscan, deps.data())) return -2;
-    std::vector<uint32_t> progress((size_t)nscan, 0u);
-    *taken = 0;
-    for (int k = 0; k < nscan; ++k) {
-        lephuff::HuffDecRow* r = reinterpret_cast<lephuff::HuffDecRow*>(rows);
-        if (lephuff::progdec_is_sequential(sorted[(size_t)k])) { emu_sequential_scan_decode(sorted[(size_t)k], r, true); progress[(size_t)k] = 0x7fffffffu; continue; }
-        const bool win = lephuff::prog_win_takes(sorted[(size_t)k]);
-        *taken += win;
-        if (win) {
-            lephuff::ProgWinWave w;
-            if (pipelined) w.run_scan_win<true>(&sorted[(size_t)k], &ws, r, &deps[(size_t)k], progress.data(), k);
-            else w.run_scan_win<false>(&sorted[(size_t)k], &ws, r);
-        } else {
-            lephuff::ProgDecWave w;
-            if (pipelined) w.run_scan<true>(&sorted[(size_t)k], &sh, r, &deps[(size_t)k], progress.data(), k);
-            else w.run_scan<false>(&sorted[(size_t)k], &sh, r);
-        }
-        if (pipelined && progress[(size_t)k] != 0x7fffffffu) return -4;
-    }
-    return 0;
+    return emu_prog_dec_drive(reinterpret_cast<const lephuff::ProgDecScan*>(scans), nscan, emu_prog_dec_options(true, true, pipelined != 0), reinterpret_cast<lephuff::HuffDecRow*>(rows), nullptr, taken);
 }
 
-// one lane per subsequence (lep_huffdec_simt.h): guess, settle passes, place, write -- every pass one wavefront after the other.
+// one lane per subsequence (lep_huffdec_simt.h): guess, settle passes, place, write, finish -- every pass one wavefront after the other.
 // settle_moved[k] (k = 0 .. kSimtSettle): whether pass k saw an end state move; nsub_out: subsequences the scan was cut into.
-#include "../../lepton_amd/csrc/lep_huffdec_simt.h"
-extern "C" int emu_huffman_decode_image_simt(const lep_huffdec_image* img, lep_huffdec_row* rows, uint32_t sub_bits, int32_t* settle_moved, uint32_t* nsub_out) {
-    static lephuff::SimtShared sh;
+// side_array = false: a caller that passes no side array of slot sums (tests/test_blind_wide_emulation.py says what happens then).
+static int emu_simt_decode_one(const lep_huffdec_image* img, lep_huffdec_row* rows, uint32_t sub_bits, int32_t* settle_moved, uint32_t* nsub_out, bool side_array) {
     lephuff::HuffDecImage im;
     memcpy(&im, img, sizeof im);
     im.rows_off = 0;
-    const uint32_t L = (sub_bits + 31u) & ~31u;
-    if (!L) return -1;
-    lephuff::SimtImage si;
-    memset(&si, 0, sizeof si);
-    si.first = 0; si.sub_bits = L;
-    si.nsub = (uint32_t)std::max<uint64_t>(1, ((uint64_t)im.scan_len * 8u + L - 1) / L);
-    if (im.flags & lephuff::kHuffDecRstTable) {   // lane = restart interval (lep_gpu_huffman_decode_simt_device)
-        if (im.rsti <= 0 || im.mcuc <= 0) return -1;
-        si.nsub = (uint32_t)((im.mcuc - 1) / im.rsti) + 1u;
-        si.changed[0] = 0xff;
-    }
-    std::vector<lephuff::SimtSub> buf[2] = {std::vector<lephuff::SimtSub>(si.nsub), std::vector<lephuff::SimtSub>(si.nsub)};
-    std::vector<lephuff::SimtPlace> place(si.nsub);
-    for (int k = 0; k <= lephuff::kSimtSettle; ++k)
-        for (uint32_t f = 0; f < si.nsub; f += 64) lephuff::simt_guess_or_settle(&im, &sh, &si, buf[(k + 1) & 1].data(), buf[k & 1].data(), f, k);
-    const lephuff::SimtSub* fin = buf[lephuff::kSimtSettle & 1].data();
-    lephuff::simt_place(&im, &si, fin, place.data(), lephuff::kSimtSettle, reinterpret_cast<lephuff::HuffDecRow*>(rows));
-    static lephuff::SimtTile tile;
-    for (uint32_t f = 0; f < si.nsub; f += 64) lephuff::simt_write(&im, &sh, &tile, &si, fin, place.data(), reinterpret_cast<lephuff::HuffDecRow*>(rows), f);
-    if (rows[im.mcuv].aux == lephuff::kHuffDecRowUnwritten) { si.status |= 2; rows[im.mcuv].aux = 255; }   // (lep_huffman_simt_finish_kernel)
-    if (im.flags & lephuff::kHuffDecRstTable) {
-        int status = si.status & 0x3fffff;
-        const int pad = lephuff::simt_intervals_pad(&si, &status);
-        rows[im.mcuv].aux = pad | (status << 8);
-    } else
-    rows[im.mcuv].aux = (rows[im.mcuv].aux & (255 | lephuff::kHuffDecRowTruncated)) | ((si.status & 0x3fffff) << 8);
-    if (settle_moved) for (int k = 0; k <= lephuff::kSimtSettle; ++k) settle_moved[k] = si.changed[k];
-    if (nsub_out) *nsub_out = si.nsub;
+    if (!((sub_bits + 31u) & ~31u)) return -1;
+    lephuff::SimtDecPlan plan;
+    if (int rc = emu_simt_dec_drive(&im, 1, sub_bits, side_array, reinterpret_cast<lephuff::HuffDecRow*>(rows), &plan)) return rc;
+    if (settle_moved) for (int k = 0; k <= lephuff::kSimtSettle; ++k) settle_moved[k] = plan.si[0].changed[k];
+    if (nsub_out) *nsub_out = plan.si[0].nsub;
     return 0;
+}
+extern "C" int emu_huffman_decode_image_simt(const lep_huffdec_image* img, lep_huffdec_row* rows, uint32_t sub_bits, int32_t* settle_moved, uint32_t* nsub_out) {
+    return emu_simt_decode_one(img, rows, sub_bits, settle_moved, nsub_out, false);
 }
 
 // split-phase encoder (lep_enc5.h): count -> plan -> emit -> fold (every chain) -> gather -> write, one segment, every pass
@@ -599,20 +525,4 @@ extern "C" int emu_prog_scan_deps(const lep_huffprogdec_scan* scans, const int* 
     const bool ok = lephuff::prog_scan_deps(reinterpret_cast<const lephuff::ProgDecScan*>(scans), order, n, deps.data());
     for (int i = 0; i < n; ++i) for (int d = 0; d < 4; ++d) deps_out[4 * i + d] = deps[(size_t)i].dep[d];
     return ok ? 1 : 0;
-}
-
-static void emu_sequential_scan_decode(const lephuff::ProgDecScan& sc, lephuff::HuffDecRow* rows, bool lanes) {
-    const lephuff::HuffDecImage im = lephuff::sequential_scan_image(sc);
-    lep_huffdec_row* at = reinterpret_cast<lep_huffdec_row*>(rows + im.rows_off);
-    if (lanes && lephuff::sequential_scan_for_lanes(im)) {
-        int32_t moved[lephuff::kSimtSettle + 1];
-        uint32_t nsub = 0;
-        // (subsequences as the launch code cuts them: 8192 bits, or 64 of the scan's average block if that is more)
-        uint64_t nblocks = 0;
-        for (int ci = 0; ci < im.ncomp && ci < 4; ++ci) { const int cmp = im.scan_cmp[ci] & 3; nblocks += (uint64_t)im.hs[cmp] * im.vs[cmp]; }
-        nblocks *= (uint64_t)std::max(im.mcuc, 1);
-        const uint64_t b = (uint64_t)im.scan_len * 8u;
-        const uint32_t sub_bits = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(8192, (64 * b / std::max<uint64_t>(nblocks, 1) + 31) & ~(uint64_t)31), 1u << 24);
-        emu_huffman_decode_image_simt(reinterpret_cast<const lep_huffdec_image*>(&im), at, sub_bits, moved, &nsub);
-    } else emu_huffman_decode_image(reinterpret_cast<const lep_huffdec_image*>(&im), at);
 }

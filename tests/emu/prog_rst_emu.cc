@@ -6,44 +6,17 @@
 #include <vector>
 #define LEP_DEV inline
 #include "../../lepton_amd/csrc/lep_derive.h"
-#include "../../lepton_amd/csrc/lep_huffprogdec_rst.h"
+#include "scan_dec_driver.h"
 
-// The scans of one file, level by level as the launch code runs a file that has a scan of this form: scans flagged
-// LEP_HUFFDEC_RST_TABLE (the caller has put the marker positions behind the slot) piece by piece and then the reduce step, the window
-// form where it takes the scan, lep_huffprogdec.h for the rest; scans of sequential frames go to the single-wave sequential kernel.
-static void run_levels(const lep_huffprogdec_scan* scans, int nscan, lephuff::HuffDecRow* rows, bool rst, uint32_t piece_floor, int32_t* taken, uint32_t* pieces) {
-    static lephuff::HuffDecShared sh;
-    static lephuff::ProgWinShared ws;
-    for (int lv = 0; lv < 64; ++lv)
-        for (int i = 0; i < nscan; ++i) {
-            const lephuff::ProgDecScan& sc = *reinterpret_cast<const lephuff::ProgDecScan*>(scans + i);
-            if (sc.level != lv) continue;
-            if (lephuff::progdec_is_sequential(sc)) {
-                const lephuff::HuffDecImage im = lephuff::sequential_scan_image(sc);
-                lephuff::HuffDecImage one = im;
-                one.rows_off = 0;
-                lephuff::HuffDecWave w;
-                w.run(&one, &sh, rows + im.rows_off);
-            } else if (rst && lephuff::prog_rst_takes(sc)) {
-                const lephuff::ProgRstScan plan = lephuff::prog_rst_plan(sc, piece_floor ? piece_floor : lephuff::kRstPieceFloor, 0);
-                std::vector<lephuff::ProgRstOut> outs(plan.npieces);
-                memset(outs.data(), 0xee, outs.size() * sizeof outs[0]);
-                for (uint32_t p = 0; p < plan.npieces; ++p) {
-                    const uint32_t first = p * plan.ipp, count = plan.nint - first < plan.ipp ? plan.nint - first : plan.ipp;
-                    lephuff::ProgRstWave w;
-                    w.run_piece(&sc, &ws, rows, plan.nint, first, count, &outs[p]);
-                }
-                lephuff::prog_rst_reduce(&sc, &plan, outs.data(), rows);
-                taken[i] = 1;
-                *pieces += plan.npieces;
-            } else if (lephuff::prog_win_takes(sc)) {
-                lephuff::ProgWinWave w;
-                w.run_scan_win<false>(&sc, &ws, rows);
-            } else {
-                lephuff::ProgDecWave w;
-                w.run_scan<false>(&sc, &sh, rows);
-            }
-        }
+// The scans of one file as the launch code runs them (scan_dec_driver.h over lep_scan_decode_plan.h's plan): a file that has a scan flagged
+// LEP_HUFFDEC_RST_TABLE (the caller has put the marker positions behind the slot) level by level -- those scans piece by piece and then the
+// reduce step, the window form where it takes the scan, lep_huffprogdec.h for the rest; scans of sequential frames go to the single-wave
+// sequential kernel.  rst = false: the interval form off, whatever the descriptors carry.
+static int run_levels(const lep_huffprogdec_scan* scans, int nscan, lephuff::HuffDecRow* rows, bool rst, uint32_t piece_floor, int32_t* taken, uint32_t* pieces) {
+    lephuff::ProgDecOptions o;
+    o.lanes = false; o.win = true; o.rst = rst; o.pipeline = false; o.split = false;
+    o.piece_floor = piece_floor ? piece_floor : lephuff::kRstPieceFloor;
+    return emu_prog_dec_drive(reinterpret_cast<const lephuff::ProgDecScan*>(scans), nscan, o, rows, nullptr, nullptr, taken, pieces);
 }
 
 // piece_floor: bytes of scan per piece (0: the product's; 1: a piece per interval; 0xffffffff: the whole scan in one piece).
@@ -55,15 +28,12 @@ extern "C" int emu_huffman_progressive_decode_rst(const lep_huffprogdec_scan* sc
                                                   int32_t* second_chance) {
     lephuff::HuffDecRow* rows = reinterpret_cast<lephuff::HuffDecRow*>(rows_);
     uint32_t pieces = 0;
-    for (int i = 0; i < nscan; ++i) taken[i] = 0;
-    run_levels(scans, nscan, rows, true, piece_floor, taken, &pieces);
+    if (int rc = run_levels(scans, nscan, rows, true, piece_floor, taken, &pieces)) return rc;
     bool again = false;
     for (int i = 0; i < nscan; ++i) again = again || (taken[i] && (rows[scans[i].result_off].aux >> 8) != 0);
     if (again) {
         for (int c = 0; c < scans[0].t.ncomp && c < 4; ++c) memset(scans[0].t.blocks[c], 0, (size_t)scans[0].t.bch[c] * (size_t)scans[0].bcv[c] * 128);
-        int32_t none[64] = {0};
-        uint32_t zero = 0;
-        run_levels(scans, nscan, rows, false, 0, none, &zero);
+        if (int rc = run_levels(scans, nscan, rows, false, 0, nullptr, nullptr)) return rc;
     }
     if (pieces_out) *pieces_out = pieces;
     if (second_chance) *second_chance = again ? 1 : 0;

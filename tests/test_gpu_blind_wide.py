@@ -61,7 +61,14 @@ def _decode_on_device(codec, jpgs, simt):
         assert L.lep_gpu_malloc(g, n, C.byref(p)) == 0
         return p
 
-    opened = [_open(j) for j in jpgs]
+    def opened_as_flagged(jpg):     # (a file flagged LEP_HUFFDEC_RST_TABLE: the marker positions go behind its scan bytes, as the flag promises)
+        one = _open(jpg)
+        if not one[0].flags & 2:
+            return one
+        L.lep_jpeg_close(one[3])
+        return _open(jpg, with_restart_table=True)
+
+    opened = [opened_as_flagged(j) for j in jpgs]
     imgs = (abi.HuffDecImage * len(jpgs))()
     dev, planes_dev, nrows = [], [], []
     rows_total = 0
@@ -137,6 +144,34 @@ def test_gpu_lane_kernels_on_wide_blind_scans_with_the_products_subsequences(mon
     monkeypatch.delenv("LEP_HUFFDEC_SIMT_BITS", raising=False)
     files = _eligible(_files(WIDE, [(1920, 1080)]), must=("5_y22_c", "6_420", "6_y21_cb21_cr21"))
     assert len(files) >= 3
+    _lane_kernels_equal_the_single_wave_kernel(files)
+
+
+@pytest.mark.parametrize("bits", [1024, 0], ids=["1024_bits", "the_rule"])
+def test_gpu_lane_kernels_on_a_mixed_launch(monkeypatch, bits):
+    """ONE launch of the lane decoder holding wide blind, plain and interval images in this order: six-block 4:2:0, 4:4:4, a 4:2:0 file
+    with a restart interval of one MCU row (flagged LEP_HUFFDEC_RST_TABLE: lane = interval), five-block, two-block.  At 1024 bits both
+    wide files have more than 64 subsequences (142 and 115), so the launch plan (lep_huffdec_simt.h simt_dec_plan) puts wide wavefronts
+    and slot offsets of two wide images on both sides of plain ones; then the subsequence length the plan chooses by itself.  For every
+    file: status 0, records and frame of the single-wave kernel."""
+    import jpeg_writer as jw
+    from test_blind_wide_emulation import _open
+
+    if bits:
+        monkeypatch.setenv("LEP_HUFFDEC_SIMT_BITS", str(bits))
+    else:
+        monkeypatch.delenv("LEP_HUFFDEC_SIMT_BITS", raising=False)
+    c420 = [(1, 2, 2, 0, 0, 0), (2, 1, 1, 1, 1, 1), (3, 1, 1, 1, 1, 1)]
+    interval = ("420 rst 333x250", jw.write_baseline(333, 250, c420, np.random.default_rng(5), density=0.1, restart_interval=21)[0])
+    files = _files(["6_420"], [(333, 250)]) + _files(["3_444"], [(97, 50)]) + [interval] + _files(["5_y22_c"], [(333, 250)]) + _files(["2_two"], [(97, 50)])
+    assert len(_eligible(files, must=("6_420", "3_444", "420", "5_y22_c", "2_two"))) == 5
+    one = _open(interval[1])
+    abi.lib().lep_jpeg_close(one[3])
+    assert one[0].flags & 2 and one[0].rsti == one[0].mcuh == 21, "the interval file must come flagged: a row of MCUs per interval"
+    for k in (0, 3):
+        one = _open(files[k][1])
+        abi.lib().lep_jpeg_close(one[3])
+        assert one[0].scan_len * 8 > 64 * 1024, (files[k][0], "more than one wavefront at 1024 bits")
     _lane_kernels_equal_the_single_wave_kernel(files)
 
 

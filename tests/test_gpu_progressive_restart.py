@@ -148,6 +148,66 @@ def test_device_entry_with_the_new_form_on_and_off(generated, without_the_new_fo
     assert results[0][2] == results[1][2] == results[2][2], "records differ"
 
 
+def test_device_entry_with_a_mixed_launch():
+    """ONE call of lep_gpu_huffman_progressive_decode_device holding the scans of three files, interleaved file by file: the fixture with
+    restart intervals (the interval form), a progressive fixture without (the pipelined launch) and a sequential frame in two scans (the
+    lane decoder) -- every part of the launch plan (lep_scan_decode_plan.h) at once, row_off / result_off shifted per file as the batch
+    pipeline shifts them.  Frames and every record equal what three separate calls give; the kernel's name is the last part's."""
+    L = abi.lib()
+    codec = GpuCodec(0)
+    g = codec.handle
+    names = ["prog_c422_rst_176x112", "prog_c420_320x240", "seq_ycb_cr_422_640x480_2seg"]
+    files = [_resident_scans(L, g, golden(n)[0]) for n in names]
+    nrow = C.sizeof(abi.HuffDecRow)
+
+    def frames_and_records(d_rows_of, first_of):
+        out = []
+        for k, (h, scans, n, d_frame, fbytes, d_rows, nrec, mem) in enumerate(files):
+            frame, rows = C.create_string_buffer(fbytes), (abi.HuffDecRow * nrec)()
+            assert L.lep_gpu_memcpy_d2h(g, frame, d_frame, fbytes) == 0
+            assert L.lep_gpu_memcpy_d2h(g, rows, C.c_void_p(d_rows_of(k).value + first_of(k) * nrow), nrec * nrow) == 0
+            out.append((frame.raw, [(r.bitpos, tuple(r.last_dc), r.aux) for r in rows]))
+        return out
+
+    for h, scans, n, d_frame, fbytes, d_rows, nrec, mem in files:                      # three separate calls
+        assert L.lep_gpu_huffman_progressive_decode_device(g, scans, n, d_rows, None) == 0, codec.last_error()
+        assert L.lep_gpu_sync(g) == 0, codec.last_error()
+    want = frames_and_records(lambda k: files[k][5], lambda k: 0)
+    assert any(f[1][i][0] for f in want for i in range(len(f[1]))), "the separate calls left no record"
+    # one call: the frames wiped, one record arena, file k's records from first[k] on
+    first = [sum(f[6] for f in files[:k]) for k in range(3)]
+    total = sum(f[6] for f in files)
+    d_all = C.c_void_p()
+    assert L.lep_gpu_malloc(g, total * nrow, C.byref(d_all)) == 0 and L.lep_gpu_memset(g, d_all, 0, total * nrow) == 0
+    mixed = (abi.HuffProgDecScan * sum(f[2] for f in files))()
+    at = 0
+    for i in range(max(f[2] for f in files)):
+        for k, (h, scans, n, d_frame, fbytes, d_rows, nrec, mem) in enumerate(files):
+            if i >= n:
+                continue
+            C.memmove(C.byref(mixed[at]), C.byref(scans[i]), C.sizeof(abi.HuffProgDecScan))
+            mixed[at].t.rows_off += first[k]
+            mixed[at].result_off += first[k]
+            at += 1
+    assert at == len(mixed)
+    for h, scans, n, d_frame, fbytes, d_rows, nrec, mem in files:
+        assert L.lep_gpu_memset(g, d_frame, 0, fbytes) == 0
+    assert L.lep_gpu_huffman_progressive_decode_device(g, mixed, at, d_all, None) == 0, codec.last_error()
+    assert L.lep_gpu_sync(g) == 0, codec.last_error()
+    name = L.lep_gpu_last_kernel_name(g).decode()
+    got = frames_and_records(lambda k: d_all, lambda k: first[k])
+    for h, scans, n, d_frame, fbytes, d_rows, nrec, mem in files:
+        L.lep_jpeg_close(h)
+        for m in mem:
+            L.lep_gpu_free(g, m)
+    L.lep_gpu_free(g, d_all)
+    codec.close()
+    assert "huffprogdec_rst" in name, name
+    for k, n in enumerate(names):
+        assert got[k][0] == want[k][0], (n, "frames differ")
+        assert got[k][1] == want[k][1], (n, "records differ")
+
+
 def test_damaged_big_files_with_restart_intervals(generated):
     """three damaged 1080p files (inside different scans): status and bytes as per-file compress gives them"""
     codec = GpuCodec(0)
