@@ -931,6 +931,7 @@ static int finish_gpu_sequential_scans(JpegFile* jf, const std::vector<ProgScanD
                     record(base + e.bitpos, e.last_dc, y);
                 }
             } else {
+                if (r[0].bitpos > sc.t.scan_len * 8u) return -1;
                 record(base + r[0].bitpos, r[0].last_dc, 0);
             }
             last_mcu = q.bc / (hmul * luma_mul);

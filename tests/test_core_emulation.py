@@ -1160,6 +1160,53 @@ def test_sequential_frames_in_several_scans_on_the_scan_kernels(emu, name):
             assert length == len(want) and got == want
 
 
+def test_sequential_scans_finish_refuses_a_chroma_record_behind_its_scan(emu):
+    """lep_jpeg_finish_gpu_progressive on a sequential frame coded in several scans: the row records the scan decoders leave are accepted
+    as they are; the same records with the first record of a one-component CHROMA scan pointing behind that scan's last bit -- what a
+    stale record in the reused rows arena would look like -- are refused like every other record past its scan, not used as an index
+    into the scan bytes."""
+    import jpeg_writer as jw
+    import numpy as np
+    from lepton_amd import abi
+
+    L = abi.lib()
+    comps, script = SEQUENTIAL_SCAN_SCRIPTS["y_cb_cr_444"]
+    jpg, _ = jw.write_sequential_scans(97, 50, comps, np.random.default_rng(20), script, density=0.3)
+    valid = []
+    hnd, planes, status = _progressive_decode_on_the_emulation(emu, jpg, rows_out=valid)
+    assert status == 0                                   # the valid records, finished by the same entry point
+    _same_as_the_host_parser(jpg, hnd, planes)
+    L.lep_jpeg_close(hnd)
+
+    def finish(patch):
+        h, plan1, ok = C.c_void_p(), abi.HuffDecImage(), C.c_int(0)
+        assert L.lep_jpeg_open_gpu(jpg, len(jpg), C.byref(h), C.byref(plan1), C.byref(ok)) == 0 and not ok.value
+        scans = (abi.HuffProgDecScan * 64)()
+        nscan, need, ok2 = C.c_int(0), C.c_int(0), C.c_int(0)
+        assert L.lep_jpeg_open_gpu_progressive(h, scans, 64, C.byref(nscan), C.byref(need), C.byref(ok2)) == 0 and ok2.value and nscan.value == 3
+        rows = (abi.HuffDecRow * len(valid))()
+        for r, (bitpos, last_dc, aux) in zip(rows, valid):
+            r.bitpos, r.aux = bitpos, aux
+            for i in range(4):
+                r.last_dc[i] = last_dc[i]
+        chroma = [scans[i] for i in range(nscan.value) if scans[i].cmpc == 1 and scans[i].cmp[0] != 0]
+        assert len(chroma) == 2
+        patch(rows, chroma[0])
+        rc = L.lep_jpeg_finish_gpu_progressive(h, scans, nscan.value, rows)
+        L.lep_jpeg_close(h)
+        return rc
+
+    def at_the_end(rows, sc):
+        rows[sc.t.rows_off].bitpos = sc.t.scan_len * 8            # the last position a record may name
+
+    def past_the_end(rows, sc):
+        rows[sc.t.rows_off].bitpos = sc.t.scan_len * 8 + 1
+
+    assert finish(lambda rows, sc: None) == 0
+    assert finish(at_the_end) == 0
+    assert finish(past_the_end) != 0
+
+
 def test_restart_interval_that_changes_from_scan_to_scan(emu):
     """A DRI segment may stand in front of ANY scan: the progressive files of phone cameras (the reference's images/androidprogressive.jpg,
     iphoneprogressive2.jpg) set one per scan -- 258 / 516, 768 / 1524 MCUs or blocks, a row of the scan's own units.  Until the end of round 6
