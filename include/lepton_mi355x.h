@@ -102,6 +102,30 @@ int lep_gpu_encode_device(lep_gpu *g, const lep_image_desc *images, int nimg, co
 int lep_gpu_decode_device(lep_gpu *g, const lep_image_desc *images, int nimg, const lep_segment *segs, int nseg,
                           const uint8_t *d_streams, const uint64_t *stream_offsets, const uint32_t *d_stream_len,
                           int32_t *d_status, void *hip_stream);
+/* Resumable decode: the launch of lep_gpu_decode_device advanced one band of MCU rows at a time, every band a launch that finishes, so
+ * that the frame rows a band completed can be used (re-coded, sent on) while the rest is still to be decoded, and a stream that turns
+ * inconsistent says at which block.
+ *   begin    derives, orders and uploads what a decode launch needs into the current workspace set (lep_gpu_use_arena) and clears the
+ *            segments' resume records.  d_streams / d_stream_len and the frames stay the caller's and must live until `end`.
+ *   advance  launches one band on the session's stream, waits for it and copies the records back: every running segment decodes on
+ *            up to the MCU row (the one it stood in + band_mcu_rows); band_mcu_rows <= 0 = to the end.  progress[nseg] (host, the
+ *            caller's segment order; may be NULL) and *running (segments still running; may be NULL) are filled.  The frames are
+ *            readable between two advances.  A segment that finished or failed is not touched by later advances.
+ *   end      closes the session.
+ * A session owns the workspace set that was current at `begin`: until `end`, encode / decode launches and a second `begin` on that set,
+ * and lep_gpu_trim / lep_gpu_release_memory (which take both sets' memory), return LEP_ASSERTION_FAILURE with a lep_gpu_last_error
+ * text; the other set stays usable after lep_gpu_use_arena.  advance / end act on the set that is current when they are called.
+ * lep_gpu_decode_device / _host are unchanged and do not go through the banded kernel. */
+typedef struct lep_decode_progress {       /* one per segment, caller's order */
+    int32_t status;                        /* -1 running, 0 finished, otherwise the exit code */
+    int32_t rows_done[LEP_MAX_COMPONENTS]; /* every block row of component c that is this segment's and lies below rows_done[c] is in the frame */
+    int32_t fail_component, fail_y, fail_x;/* the block at which status became non-zero (it is not stored, everything before it is); -1 otherwise */
+    uint32_t bins;
+} lep_decode_progress;
+int lep_gpu_decode_rows_begin(lep_gpu *g, const lep_image_desc *images, int nimg, const lep_segment *segs, int nseg,
+                              const uint8_t *d_streams, const uint64_t *stream_offsets, const uint32_t *d_stream_len, void *hip_stream);
+int lep_gpu_decode_rows_advance(lep_gpu *g, int band_mcu_rows, lep_decode_progress *progress /* host, nseg */, int *running);
+int lep_gpu_decode_rows_end(lep_gpu *g);
 /* Workspace set (0 or 1) the next lep_gpu_*_device launches use.  Two launches that overlap in time (different hip streams) must
  * use different sets; a set may be reused once the launch that used it has finished (stream order does that when the same
  * stream always goes with the same set).  Default 0. */
@@ -431,6 +455,20 @@ int lep_compress(lep_gpu *g, const uint8_t *jpg, size_t len, lep_bytes *out);
  * One file per call, on the host parser; lep_compress_batch_slices takes many slices through the batch pipeline and gives the same bytes. */
 int lep_compress_slice(lep_gpu *g, const uint8_t *jpg, size_t len, size_t start_byte, size_t trunc, lep_bytes *out);
 int lep_decompress(lep_gpu *g, const uint8_t *lepdata, size_t len, lep_bytes *out);
+/* lep_decompress with the JPEG's bytes handed to `sink` as they become final, in file order.  A whole baseline file with one interleaved
+ * scan is decoded in a session (lep_gpu_decode_rows_*), band_mcu_rows MCU rows per advance (<= 0: one advance): the header goes out before
+ * the first advance, then after every advance the MCU rows that have become complete are Huffman-coded on the host, segment by segment
+ * from each segment's hand-off; segment 0's rows go out as they come, a later segment's bytes once the segments in front of it are done.
+ * Every other file (progressive, truncated, several files back to back, ...) is lep_decompress and one sink call: stats->advances = 0.
+ * The bytes sunk, concatenated, are lep_decompress's and the return value is the same; when a segment fails, what has been sunk by
+ * then are bytes of rows in front of the failing block.  A sink that returns non-zero ends the call with LEP_OS_ERROR.  stats may be NULL. */
+typedef int (*lep_sink)(void *user, const uint8_t *data, size_t len);
+typedef struct lep_stream_stats {
+    int32_t advances;                          /* lep_gpu_decode_rows_advance calls made */
+    int32_t advances_before_first_scan_byte;   /* ... of them before the first byte of the scan reached the sink */
+    uint64_t bytes_before_last_advance;        /* bytes the sink had when the last advance was launched */
+} lep_stream_stats;
+int lep_decompress_stream(lep_gpu *g, const uint8_t *lepdata, size_t len, int band_mcu_rows, lep_sink sink, void *user, lep_stream_stats *stats);
 
 /* Whole batches of files as a pipeline (what `lepton -socket` workers / src/lepton/socket_serve.cc:312-390 would hand to
  * the GPU): JPEG parsing + Huffman scan decode on a host thread pool, coefficient frames over PCIe on a copy stream while

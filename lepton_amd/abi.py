@@ -96,6 +96,18 @@ class HuffDecRow(C.Structure):
     _fields_ = [("bitpos", C.c_uint32), ("last_dc", C.c_int16 * 4), ("aux", C.c_int32)]
 
 
+class DecodeProgress(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rows_done", C.c_int32 * MAX_COMPONENTS), ("fail_component", C.c_int32), ("fail_y", C.c_int32),
+                ("fail_x", C.c_int32), ("bins", C.c_uint32)]
+
+
+class StreamStats(C.Structure):
+    _fields_ = [("advances", C.c_int32), ("advances_before_first_scan_byte", C.c_int32), ("bytes_before_last_advance", C.c_uint64)]
+
+
+SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
+
+
 class BatchOptions(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("verify", C.c_int32), ("chunk_frame_bytes", C.c_size_t), ("host_huffman", C.c_int32), ("chunk_images", C.c_int32), ("overlap_launches", C.c_int32)]
 
@@ -182,6 +194,12 @@ def lib():
         L.lep_gpu_decode_host.argtypes = [vp, P(ImageDesc), C.c_int, P(Segment), C.c_int, P(Bytes), P(C.c_int32)]
         L.lep_gpu_encode_device.argtypes = [vp, P(ImageDesc), C.c_int, P(Segment), C.c_int, vp, P(C.c_uint64), vp, vp, vp]
         L.lep_gpu_decode_device.argtypes = [vp, P(ImageDesc), C.c_int, P(Segment), C.c_int, vp, P(C.c_uint64), vp, vp, vp]
+        if hasattr(L, "lep_gpu_decode_rows_begin"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_gpu_decode_rows_begin.argtypes = [vp, P(ImageDesc), C.c_int, P(Segment), C.c_int, vp, P(C.c_uint64), vp, vp]
+            L.lep_gpu_decode_rows_advance.argtypes = [vp, C.c_int, P(DecodeProgress), P(C.c_int)]
+            L.lep_gpu_decode_rows_end.argtypes = [vp]
+            L.lep_decompress_stream.argtypes = [vp, vp, C.c_size_t, C.c_int, SINK_FN, vp, P(StreamStats)]
+        L.lep_gpu_use_arena.argtypes = [vp, C.c_int]
         L.lep_gpu_sync.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.restype = C.c_double
@@ -261,4 +279,5 @@ EXPORTS = [
     "lep_jpeg_open_gpu_progressive", "lep_jpeg_finish_gpu_progressive", "lep_jpeg_scan_restarts_of", "lep_gpu_huffman_progressive_decode_device",
     "lep_jpeg_plan_progressive_check", "lep_gpu_last_stage_ms", "lep_jpeg_set_container_version", "lep_container_can_write_version", "lep_jpeg_plan_scan_check", "lep_jpeg_scan_file_range",
     "lep_gpu_huffman_progressive_encode_forms", "lep_compress_batch_slices",
+    "lep_gpu_decode_rows_begin", "lep_gpu_decode_rows_advance", "lep_gpu_decode_rows_end", "lep_decompress_stream",
 ]

@@ -192,6 +192,77 @@ class GpuCodec:
         if rc:
             raise LeptonError(rc, "lep_gpu_decode_host [%s]" % self.last_error())
 
+    def decode_rows(self, files, band_mcu_rows, fill=0):
+        """files: [LepFile].  A generator over a decode session (lep_gpu_decode_rows_*): after every advance of band_mcu_rows MCU rows
+        (<= 0: to the end) the files' coefficient frames are fetched from the device and the list of progress records, one per
+        segment in the files' order, is yielded; the frames are readable between yields.  The device frames start filled with the
+        byte `fill`.  The session is closed when the generator ends or is closed."""
+        L, h = self._L, self.handle
+        nimg = len(files)
+        flat, offs, blob = [], [0], b""
+        for i, f in enumerate(files):
+            for s, st in zip(f.segments, f.streams):
+                flat.append(abi.Segment(i, s.luma_y_start, s.luma_y_end, s.is_last))
+                blob += st + bytes(-len(st) % 256)
+                offs.append(len(blob))
+        nseg = len(flat)
+        segs = (abi.Segment * nseg)(*flat)
+        lens = (C.c_uint32 * nseg)(*[len(st) for f in files for st in f.streams])
+        offsets = (C.c_uint64 * (nseg + 1))(*offs)
+        dev = (abi.ImageDesc * nimg)(*[f.desc for f in files])
+        owned = []
+
+        def dmalloc(n):
+            p = C.c_void_p()
+            _check(L.lep_gpu_malloc(h, n, C.byref(p)), "lep_gpu_malloc")
+            owned.append(p)
+            return p
+
+        begun = False
+        try:
+            for i, f in enumerate(files):
+                for c in range(f.desc.ncomp):
+                    p = dmalloc(f.desc.nblocks(c) * 128 + 256)
+                    _check(L.lep_gpu_memset(h, p, fill, f.desc.nblocks(c) * 128), "lep_gpu_memset")
+                    dev[i].blocks[c] = p.value
+            d_streams, d_lens = dmalloc(len(blob) + 256), dmalloc(4 * nseg)
+            if blob:
+                _check(L.lep_gpu_memcpy_h2d(h, d_streams, blob, len(blob)), "lep_gpu_memcpy_h2d")
+            _check(L.lep_gpu_memcpy_h2d(h, d_lens, lens, 4 * nseg), "lep_gpu_memcpy_h2d")
+            rc = L.lep_gpu_decode_rows_begin(h, dev, nimg, segs, nseg, d_streams, offsets, d_lens, None)
+            if rc:
+                raise LeptonError(rc, "lep_gpu_decode_rows_begin [%s]" % self.last_error())
+            begun = True
+            prog = (abi.DecodeProgress * nseg)()
+            running = C.c_int(1)
+            while running.value > 0:
+                rc = L.lep_gpu_decode_rows_advance(h, band_mcu_rows, prog, C.byref(running))
+                if rc:
+                    raise LeptonError(rc, "lep_gpu_decode_rows_advance [%s]" % self.last_error())
+                for i, f in enumerate(files):
+                    for c in range(f.desc.ncomp):
+                        _check(L.lep_gpu_memcpy_d2h(h, f.desc.blocks[c], dev[i].blocks[c], f.desc.nblocks(c) * 128), "lep_gpu_memcpy_d2h")
+                yield [abi.DecodeProgress.from_buffer_copy(prog[k]) for k in range(nseg)]
+        finally:
+            if begun:
+                L.lep_gpu_decode_rows_end(h)
+            for p in owned:
+                L.lep_gpu_free(h, p)
+
+    def decompress_stream(self, lep, band_mcu_rows):
+        """lep_decompress_stream: (chunks, stats) -- the byte strings the sink received, in order, and the call's statistics as a dict"""
+        chunks = []
+
+        def sink(user, data, n):
+            chunks.append(C.string_at(data, n))
+            return 0
+
+        stats = abi.StreamStats()
+        rc = self._L.lep_decompress_stream(self.handle, bytes(lep), len(lep), band_mcu_rows, abi.SINK_FN(sink), None, C.byref(stats))
+        if rc:
+            raise LeptonError(rc, "lep_decompress_stream [%s]" % self.last_error())
+        return chunks, {k: getattr(stats, k) for k, _ in abi.StreamStats._fields_}
+
     def compress(self, jpg):
         out = abi.Bytes()
         rc = self._L.lep_compress(self.handle, bytes(jpg), len(jpg), C.byref(out))

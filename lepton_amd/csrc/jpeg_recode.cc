@@ -309,40 +309,61 @@ int recode_finish(LepFile* lf, const RecodePlan& plan, const std::vector<std::pa
     return 0;
 }
 
+// One thread segment of a planned file (recode_prepare said gpu_ok) coded MCU row by MCU row, as far as the caller says its rows are in
+// the frame: starts from the segment's hand-off (partial byte, last DCs), is bound by its out_cap.  Coded in one go by the host threads
+// below, and band by band by lep_decompress_stream (lep_api.cc), whose decoder delivers the frame a few MCU rows at a time.
+struct SegmentRowCoder::Impl {
+    RowCoder rc;
+    BitWriter w;
+    BoundedOut o;
+    int16_t lastdc[4];
+    int next, end, mcuh;
+    Impl(LepFile* lf) : rc(*lf) {}
+};
+SegmentRowCoder::SegmentRowCoder(LepFile* lf, const RecodePlan& plan, size_t s) : p(new Impl(lf)) {
+    const RecodeSegment& g = plan.segs[s];
+    p->rc.seg_first_mcu_row = g.mcu_row0;
+    p->w.fillbit = (uint8_t)lf->jpeg.padbit;
+    p->w.seed((uint8_t)(g.overhang & 255u), (int)((g.overhang >> 8) & 255u));
+    p->o.bound = g.out_cap;
+    p->o.shut = g.out_cap == 0;
+    memcpy(p->lastdc, g.last_dc, sizeof p->lastdc);
+    p->next = g.mcu_row0; p->end = g.mcu_row1; p->mcuh = lf->jpeg.mcuh;
+}
+SegmentRowCoder::~SegmentRowCoder() { delete p; }
+int SegmentRowCoder::next_row() const { return p->next; }
+int SegmentRowCoder::end_row() const { return p->end; }
+void SegmentRowCoder::code_rows(int upto) {
+    for (; p->next < upto && p->next < p->end; ++p->next) {
+        p->rc.mcu_row(p->w, p->next * p->mcuh, p->o, p->lastdc);
+        drain(p->w, p->o);
+        p->w.row_flush();
+    }
+}
+const std::vector<uint8_t>& SegmentRowCoder::bytes() const { return p->o.buf; }
+void SegmentRowCoder::take_bytes(std::vector<uint8_t>* out) { out->swap(p->o.buf); }
+void SegmentRowCoder::end_state(lep_huff_end* e) const {
+    e->attempted = (uint32_t)std::min<size_t>(p->o.attempted, 0xffffffffu);
+    e->overhang_byte = p->w.overhang_bits() ? p->w.overhang_byte() : (uint8_t)0;
+    e->num_overhang_bits = (uint8_t)p->w.overhang_bits();
+    memcpy(e->last_dc, p->lastdc, sizeof p->lastdc);
+    e->pad = 0;
+}
+
 // The thread segments of a planned file (recode_prepare said gpu_ok) written on host threads, one per segment: what the GPU scan
 // encoders do, with the row coder above.  Every segment starts from its hand-off (partial byte, last DCs) and is bound by its
 // out_cap; bytes and end states go to recode_finish like the kernels'.  Used by lep_jpeg_check_restores, where the one-thread walk of
 // recode_jpeg was a quarter of a 4K file's compression time.
 int recode_segments_on_threads(LepFile* lf, const RecodePlan& plan, std::vector<std::vector<uint8_t>>* seg_bytes, std::vector<lep_huff_end>* ends) {
     if (!plan.gpu_ok) return EX_ASSERTION_FAILURE;
-    const JpegFile& jf = lf->jpeg;
     const size_t n = plan.segs.size();
     seg_bytes->assign(n, std::vector<uint8_t>());
     ends->assign(n, lep_huff_end());
     auto one = [&](size_t s) {
-        const RecodeSegment& g = plan.segs[s];
-        RowCoder rc(*lf);
-        rc.seg_first_mcu_row = g.mcu_row0;
-        BitWriter w;
-        w.fillbit = (uint8_t)jf.padbit;
-        w.seed((uint8_t)(g.overhang & 255u), (int)((g.overhang >> 8) & 255u));
-        BoundedOut o;
-        o.bound = g.out_cap;
-        o.shut = g.out_cap == 0;
-        int16_t lastdc[4];
-        memcpy(lastdc, g.last_dc, sizeof lastdc);
-        for (int row = g.mcu_row0; row < g.mcu_row1; ++row) {
-            rc.mcu_row(w, row * jf.mcuh, o, lastdc);
-            drain(w, o);
-            w.row_flush();
-        }
-        lep_huff_end& e = (*ends)[s];
-        e.attempted = (uint32_t)std::min<size_t>(o.attempted, 0xffffffffu);
-        e.overhang_byte = w.overhang_bits() ? w.overhang_byte() : (uint8_t)0;
-        e.num_overhang_bits = (uint8_t)w.overhang_bits();
-        memcpy(e.last_dc, lastdc, sizeof lastdc);
-        e.pad = 0;
-        (*seg_bytes)[s].swap(o.buf);
+        SegmentRowCoder c(lf, plan, s);
+        c.code_rows(c.end_row());
+        c.end_state(&(*ends)[s]);
+        c.take_bytes(&(*seg_bytes)[s]);
     };
     // Nothing may leave this function as an exception: it is called from extern "C" entry points, and a vector of joinable threads
     // unwound by one would end the process (a thread limit under lepton_served, an allocation failure in a worker).  A segment that

@@ -11,19 +11,8 @@
 #include "jpeg_model.h"
 #include "lep_container.h"
 #include "lep_slice.h"
+#include "lep_handles.h"
 
-struct lep_jpeg {
-    lep::JpegFile jf;
-    lep::EncodeOptions opt;
-};
-struct lep_file {
-    lep::LepFile lf;
-    bool frame_ready = false;
-    lep::RecodePlan plan;
-    bool planned = false;
-    lep::ProgPlan prog;
-    bool prog_planned = false;
-};
 static_assert(sizeof(lep_huffprog_image) == sizeof(lep::ProgImage) && sizeof(lep_huffprog_scan) == sizeof(lep::ProgScan), "C ABI mirrors");
 static_assert(sizeof(lep_huffdec_image) == sizeof(lep::ScanDecodePlan) && sizeof(lep_huffdec_row) == sizeof(lep::ScanDecodeRow), "C ABI mirrors");
 static_assert(sizeof(lep_huffprogdec_scan) == sizeof(lep::ProgScanDecodePlan), "C ABI mirrors");

@@ -122,5 +122,22 @@ int recode_progressive_finish(LepFile* lf, const ProgPlan& plan, const std::vect
                               std::vector<uint8_t>* out);
 int recode_finish(LepFile* lf, const RecodePlan& plan, const std::vector<std::pair<const uint8_t*, size_t>>& seg_bytes, const lep_huff_end* ends,
                   std::vector<uint8_t>* out);
+// one thread segment of a planned file Huffman-coded on the host MCU row by MCU row (jpeg_recode.cc): rows [next_row, upto) per call
+class SegmentRowCoder {
+public:
+    SegmentRowCoder(LepFile* lf, const RecodePlan& plan, size_t s);
+    ~SegmentRowCoder();
+    SegmentRowCoder(const SegmentRowCoder&) = delete;
+    SegmentRowCoder& operator=(const SegmentRowCoder&) = delete;
+    int next_row() const;
+    int end_row() const;
+    void code_rows(int upto);
+    const std::vector<uint8_t>& bytes() const;    // what has been written so far (every byte final)
+    void take_bytes(std::vector<uint8_t>* out);
+    void end_state(lep_huff_end* e) const;        // the state the writer is in: what the next hand-off recorded
+private:
+    struct Impl;
+    Impl* p;
+};
 
 }  // namespace lep

@@ -368,6 +368,31 @@ struct BoolDec4S {
 #define LEP_DEC4_SCALAR 2   // measured (1024 x 4K, MI355X, profiles/r02m_*): 0: 1232 ms, 2: 1204, 3: 1212, 11: 1226, 7: 1400, 15: 1440
 #endif
 
+// A segment's resume record (Dec4WaveT::run_rows): all that a segment carries from one band's launch to the next beside its model, its
+// summary rings, the frame and the two LDS-resident Branch tables.  Written by lane 0 at a band's end; all zero = fresh.
+enum : int32_t { kRowsFresh = 0, kRowsRunning = 1, kRowsFinished = 2, kRowsFailed = 3 };
+struct Dec4Resume {
+    int32_t state, code;          // kRows*; the exit code when failed
+    uint32_t idx, top;            // next schedule index (row_spec); bit c: component c has not had a row in this segment yet
+    uint32_t vhi, vlo;            // the bool reader between two bins; raw is fetch(wi)
+    int32_t count;
+    uint32_t range, wi;
+    uint32_t nbins;
+    int32_t rows_done[3];         // frame row one past the last block row of component c this segment has stored (0 before the first)
+    int32_t fail_component, fail_y, fail_x;   // the block decode_block refused (kRowsFailed), else -1
+};
+
+// what Dec4WaveT::run<true> starts from and reports (run_rows fills it from the record and writes the record from it)
+struct RowsWalk {
+    const Dec4Resume* rec; const uint32_t* lds_save;   // the bool reader's words and the LDS Branches of the band before (not fresh)
+    bool fresh;
+    uint32_t idx, stop, total;    // first schedule index; the index the band ends in front of (0xffffffff: set at the first row decoded, or none); indices per MCU row
+    int band;
+    bool top[3];
+    int rows_done[3];
+    int state, fail_component, fail_y, fail_x;
+};
+
 // SCMASK: which serial rounds run on the scalar unit (LEP_DEC4_SCALAR above for the throughput kernel; the launches of a few segments,
 // where a wavefront has its SIMD to itself and the dependent-instruction latency is all that counts, take their own: lep_gpu.hip)
 template <int SCMASK>
@@ -1139,19 +1164,27 @@ struct Dec4WaveT {
         return 0;
     }
 
+    // ROWS = false: the segment from its first row to its last.  ROWS = true (run_rows): the same walk, taken up where `rw` says and ended
+    // in front of the band's end as well, after which `rw` says where and how it ended.  Returns the exit code of the block that could
+    // not be decoded; that block is not stored, everything in front of it is.
+    template <bool ROWS = false>
     WDEV int run(const ImageDev* image, const SegDev& seg, uint32_t* model_words, NSum* ns, Dec4Shared* shared, const uint8_t* stream,
-                 uint32_t len) {
+                 uint32_t len, RowsWalk* rw = nullptr) {
         img = image; model = model_words; sh = shared; nbins = 0;
         LEP_PRIO_PARALLEL();
         init_tables();
-        bc.init_stream(stream, len);
+        if (ROWS && !rw->fresh) resume_stream(stream, len, *rw);
+        else bc.init_stream(stream, len);
         bool top[3] = {true, true, true};
-        for (uint32_t idx = 0;; ++idx) {
+        if (ROWS) for (int c = 0; c < 3; ++c) top[c] = rw->top[c];
+        for (uint32_t idx = ROWS ? rw->idx : 0;; ++idx) {
             RowSpec r = row_spec(image, idx);
             if (r.done) break;
             if (r.luma_y >= seg.y1 && !seg.is_last) break;
+            if (ROWS) if (idx >= rw->stop) { rw->state = kRowsRunning; rw->idx = idx; break; }
             if (r.skip) continue;
             if (r.luma_y < seg.y0) continue;
+            if (ROWS) if (rw->stop == 0xffffffffu && rw->band > 0) rw->stop = (idx / rw->total + (uint32_t)rw->band) * rw->total;   // a fresh segment's first row
             stage_component(r.component);
             const int w = img->width[comp], yb = r.curr_y;
             int16_t* row = img->blocks[comp] + (int64_t)yb * w * 64;
@@ -1187,6 +1220,7 @@ struct Dec4WaveT {
                 }
                 LSYNC();
                 int rc = decode_block(x > 0, has_above);
+                if (ROWS) if (rc) { rw->state = kRowsFailed; rw->fail_component = comp; rw->fail_y = yb; rw->fail_x = x; }
                 if (rc) return rc;
                 LEP_MARK("store");
         LANES(l) {
@@ -1194,8 +1228,63 @@ struct Dec4WaveT {
                     if (l < (int)(sizeof(NSum) / 4)) ((uint32_t*)&nrow[x])[l] = ((const uint32_t*)&sh->ns_here)[l];
                 }
             }
+            if (ROWS) for (int c = 0; c < 3; ++c) { if (c == comp) { rw->rows_done[c] = yb + 1; rw->top[c] = false; } }   // (constant indices: rw stays in registers)
         }
         return 0;
+    }
+
+    // the bool reader and the LDS-resident Branches as the band before left them (run<true>)
+    WDEV void resume_stream(const uint8_t* stream, uint32_t len, const RowsWalk& rw) {
+        const uint32_t mis = (uint32_t)((uintptr_t)stream & 3);
+        bc.words = reinterpret_cast<const uint32_t*>(stream - mis);
+        bc.first = mis; bc.end = mis + len;
+        bc.vhi = vec(rw.rec->vhi); bc.vlo = vec(rw.rec->vlo); bc.count = (int)vec((uint32_t)rw.rec->count); bc.range = vec(rw.rec->range);
+        bc.wi = rw.rec->wi;
+        bc.raw = bc.fetch(bc.wi);
+        nbins = rw.rec->nbins;
+        LANES(l) {
+            for (int d = l; d < kSignWords; d += 64) sh->sign[d] = rw.lds_save[d];
+            for (int d = l; d < kResDcWords; d += 64) sh->resdc[d] = rw.lds_save[kSignWords + d];
+        }
+        LSYNC();
+    }
+
+    // The resumable form (lep_decode_v4_rows_kernel): run() in bands of MCU rows, one launch per band.  Between two rows of the schedule
+    // a segment's state is its model and summary rings (HBM, where they are), the frame, and what Dec4Resume holds; the sign and
+    // DC-residual Branches, which live in LDS while a launch runs, go to `lds_save` (kSignWords + kResDcWords words) at a band's end.
+    // A fresh record starts as run() does.  The band ends in front of the first schedule index of MCU row (first MCU row decoded in this
+    // launch + band_mcu_rows); band_mcu_rows <= 0: no such end.  The caller has checked that the record is fresh or running.
+    WDEV void run_rows(const ImageDev* image, const SegDev& seg, uint32_t* model_words, NSum* ns, Dec4Shared* shared, const uint8_t* stream,
+                       uint32_t len, Dec4Resume* rec, uint32_t* lds_save, int band_mcu_rows) {
+        RowsWalk rw;
+        rw.rec = rec; rw.lds_save = lds_save;
+        rw.fresh = rec->state == kRowsFresh;
+        rw.idx = 0; rw.stop = 0xffffffffu; rw.total = 0; rw.band = band_mcu_rows;
+        for (int i = 0; i < 3 && i < image->ncomp; ++i) rw.total += (uint32_t)image->height[i] / (uint32_t)image->mcu_rows;
+        for (int c = 0; c < 3; ++c) { rw.top[c] = true; rw.rows_done[c] = 0; }
+        rw.state = kRowsFinished; rw.fail_component = -1; rw.fail_y = -1; rw.fail_x = -1;
+        if (!rw.fresh) {
+            rw.idx = rec->idx;
+            for (int c = 0; c < 3; ++c) { rw.top[c] = ((rec->top >> c) & 1u) != 0; rw.rows_done[c] = rec->rows_done[c]; }
+            if (band_mcu_rows > 0) rw.stop = (rw.idx / rw.total + (uint32_t)band_mcu_rows) * rw.total;
+        }
+        const int code = run<true>(image, seg, model_words, ns, shared, stream, len, &rw);
+        LSYNC();
+        if (rw.state == kRowsRunning) {
+            LANES(l) {
+                for (int d = l; d < kSignWords; d += 64) lds_save[d] = sh->sign[d];
+                for (int d = l; d < kResDcWords; d += 64) lds_save[kSignWords + d] = sh->resdc[d];
+            }
+        }
+#if LEP_ON_GPU
+        if (threadIdx.x != 0) return;
+#endif
+        rec->state = rw.state; rec->code = code;
+        rec->idx = rw.idx; rec->top = (rw.top[0] ? 1u : 0u) | (rw.top[1] ? 2u : 0u) | (rw.top[2] ? 4u : 0u);
+        rec->vhi = bc.vhi; rec->vlo = bc.vlo; rec->count = bc.count; rec->range = bc.range; rec->wi = bc.wi;
+        rec->nbins = nbins;
+        for (int c = 0; c < 3; ++c) rec->rows_done[c] = rw.rows_done[c];
+        rec->fail_component = rw.fail_component; rec->fail_y = rw.fail_y; rec->fail_x = rw.fail_x;
     }
 };
 typedef Dec4WaveT<LEP_DEC4_SCALAR> Dec4Wave;

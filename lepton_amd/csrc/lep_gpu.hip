@@ -164,6 +164,35 @@ __global__ __launch_bounds__(64, WAVES) void lep_decode_v4_kernel(const ImageDev
     bins[seg.slot] = w.nbins;
 }
 
+// The same decoder one band of MCU rows per launch (Dec4WaveT::run_rows; lep_gpu_decode_rows_*): a segment takes up where its record
+// (recs[slot], lds_save[slot]) says the launch before left it; models and rings are reset on a segment's first band only, and a
+// segment that is finished or has failed returns at once.
+constexpr int kRowsLdsWords = lep3::kSignWords + lep3::kResDcWords;
+template <int WAVES, int SCMASK = LEP_DEC4_SCALAR>
+__global__ __launch_bounds__(64, WAVES) void lep_decode_v4_rows_kernel(const ImageDev* __restrict__ images, const SegDev* __restrict__ segs,
+                                                                uint32_t* models, NSum* ns_area, const uint64_t* ns_offsets,
+                                                                const uint8_t* streams, const uint32_t* stream_len, lep4::Dec4Resume* recs,
+                                                                uint32_t* lds_save, int band_mcu_rows) {
+    __shared__ lep4::Dec4Shared sh;
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const SegDev seg = segs[s];
+    lep4::Dec4Resume* rec = recs + seg.slot;
+    const int state = rec->state;
+    if (state != lep4::kRowsFresh && state != lep4::kRowsRunning) return;
+    const ImageDev* img = images + seg.image;
+    uint32_t* model = models + (size_t)s * kModelStride;
+    NSum* ns = ns_area + ns_offsets[s];
+    if (state == lep4::kRowsFresh) {
+        reset_segment_state<lep3::kModelWords>(model, ns, img->ns_total, lane);
+        __syncthreads();
+    }
+    lep4::Dec4WaveT<SCMASK> w;
+#ifdef LEP_PROF
+    w.prof_begin(&g_prof4[s & 8191][0]);
+#endif
+    w.run_rows(img, seg, model, ns, &sh, streams + seg.stream_off, stream_len[seg.slot], rec, lds_save + (size_t)seg.slot * kRowsLdsWords, band_mcu_rows);
+}
+
 
 // ---- the split-phase encoder (lep_enc5.h) -------------------------------------------------------------------------------------
 // walk: one or two wavefronts per segment (count / emit / gather share the code; NW = 2: lep_enc5.h Walk5); LDS: two transposed
@@ -572,6 +601,7 @@ struct lep_gpu {
         W_NS, W_NS_1,
         W_TRIMMED,                  // -- what stays through a trim: from here on
         W_META = W_TRIMMED, W_META_1,   // ImageDev[] | SegDev[] | ns_offsets[] | bins[]
+        W_ROWS, W_ROWS_1,           // a decode session's records: Dec4Resume[] | the segments' LDS-resident Branches (one per arena set)
         W_ENC5_PLANS,               // SegPlan5[] | counts | totals
         W_ENC5_WCHUNKS,             // the stitched writer's records, one per (segment, chunk)
         // host-variant staging
@@ -593,6 +623,16 @@ struct lep_gpu {
     };
     lepbuf::DevBuf<> ws[W_COUNT];
     int cur = 0;                    // the arena set of the launches being set up (lep_gpu_use_arena)
+    // a decode session per arena set (lep_gpu_decode_rows_begin .. _end): the launch it advances band by band
+    struct RowsSession {
+        bool open = false;
+        int nseg = 0, waves = 4;
+        hipStream_t st = nullptr;
+        const ImageDev* d_img = nullptr; const SegDev* d_seg = nullptr; const uint64_t* d_nsoff = nullptr;
+        uint32_t* d_models = nullptr; NSum* d_ns = nullptr;
+        const uint8_t* d_streams = nullptr; const uint32_t* d_stream_len = nullptr;
+        std::vector<lep4::Dec4Resume> h_recs;
+    } rows[2];
     hipEvent_t ev_enc5_done = nullptr;
     uint32_t* d_bins = nullptr;
     std::vector<uint32_t> h_bins;
@@ -663,10 +703,15 @@ static void vmm_destroy(lep_gpu* g) {
 }
 // before an allocation failure is reported: the cached memory no launch that is being set up depends on -- the split-phase
 // encoder's scratch (its launches take the single-kernel encoder when they cannot have it) and the other arena set's models
+static bool session_holds(const lep_gpu* g, int w) {   // the models and rings of an arena set with an open decode session
+    for (int k = 0; k < 2; ++k)
+        if (g->rows[k].open && (w == lep_gpu::W_MODELS + k || w == lep_gpu::W_NS + k)) return true;
+    return false;
+}
 static void release_idle_caches(lep_gpu* g) {
     (void)hipDeviceSynchronize();
     for (int w = 0; w < lep_gpu::W_TRIMMED; ++w)
-        if (w != lep_gpu::W_MODELS + g->cur && w != lep_gpu::W_NS + g->cur) dev_release(g, g->ws[w]);
+        if (w != lep_gpu::W_MODELS + g->cur && w != lep_gpu::W_NS + g->cur && !session_holds(g, w)) dev_release(g, g->ws[w]);
 }
 static int vmm_ensure(lep_gpu* g, Workspace& w, size_t need, bool may_release) {
     lep_gpu::Vmm& V = g->vmm;
@@ -880,13 +925,22 @@ static int upload(lep_gpu* g, void* dst, const void* src, size_t n, hipStream_t 
     return 0;
 }
 
-template <bool DEC>
-static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_segment* segs, int nseg, uint8_t* d_streams,
-                  const uint64_t* stream_offsets, uint32_t* d_stream_len, int32_t* d_status, hipStream_t st) {
-    if (nseg <= 0) return 0;
+// A decode session (lep_gpu_decode_rows_begin .. _end) owns the arena set it was begun on: its models, rings and descriptors carry a
+// half-decoded launch from one advance to the next, so everything else that would set up work in that set is refused until the end.
+static int refuse_if_session(lep_gpu* g, const char* what) {
+    if (!g->rows[g->cur].open) return 0;
+    g->err = std::string(what) + ": arena set " + std::to_string(g->cur) + " belongs to a decode session until lep_gpu_decode_rows_end";
+    return LEP_ASSERTION_FAILURE;
+}
+
+// The front of a coder launch: descriptors derived, the launch order chosen, models / rings / descriptors ensured in the current arena
+// set and the descriptors queued for upload on `st`.
+struct LaunchFront { const ImageDev* d_img; const SegDev* d_seg; const uint64_t* d_nsoff; uint32_t* d_models; NSum* d_ns; };
+static int launch_front(lep_gpu* g, bool dec, const lep_image_desc* images, int nimg, const lep_segment* segs, int nseg,
+                        const uint64_t* stream_offsets, hipStream_t st, LaunchFront* out) {
     std::vector<ImageDev> himg(nimg);
     for (int i = 0; i < nimg; ++i) {
-        int rc = derive_image(images[i], &himg[i], !DEC);
+        int rc = derive_image(images[i], &himg[i], !dec);
         if (rc) return rc;
     }
     std::vector<SegDev> hseg(nseg);
@@ -965,44 +1019,58 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
     g->d_bins = (uint32_t*)(meta + o_bins);
     g->h_bins.assign(nseg, 0);
     g->nstage = 0;
+    out->d_img = (const ImageDev*)(meta + o_img); out->d_seg = (const SegDev*)(meta + o_seg); out->d_nsoff = (const uint64_t*)(meta + o_ns);
+    out->d_models = (uint32_t*)models.p; out->d_ns = (NSum*)ns.p;
+    return 0;
+}
+
+// waves per SIMD the decoder's register allocation is held to for a launch of nseg segments: more resident waves only pay once the
+// batch can fill them (MI355X, 4K corpus: below ~4600 segments the 4-wave build, which does not spill, is faster)
+static int decoder_waves(const lep_gpu* g, int nseg) {
+    // (a launch that is to share the chip with the launch before or behind it -- lep_gpu_expect_company, the batch decompressor's
+    // chunks on two streams -- takes the 64-VGPR build whatever its size: four 128-VGPR wavefronts hold a SIMD's whole register file,
+    // and the other launch's wavefronts could not move into the wave slots they leave empty)
+    if (g->dec_waves) return g->dec_waves;
+    return (nseg > 4608 || (g->dec_company && nseg >= 64)) ? 8 : 4;
+}
+
+template <bool DEC>
+static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_segment* segs, int nseg, uint8_t* d_streams,
+                  const uint64_t* stream_offsets, uint32_t* d_stream_len, int32_t* d_status, hipStream_t st) {
+    if (nseg <= 0) return 0;
+    if (int rc = refuse_if_session(g, DEC ? "decode launch" : "encode launch")) return rc;
+    LaunchFront F;
+    if (int rc = launch_front(g, DEC, images, nimg, segs, nseg, stream_offsets, st, &F)) return rc;
+    Workspace &models = g->ws[lep_gpu::W_MODELS + g->cur], &ns = g->ws[lep_gpu::W_NS + g->cur];
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (DEC) {
 #ifdef LEP_PROF
         { void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_prof4)) == hipSuccess) (void)hipMemsetAsync(p, 0, sizeof(g_prof4), st); }
 #endif
 #define LEP_LAUNCH_DEC4(W)                                                                                                     \
-    hipLaunchKernelGGL((lep_decode_v4_kernel<W>), dim3(nseg), dim3(64), 0, st, (const ImageDev*)(meta + o_img),                  \
-                       (const SegDev*)(meta + o_seg), (uint32_t*)models.p, (NSum*)ns.p, (const uint64_t*)(meta + o_ns), \
-                       d_streams, d_stream_len, d_status, g->d_bins)
-        // more resident waves only pay once the batch can fill them (MI355X, 4K corpus: below ~4600 segments the 4-wave
-        // build, which does not spill, is faster)
-        int waves = g->dec_waves;
-        // (a launch that is to share the chip with the launch before or behind it -- lep_gpu_expect_company, the batch decompressor's
-        // chunks on two streams -- takes the 64-VGPR build whatever its size: four 128-VGPR wavefronts hold a SIMD's whole register file,
-        // and the other launch's wavefronts could not move into the wave slots they leave empty)
-        if (!waves) waves = (nseg > 4608 || (g->dec_company && nseg >= 64)) ? 8 : 4;
+    hipLaunchKernelGGL((lep_decode_v4_kernel<W>), dim3(nseg), dim3(64), 0, st, F.d_img, F.d_seg, (uint32_t*)models.p, (NSum*)ns.p, \
+                       F.d_nsoff, d_streams, d_stream_len, d_status, g->d_bins)
+        const int waves = decoder_waves(g, nseg);
         if (waves >= 8) { g->last_kernel = "lep_decode_v4_kernel<8>"; LEP_LAUNCH_DEC4(8); }
         else { g->last_kernel = "lep_decode_v4_kernel<4>"; LEP_LAUNCH_DEC4(4); }
 #undef LEP_LAUNCH_DEC4
     } else {
 #define LEP_LAUNCH_ENC3(W)                                                                                                     \
-    hipLaunchKernelGGL((lep_encode_v3_kernel<W>), dim3(nseg), dim3(64), 0, st, (const ImageDev*)(meta + o_img),                  \
-                       (const SegDev*)(meta + o_seg), (uint32_t*)models.p, (NSum*)ns.p, (const uint64_t*)(meta + o_ns), \
-                       d_streams, d_stream_len, d_status, g->d_bins)
+    hipLaunchKernelGGL((lep_encode_v3_kernel<W>), dim3(nseg), dim3(64), 0, st, F.d_img, F.d_seg, (uint32_t*)models.p, (NSum*)ns.p, \
+                       F.d_nsoff, d_streams, d_stream_len, d_status, g->d_bins)
         // like the decoder: a launch that cannot fill 8 wavefronts per SIMD takes the 4-wave build (128 VGPRs, no spills)
         int waves = g->enc_waves;
         if (!waves) waves = nseg > 4608 ? 8 : (nseg <= g->enc_pair_max ? 2 : 4);
         bool done = false;
         if (g->enc5_min > 0 && !g->enc_waves && nseg >= g->enc5_min) {   // (LEP_ENC_WAVES asks for one of the single-kernel forms)
-            const int rc = launch_enc5(g, (const ImageDev*)(meta + o_img), (const SegDev*)(meta + o_seg), (const uint64_t*)(meta + o_ns), nseg, d_streams, d_stream_len, d_status, st);
+            const int rc = launch_enc5(g, F.d_img, F.d_seg, F.d_nsoff, nseg, d_streams, d_stream_len, d_status, st);
             if (rc && rc != kEnc5NoMemory) return rc;
             done = rc == 0;
         }
         if (done) {}
         else if (waves == 2) {   // few segments: two wavefronts per segment (producer / bool coder), half the serial chain
             g->last_kernel = "lep_encode_v3x2_kernel";
-            hipLaunchKernelGGL(lep_encode_v3x2_kernel, dim3(nseg), dim3(128), 0, st, (const ImageDev*)(meta + o_img),
-                               (const SegDev*)(meta + o_seg), (uint32_t*)models.p, (NSum*)ns.p, (const uint64_t*)(meta + o_ns),
+            hipLaunchKernelGGL(lep_encode_v3x2_kernel, dim3(nseg), dim3(128), 0, st, F.d_img, F.d_seg, (uint32_t*)models.p, (NSum*)ns.p, F.d_nsoff,
                                d_streams, d_stream_len, d_status, g->d_bins);
         }
         else if (waves >= 8) { g->last_kernel = "lep_encode_v3_kernel<8>"; LEP_LAUNCH_ENC3(8); }
@@ -1131,7 +1199,77 @@ int lep_gpu_decode_device(lep_gpu* g, const lep_image_desc* images, int nimg, co
                         const_cast<uint32_t*>(d_stream_len), d_status, hip_stream ? (hipStream_t)hip_stream : g->stream);
 }
 
-static_assert(sizeof(lep_huff_image) == sizeof(lephuff::HuffImage) && sizeof(lep_huff_segment) == sizeof(lephuff::HuffSegment) &&
+// ---- resumable decode: a launch advanced one band of MCU rows at a time (lep_decode_v4_rows_kernel) -----------------------------------
+// begin = the front of a decode launch + cleared records; advance = one band on the session's stream, waited for, records copied back;
+// end gives the arena set back.  The host only ever reads what a completed launch left behind.
+int lep_gpu_decode_rows_begin(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_segment* segs, int nseg,
+                              const uint8_t* d_streams, const uint64_t* stream_offsets, const uint32_t* d_stream_len, void* hip_stream) {
+    if (!g) return LEP_GPU_ERROR;
+    if (int rc = refuse_if_session(g, "lep_gpu_decode_rows_begin")) return rc;
+    if (nseg <= 0 || nimg <= 0) { g->err = "lep_gpu_decode_rows_begin: nothing to decode"; return LEP_ASSERTION_FAILURE; }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
+    LaunchFront F;
+    if (int rc = launch_front(g, true, images, nimg, segs, nseg, stream_offsets, st, &F)) return rc;
+    Workspace& recs = g->ws[lep_gpu::W_ROWS + g->cur];
+    lepbuf::Layout L;
+    L.add<lep4::Dec4Resume>((size_t)nseg);
+    L.add<uint32_t>((size_t)nseg * kRowsLdsWords);
+    if (int rc = ensure(g, recs, L.bytes())) return rc;
+    HIPCHK(g, hipMemsetAsync(recs.p, 0, L.bytes(), st));   // all zero = fresh
+    lep_gpu::RowsSession& R = g->rows[g->cur];
+    R.nseg = nseg; R.st = st; R.waves = decoder_waves(g, nseg);
+    R.d_img = F.d_img; R.d_seg = F.d_seg; R.d_nsoff = F.d_nsoff; R.d_models = F.d_models; R.d_ns = F.d_ns;
+    R.d_streams = d_streams; R.d_stream_len = d_stream_len;
+    R.h_recs.assign((size_t)nseg, lep4::Dec4Resume());
+    R.open = true;
+    return 0;
+}
+
+int lep_gpu_decode_rows_advance(lep_gpu* g, int band_mcu_rows, lep_decode_progress* progress, int* running) {
+    if (!g) return LEP_GPU_ERROR;
+    lep_gpu::RowsSession& R = g->rows[g->cur];
+    if (!R.open) { g->err = "lep_gpu_decode_rows_advance: no decode session on arena set " + std::to_string(g->cur); return LEP_ASSERTION_FAILURE; }
+    HIPCHK(g, hipSetDevice(g->device));
+    Workspace& ws = g->ws[lep_gpu::W_ROWS + g->cur];
+    lep4::Dec4Resume* d_recs = ws.at<lep4::Dec4Resume>(0);
+    lepbuf::Layout L;
+    L.add<lep4::Dec4Resume>((size_t)R.nseg);
+    uint32_t* d_lds = ws.at<uint32_t>(L.add<uint32_t>((size_t)R.nseg * kRowsLdsWords));
+#define LEP_LAUNCH_ROWS(W)                                                                                                             \
+    hipLaunchKernelGGL((lep_decode_v4_rows_kernel<W>), dim3(R.nseg), dim3(64), 0, R.st, R.d_img, R.d_seg, R.d_models, R.d_ns, R.d_nsoff, \
+                       R.d_streams, R.d_stream_len, d_recs, d_lds, band_mcu_rows)
+    if (R.waves >= 8) { g->last_kernel = "lep_decode_v4_rows_kernel<8>"; LEP_LAUNCH_ROWS(8); }
+    else { g->last_kernel = "lep_decode_v4_rows_kernel<4>"; LEP_LAUNCH_ROWS(4); }
+#undef LEP_LAUNCH_ROWS
+    HIPCHK(g, hipGetLastError());
+    HIPCHK(g, hipMemcpyAsync(R.h_recs.data(), d_recs, (size_t)R.nseg * sizeof(lep4::Dec4Resume), hipMemcpyDeviceToHost, R.st));
+    HIPCHK(g, hipStreamSynchronize(R.st));
+    int still = 0;
+    for (int s = 0; s < R.nseg; ++s) {
+        const lep4::Dec4Resume& r = R.h_recs[(size_t)s];
+        const bool failed = r.state == lep4::kRowsFailed;
+        if (r.state != lep4::kRowsFinished && !failed) ++still;
+        if (!progress) continue;
+        lep_decode_progress& p = progress[s];
+        p.status = r.state == lep4::kRowsFinished ? 0 : (failed ? r.code : -1);
+        for (int c = 0; c < LEP_MAX_COMPONENTS; ++c) p.rows_done[c] = c < 3 ? r.rows_done[c] : 0;
+        p.fail_component = failed ? r.fail_component : -1; p.fail_y = failed ? r.fail_y : -1; p.fail_x = failed ? r.fail_x : -1;
+        p.bins = r.nbins;
+    }
+    if (running) *running = still;
+    return 0;
+}
+
+int lep_gpu_decode_rows_end(lep_gpu* g) {
+    if (!g) return LEP_GPU_ERROR;
+    lep_gpu::RowsSession& R = g->rows[g->cur];
+    if (!R.open) { g->err = "lep_gpu_decode_rows_end: no decode session on arena set " + std::to_string(g->cur); return LEP_ASSERTION_FAILURE; }
+    R.open = false;
+    R.h_recs.clear();
+    return 0;
+}
+
+static_assert(sizeof(lep_huff_image) == sizeof(lephuff::HuffImage) &&sizeof(lep_huff_segment) == sizeof(lephuff::HuffSegment) &&
               sizeof(lep_huff_end) == sizeof(lephuff::HuffEnd) && sizeof(lep_huff_end) == 16, "C ABI mirrors");
 
 int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int nimg, const lep_huff_segment* segs, int nseg,
@@ -1565,6 +1703,9 @@ int lep_gpu_debug_prof(lep_gpu* g, uint64_t* out /* [64][32] */) {
 // give back what the object caches between launches (models, neighbour rings, the split-phase encoder's scratch): all of it
 // is re-acquired by the next launch that needs it.  Waits for the device first.
 int lep_gpu_trim(lep_gpu* g) {
+    // (a trim takes the models and rings of BOTH arena sets: refused while either has a decode session)
+    for (int k = 0; k < 2; ++k)
+        if (g->rows[k].open) { g->err = "lep_gpu_trim / lep_gpu_release_memory: arena set " + std::to_string(k) + " belongs to a decode session until lep_gpu_decode_rows_end"; return LEP_ASSERTION_FAILURE; }
     HIPCHK(g, hipSetDevice(g->device));
     HIPCHK(g, hipDeviceSynchronize());
     for (int w = 0; w < lep_gpu::W_TRIMMED; ++w) dev_release(g, g->ws[w]);
