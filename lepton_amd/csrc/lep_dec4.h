@@ -217,9 +217,17 @@ WDEV uint64_t pair64(uint32_t hi, uint32_t lo) {
     return ((uint64_t)hi << 32) | lo;
 #endif
 }
+// The refill test once per GROUP of bins (LEP_DEC4_REFILL_GROUPS, 0 = one test in front of every bin as before): ensure() refills when
+// fewer than 32 bits are valid (a refill adds 32, the window holds 64), a bin shifts out at most 7, and the decision reads the top 8 --
+// so behind one ensure() four bins may run (32, 25, 18, 11 bits valid in front of them), and behind a bin that had its own ensure() three
+// more.  get() = ensure() + get_raw(); the callers that code a group (unary_from, residual, tree, the sign bin with a short residual)
+// say ensure() once and get_raw() per bin.  The values decoded do not depend on when a dword enters the window.
+#ifndef LEP_DEC4_REFILL_GROUPS
+#define LEP_DEC4_REFILL_GROUPS 1
+#endif
 struct BoolDec4 {
     uint32_t vhi, vlo;      // top-aligned window
-    int count;              // valid bits - 8
+    int count;              // valid bits - 8; >= 24 behind ensure()
     uint32_t range;
     const uint32_t* words;  // aligned dword that holds stream byte 0
     uint32_t first, end;    // stream bytes live at byte offsets [first, end) from `words`
@@ -246,16 +254,25 @@ struct BoolDec4 {
         vhi = vec(0); vlo = vec(0); count = (int)vec((uint32_t)-8); range = vec(255); wi = 0;
         raw = fetch(0);
         refill();
-        get(128);
+        ensure();   // (a stream that starts inside its first dword brings fewer than 32 bits with it: the one place where a second refill follows the first)
+        get_raw(128);
     }
+    WDEV void ensure() {
+#if LEP_DEC4_REFILL_GROUPS
+        if (ucond(count < 24)) refill();
+#endif
+    }
+    WDEV uint32_t get(uint32_t prob) { ensure(); return get_raw(prob); }
     // returns the decoded bit (0 / 1) as a uniform vector value
-    WDEV uint32_t get(uint32_t prob) {
+    WDEV uint32_t get_raw(uint32_t prob) {
 #if LEP_ON_GPU
         const uint32_t split = 1 + (__umul24(range - 1, prob) >> 8);
 #else
         const uint32_t split = 1 + (((range - 1) * prob) >> 8);
 #endif
+#if !LEP_DEC4_REFILL_GROUPS
         if (ucond(count < 0)) refill();
+#endif
         const uint32_t big = split << 24;
         const uint32_t bit = vhi >= big ? 1u : 0u;
         const uint32_t d = vhi - big;
@@ -306,9 +323,21 @@ struct BoolDec4S {
         ++b.wi;
         b.raw = b.fetch(b.wi);
     }
+    WDEV void ensure(BoolDec4& b) {
+#if LEP_DEC4_REFILL_GROUPS
+        if (count < 24) refill(b);
+#else
+        (void)b;
+#endif
+    }
+    WDEV uint32_t get(BoolDec4& b, uint32_t pk) { ensure(b); return get_raw(b, pk); }
     // prob in the low byte of `pk` (the bytes above it are the caller's next probabilities and fall off the shift)
-    WDEV uint32_t get(BoolDec4& b, uint32_t pk) {
+    WDEV uint32_t get_raw(BoolDec4& b, uint32_t pk) {
+#if !LEP_DEC4_REFILL_GROUPS
         if (count < 0) refill(b);
+#else
+        (void)b;
+#endif
 #ifdef LEP_DEC4_RANGE_LOW
         const uint32_t split = 1 + (((range - 1) * (pk & 255u)) >> 8);
         const uint32_t big = split << 24;
@@ -366,6 +395,11 @@ struct BoolDec4S {
 // which serial rounds run on the scalar unit: 1 = non-zero count tree, 2 = 7x7 interior, 4 = edges, 8 = DC
 #ifndef LEP_DEC4_SCALAR
 #define LEP_DEC4_SCALAR 2   // measured (1024 x 4K, MI355X, profiles/r02m_*): 0: 1232 ms, 2: 1204, 3: 1212, 11: 1226, 7: 1400, 15: 1440
+#endif
+
+// owners' updates with one Branch word per lane (adapt_words below); 0 = adapt_group on whole groups everywhere, the form before (A/B builds)
+#ifndef LEP_DEC4_WORD_PER_LANE
+#define LEP_DEC4_WORD_PER_LANE 1
 #endif
 
 // A segment's resume record (Dec4WaveT::run_rows): all that a segment carries from one band's launch to the next beside its model, its
@@ -479,6 +513,9 @@ struct Dec4WaveT {
         static WDEV uint32_t U(uint32_t x) { return SC ? uni(x) : vec(x); }
         static WDEV bool is(bool c) { return SC ? c : ucond(c); }
         WDEV uint32_t get(uint32_t prob) { return SC ? s.get(w.bc, prob) : w.bc.get(prob); }
+        // a group of bins: ensure() once, then up to four get_raw() (three behind a get())
+        WDEV void ensure() { if (SC) s.ensure(w.bc); else w.bc.ensure(); }
+        WDEV uint32_t get_raw(uint32_t prob) { return SC ? s.get_raw(w.bc, prob) : w.bc.get_raw(prob); }
         WDEV uint32_t bupd(uint32_t word, uint32_t obs) {
             if (!SC) return bupd_u(word, obs, w.sh->inv24);
             const uint32_t w2 = word + 1u + obs * 255u;
@@ -503,12 +540,15 @@ struct Dec4WaveT {
             return bit;
         }
         // unary bins k.. of one packed exponent group (k = first bin to decode); returns the number of ones from bin 0 (<= 4)
-        template <int K>
+        // ENSURE = false: the caller's bin in front of these had the refill test (K >= 1: at most three bins follow it)
+        template <int K, bool ENSURE = true>
         WDEV int unary_from(uint32_t pk) {
-            if (K <= 0) { if (!is(get(pk & 255) != 0)) return 0; }
-            if (K <= 1) { if (!is(get((pk >> 8) & 255) != 0)) return 1; }
-            if (K <= 2) { if (!is(get((pk >> 16) & 255) != 0)) return 2; }
-            if (!is(get(pk >> 24) != 0)) return 3;
+            static_assert(ENSURE || K >= 1, "four bins need a refill test of their own");
+            if (ENSURE) ensure();
+            if (K <= 0) { if (!is(get_raw(pk & 255) != 0)) return 0; }
+            if (K <= 1) { if (!is(get_raw((pk >> 8) & 255) != 0)) return 1; }
+            if (K <= 2) { if (!is(get_raw((pk >> 16) & 255) != 0)) return 2; }
+            if (!is(get_raw(pk >> 24) != 0)) return 3;
             return 4;
         }
         WDEV int unary_tail(uint32_t gbase) {   // exponent bins 8..10 straight from HBM (|v| >= 128: rare)
@@ -518,27 +558,32 @@ struct Dec4WaveT {
             return i;
         }
         // residual bits b..0 (b <= 3) of |v| from the packed probabilities of the residual group (word i = bit i)
+        // Called behind a bin that had the refill test (the sign bin, or the last bin coded straight from HBM): up to three bins go with
+        // that test, four take one of their own
         WDEV uint32_t residual(uint32_t pk, int b, uint32_t v) {
-            if (b >= 3) v |= get(pk >> 24) << 3;
-            if (b >= 2) v |= get((pk >> 16) & 255) << 2;
-            if (b >= 1) v |= get((pk >> 8) & 255) << 1;
-            if (b >= 0) v |= get(pk & 255);
+            if (b >= 3) { ensure(); v |= get_raw(pk >> 24) << 3; }
+            if (b >= 2) v |= get_raw((pk >> 16) & 255) << 2;
+            if (b >= 1) v |= get_raw((pk >> 8) & 255) << 1;
+            if (b >= 0) v |= get_raw(pk & 255);
             return v;
         }
         // a LEVELS-level binary tree decoded MSB first; the d-th decoded level has 2^d nodes stored as whole groups owned
         // by lanes base + first(d) .., first = 0,1,2,3,5,9 (1,1,1,2,4,8 groups per level); levels 0..2 read fixed lanes
         template <int LEVELS>
         WDEV int tree(const uint32_t* PK, int base) {
+            static_assert(LEVELS <= 6, "one refill test per three levels");
             uint32_t pk = U(lepwave::wave_read(PK, base));
-            uint32_t n = get(pk & 255);
+            ensure();
+            uint32_t n = get_raw(pk & 255);
             pk = U(lepwave::wave_read(PK, base + 1));
-            n = (n << 1) | get((pk >> (n * 8)) & 255);
+            n = (n << 1) | get_raw((pk >> (n * 8)) & 255);
             pk = U(lepwave::wave_read(PK, base + 2));
-            n = (n << 1) | get((pk >> (n * 8)) & 255);
+            n = (n << 1) | get_raw((pk >> (n * 8)) & 255);
+            if (LEVELS > 3) ensure();
 #pragma unroll
             for (int d = 3; d < LEVELS; ++d) {
                 pk = U(lepwave::wave_read(PK, base + (1 << (d - 2)) + 1 + (int)uni(n >> 2)));
-                n = (n << 1) | get((pk >> ((n & 3) * 8)) & 255);
+                n = (n << 1) | get_raw((pk >> ((n & 3) * 8)) & 255);
             }
             return (int)uni(n);
         }
@@ -639,6 +684,50 @@ struct Dec4WaveT {
 #undef LEP_SLOT
     }
 
+    // ---- the same with ONE Branch word per lane ---------------------------------------------------------------------------------
+    // adapt_group spends a pass of all 64 lanes on each word slot of a group register while three or four lanes hold a used word in that
+    // slot (counted on the bench's images: 21.7 passes per block adapt 75 words), and a compare + ballot on every slot it may skip.  A
+    // round knows, once its serial code is through, which word of which lane's group each coded bin went to; it hands every such word to
+    // a lane of its own (regroup: one ds_bpermute_b32 per slot register and a select on the lane's slot -- LDS instructions are free
+    // at this kernel's occupancy), and ONE straight-line pass adapts them all: adapt_group's slot body once, one ballot for
+    // the lanes whose count wrapped.  The adapting lane stores its word itself (a dword at the group's address + slot).
+    // No two lanes of a pass hold the same word: a pass's lanes stand for distinct (position, word) pairs, and a position is coded under
+    // one context.  use / obs are 0 or 1 per lane; a lane with use = 0 keeps its word.
+    WDEV void adapt_words(uint32_t* W, const int* use, const int* obs) {
+        const uint32_t* inv = sh->inv24;
+        LV(int, wrapped); LV(uint32_t, oldw);
+        LANES(l) {
+            const uint32_t w = L(W);
+            const uint32_t u = (uint32_t)L(use), u1 = u & (uint32_t)L(obs), u0 = u & ~(uint32_t)L(obs);
+            const uint32_t w2 = w + (u0 | (u1 << 8));
+            const uint32_t f = w2 & 255u, t = (w2 >> 8) & 255u;
+            const uint32_t p = mul24_low(f, inv[f + t]);   // f * 2^24 / (f + t): the probability is bits 16..23
+            const uint32_t m = mul24(u, 0xff0000u);
+            L(oldw) = w; L(wrapped) = (f < t ? f : t) + (u ^ 1u) == 0;   // a bumped count wrapped
+            L(W) = (p & m) | (w2 & ~m);
+        }
+        if (lepwave::wave_ballot(wrapped)) {
+            LANES(l) if (L(wrapped)) L(W) = bupd_t(L(oldw), (uint32_t)L(obs), inv);
+        }
+    }
+    // lane l of out = word slot[l] (0..3) of the group that lane src[l] holds
+    static WDEV void regroup(const U4* G, const int* src, const int* slot, uint32_t* out) {
+        LV(uint32_t, c0); LV(uint32_t, c1); LV(uint32_t, c2); LV(uint32_t, c3);
+        LV(uint32_t, g0); LV(uint32_t, g1); LV(uint32_t, g2); LV(uint32_t, g3);
+        LANES(l) { L(c0) = L(G).x; L(c1) = L(G).y; L(c2) = L(G).z; L(c3) = L(G).w; }
+        lepwave::wave_gather(c0, src, g0); lepwave::wave_gather(c1, src, g1);
+        lepwave::wave_gather(c2, src, g2); lepwave::wave_gather(c3, src, g3);
+        LANES(l) { const int k = L(slot); L(out) = k == 0 ? L(g0) : (k == 1 ? L(g1) : (k == 2 ? L(g2) : L(g3))); }
+    }
+    // the words (group G and its address adr in lane src, word slot) one per lane, adapted where `use`, stored by the adapting lanes
+    WDEV void adapt_regrouped(const U4* G, const uint32_t* adr, const int* src, const int* slot, const int* use, const int* obs) {
+        LV(uint32_t, Wd); LV(uint32_t, ad);
+        regroup(G, src, slot, Wd);
+        lepwave::wave_gather(adr, src, ad);
+        adapt_words(Wd, use, obs);
+        LANES(l) if (L(use)) model[L(ad) + (uint32_t)L(slot)] = L(Wd);
+    }
+
     // ---- round 1: the 6-bit count of interior non-zeros (model.hh:463-485) --------------------------------------------
     WDEV int round_nz(int nzbin_ctx) {
         LEP_MARK("nz_prefetch");
@@ -662,6 +751,16 @@ struct Dec4WaveT {
             LEP_BINS(nbins += 6);
         }
         LEP_MARK("nz_update"); LEP_PRIO_PARALLEL();
+#if LEP_DEC4_WORD_PER_LANE
+        {   // lane t < 6: the one word of tree level 5 - t that nz's prefix selects (groups of a level: lanes 0,1,2,3,5,9 ..)
+            LV(int, src); LV(int, slot); LV(int, use); LV(int, ob);
+            LANES(l) {
+                const int t = l < 6 ? l : 0, i = 5 - t, prefix = nz >> (i + 1);
+                L(src) = ((0x953210 >> (4 * t)) & 15) + (prefix >> 2); L(slot) = prefix & 3; L(use) = l < 6; L(ob) = (nz >> i) & 1;
+            }
+            adapt_regrouped(W0, a0, src, slot, use, ob);
+        }
+#else
         LV(int, u0); LV(int, b0);
         LANES(l) {
             int u = 0, b = 0;
@@ -674,6 +773,7 @@ struct Dec4WaveT {
         }
         adapt_group<3>(W0, u0, b0);
         LANES(l) if (L(u0)) st4(model + L(a0), L(W0));
+#endif
         return nz;
     }
 
@@ -684,7 +784,10 @@ struct Dec4WaveT {
         Dec4Shared& S = *sh;
         LEP_MARK("77_prefetch");
         const int zz0 = zz_io, left0 = left_io, nb0 = nzbin_of(left0);
-        LV(U4, W0); LV(U4, W1); LV(uint32_t, a0); LV(uint32_t, a1); LV(uint32_t, PK0); LV(uint32_t, PK1); LV(int, ok);
+        LV(U4, W0); LV(U4, W1); LV(uint32_t, a0); LV(uint32_t, a1); LV(uint32_t, PK0); LV(uint32_t, PK1);
+#if !LEP_DEC4_WORD_PER_LANE
+        LV(int, ok);
+#endif
         LANES(l) {
             const int pi = l & 15, cand = l >> 4, p = zz0 + pi, nb = nb0 - cand;
             uint32_t adr0 = 0, adr1 = 0, pk0 = 0, pk1 = 0;
@@ -698,7 +801,10 @@ struct Dec4WaveT {
                 L(W1) = ld4(model + adr1); pk1 = pack_probs(L(W1));
 
             }
-            L(a0) = adr0; L(a1) = adr1; L(PK0) = pk0; L(PK1) = pk1; L(ok) = valid;
+            L(a0) = adr0; L(a1) = adr1; L(PK0) = pk0; L(PK1) = pk1;
+#if !LEP_DEC4_WORD_PER_LANE
+            L(ok) = valid;
+#endif
         }
         LSYNC();
         // ---- serial (uniform vector) -----------------------------------------------------------------------------
@@ -730,7 +836,7 @@ struct Dec4WaveT {
                 pi = lane - 16 * cand;
                 if (!found) break;   // the window is exhausted
                 zz = zz0 + pi;
-                int len = sr.template unary_from<1>(pkv);   // bin 0 was a one: 1..4
+                int len = sr.template unary_from<1, false>(pkv);   // bin 0 was a one: 1..4
                 if (len == 4) {
                     // exponent words 4..7 (|v| >= 8: 5 % of the interior non-zeros) are not prefetched -- that third of the
                     // round's traffic was almost all waste; the serial code reads the group when it gets there, the owner
@@ -769,6 +875,32 @@ struct Dec4WaveT {
         LANES(l) L(nzw) = l < 16 && zz0 + l < zz && S.here[zz0 + l] != 0;
         const uint32_t nzmask = (uint32_t)lepwave::wave_ballot(nzw);
         LV(int, u0); LV(int, b0); LV(int, u1); LV(int, b1); LV(int, u2); LV(int, b2);
+#if LEP_DEC4_WORD_PER_LANE
+        // lane = pi + 16 * slot: word `slot` of position pi's exponent group (then of its residual group), which the lane of the one
+        // candidate in force at pi holds; that lane is also where u2 / b2 (exponent words 4..7, re-read on demand) are set.
+        // (No test of the source lane's `valid`: the candidate in force at a visited position is nzbin(left_at) with left0 - pi <= left_at
+        // <= nzhi(that bin), which is the prefetch condition, and the serial loop ends before a candidate >= LEP_DEC4_CANDS is coded.)
+        LV(int, src); LV(int, slot);
+        LANES(l) {
+            int s = l, ua = 0, oa = 0, ub = 0, ob = 0, uc = 0, bcc = 0;
+            const int pi = l & 15, k = l >> 4, p = zz0 + pi;
+            if (p < zz) {
+                const int left_at = left0 - __builtin_popcount(nzmask & ((1u << pi) - 1));
+                const int c = left_at > 0 ? nb0 - (int)S.nzbin[left_at] : LEP_DEC4_CANDS;
+                if (c < LEP_DEC4_CANDS) {
+                    const int cf = S.here[p];
+                    const int v = cf < 0 ? -cf : cf, len = bitlen((uint32_t)v);
+                    s = pi + 16 * c;
+                    ua = k <= len; oa = len != k;                 // exponent word k: bins 0..len, the bin of word len is the zero
+                    ub = k <= len - 2; ob = (v >> k) & 1;         // residual word k = bit k of |v|, bits len-2..0 are coded
+                    if (c == k) mask_exp(4, len, uc, bcc);
+                }
+            }
+            L(src) = s; L(slot) = k; L(u0) = ua; L(b0) = oa; L(u1) = ub; L(b1) = ob; L(u2) = uc; L(b2) = bcc;
+        }
+        adapt_regrouped(W0, a0, src, slot, u0, b0);
+        if (lepwave::wave_ballot(u1)) adapt_regrouped(W1, a1, src, slot, u1, b1);
+#else
         LANES(l) {
             int ua = 0, ba = 0, ub = 0, bb = 0, uc = 0, bcc = 0;
             const int pi = l & 15, cand_l = l >> 4, p = zz0 + pi;
@@ -790,6 +922,7 @@ struct Dec4WaveT {
             if (L(u0)) st4(model + L(a0), L(W0));
             if (L(u1)) st4(model + L(a1), L(W1));
         }
+#endif
         if (lepwave::wave_ballot(u2)) {   // exponent words 4..7: re-read by the owner (rare in the interior)
             LV(U4, W2);
             LANES(l) if (L(u2)) L(W2) = ld4(model + L(a0) + kGS);
@@ -902,7 +1035,7 @@ struct Dec4WaveT {
                 if (SR::is(sr.get(pkv & 255) != 0)) {
                     const int j = 7 - step;
                     const int coord = horizontal ? j + 1 : (j + 1) * 8;
-                    int len = sr.template unary_from<1>(pkv);
+                    int len = sr.template unary_from<1, false>(pkv);
                     if (len == 4) {
                         len = 4 + sr.template unary_from<0>(SR::U(pack_probs(vload4(model + ctx4_expx(ci, left, horizontal ? j : j + 7, (int)((info >> 24) & 15)) + kGS))));
                         if (len == 8) len = sr.unary_tail(ctx4_expx(ci, left, horizontal ? j : j + 7, (int)((info >> 24) & 15)));
@@ -951,7 +1084,11 @@ struct Dec4WaveT {
         const uint64_t em = lepwave::wave_ballot(enz);
         const uint32_t mh = (uint32_t)(em >> 50) & 0x7f, mv = (uint32_t)(em >> 57) & 0x7f;
         const int neh = ne[0], nev = ne[1];
-        LV(int, u0); LV(int, b0); LV(int, u1); LV(int, b1); LV(int, u2); LV(int, b2);
+        // owners' masks: exponent words 4..7 (u1, re-read on demand) and the residual words (u2); the old form also words 0..3 and the trees (u0)
+        LV(int, u1); LV(int, b1); LV(int, u2); LV(int, b2);
+#if !LEP_DEC4_WORD_PER_LANE
+        LV(int, u0); LV(int, b0);
+#endif
         LANES(l) {
             int ua = 0, ba = 0, ub = 0, bb = 0, uc = 0, bcc = 0;
             if (l < 56) {
@@ -961,18 +1098,52 @@ struct Dec4WaveT {
                 if (left_at == n) {   // n >= 1: the position was visited with n non-zeros left
                     const int cf = S.here[(e ? 57 : 50) + j];
                     const int v = cf < 0 ? -cf : cf, len = bitlen((uint32_t)v);
+#if !LEP_DEC4_WORD_PER_LANE
                     mask_exp(0, len, ua, ba);
+#endif
                     mask_exp(4, len, ub, bb);
                     mask_res(imin(len - 2, (int)S.thr[e ? (j + 1) * 8 : j + 1] - 1), v, uc, bcc);
                 }
-            } else if (l < 62) {
+            }
+#if !LEP_DEC4_WORD_PER_LANE
+            else if (l < 62) {
                 const int e = l >= 59 ? 1 : 0, lv = l - 56 - 3 * e;
                 mask_tree(2 - lv, 0, e ? nev : neh, ua, ba);
             }
-            L(u0) = ua; L(b0) = ba; L(u1) = ub; L(b1) = bb; L(u2) = uc; L(b2) = bcc;
+            L(u0) = ua; L(b0) = ba;
+#else
+            (void)ua; (void)ba;
+#endif
+            L(u1) = ub; L(b1) = bb; L(u2) = uc; L(b2) = bcc;
         }
+#if LEP_DEC4_WORD_PER_LANE
+        {   // exponent words 0..3 of the 14 positions on lanes 4 * (e * 7 + j) + slot, from the one combo lane the position was coded under;
+            // lanes 56..61: the word of its tree level that the count's prefix selects.  (Exponent words 4..7 and the residual words keep
+            // their owners' form below: u1 / u2.)
+            LV(int, src); LV(int, slot); LV(int, use); LV(int, ob);
+            LANES(l) {
+                int s = l, k = l & 3, u = 0, o = 0;
+                if (l < 56) {
+                    const int q = l >> 2, e = q >= 7 ? 1 : 0, j = q - 7 * e;
+                    const int left_at = (e ? nev : neh) - __builtin_popcount((e ? mv : mh) & ((1u << j) - 1));
+                    if (left_at >= 1 && left_at <= 7 - j) {   // visited, and not on the path that codes straight from HBM
+                        const int cf = S.here[(e ? 57 : 50) + j];
+                        const int v = cf < 0 ? -cf : cf, len = bitlen((uint32_t)v);
+                        s = e * 28 + ((j * (15 - j)) >> 1) + left_at - 1;   // combo_base(j) = j * (15 - j) / 2
+                        u = k <= len; o = len != k;
+                    }
+                } else if (l < 62) {
+                    const int e = l >= 59 ? 1 : 0, i = 2 - (l - 56 - 3 * e), value = e ? nev : neh;
+                    k = (value >> (i + 1)) & 3; u = 1; o = (value >> i) & 1;
+                }
+                L(src) = s; L(slot) = k; L(use) = u; L(ob) = o;
+            }
+            adapt_regrouped(W0, a0, src, slot, use, ob);
+        }
+#else
         adapt_group<3>(W0, u0, b0);
         LANES(l) if (L(u0)) st4(model + L(a0), L(W0));
+#endif
         if (lepwave::wave_ballot(u1)) {
             LANES(l) if (L(u1)) L(W1) = ld4(model + L(a0) + kGS);   // read on demand by the serial code: the owner re-reads it
             adapt_group<0>(W1, u1, b1);
@@ -1006,8 +1177,9 @@ struct Dec4WaveT {
             len += sr.template unary_from<0>(SR::U(lepwave::wave_read(PK0, 1)));
             if (len == 8) {
                 uint32_t pk = SR::U(lepwave::wave_read(PK0, 2));
+                sr.ensure();
 #pragma nounroll
-                for (; len < 11; ++len) { if (!SR::is(sr.get(pk & 255) != 0)) break; pk >>= 8; }
+                for (; len < 11; ++len) { if (!SR::is(sr.get_raw(pk & 255) != 0)) break; pk >>= 8; }
             }
         }
         LEP_BINS(nbins += (uint32_t)(len ? 2 * len + 1 - (len == 11) : 1));
@@ -1030,8 +1202,29 @@ struct Dec4WaveT {
         LSYNC();
         // owners: exponent groups (lanes 0..2), residual Branches (lanes 3..12)
         LEP_MARK("dc_update"); LEP_PRIO_PARALLEL();
-        LV(uint32_t, VV); LV(int, u0); LV(int, b0);
+        LV(uint32_t, VV);
         LANES(l) L(VV) = v;   // uniform -> per lane (identity on the GPU)
+#if LEP_DEC4_WORD_PER_LANE
+        {   // lanes 0..10: exponent word l (group l / 4 of lanes 0..2); lanes 11..20: the residual Branch of bit l - 11 (lanes 3..12 hold them)
+            LV(int, src); LV(int, slot); LV(int, use); LV(int, ob); LV(uint32_t, Wd); LV(uint32_t, ad); LV(uint32_t, rg);
+            LANES(l) {
+                int s = l, k = 0, u = 0, o = 0;
+                if (l < 11) { s = l >> 2; k = l & 3; u = l <= len; o = len != l; }
+                else if (l < 21) { s = l - 8; u = l - 11 <= len - 2; o = (int)((L(VV) >> (l - 11)) & 1u); }
+                L(src) = s; L(slot) = k; L(use) = u; L(ob) = o;
+            }
+            regroup(W0, src, slot, Wd);
+            lepwave::wave_gather(RW, src, rg);
+            lepwave::wave_gather(a0, src, ad);
+            LANES(l) if (l >= 11) L(Wd) = L(rg);
+            adapt_words(Wd, use, ob);
+            LANES(l) if (L(use)) {
+                if (l < 11) model[L(ad) + (uint32_t)L(slot)] = L(Wd);
+                else S.resdc[a * 12 + (l - 11)] = L(Wd);
+            }
+        }
+#else
+        LV(int, u0); LV(int, b0);
         LANES(l) {
             int u = 0, b = 0;
             if (l < 3) mask_exp(l * 4, len, u, b);
@@ -1042,6 +1235,7 @@ struct Dec4WaveT {
             if (L(u0)) st4(model + L(a0), L(W0));
             if (l >= 3 && l < 13 && l - 3 <= len - 2) S.resdc[a * 12 + (l - 3)] = bupd_t(L(RW), (L(VV) >> (l - 3)) & 1u, S.inv24);
         }
+#endif
         LSYNC();
     }
 

@@ -145,6 +145,16 @@ WDEV uint32_t wave_read(const uint32_t* v, int src) {
 #endif
 }
 
+// lane l of out = lane src[l] of v (src per lane, taken modulo 64; several lanes may name the same source): one ds_bpermute_b32, an LDS
+// instruction that uses no LDS space.  out may not be v.
+WDEV void wave_gather(const uint32_t* v, const int* src, uint32_t* out) {
+#if LEP_ON_GPU
+    out[0] = (uint32_t)__builtin_amdgcn_ds_bpermute(src[0] << 2, (int)v[0]);
+#else
+    for (int i = 0; i < 64; ++i) out[i] = v[src[i] & 63];
+#endif
+}
+
 // lane `dst` (wave-uniform) of v takes `value` (wave-uniform).  (A compare and a select: this compiler has no builtin for
 // v_writelane_b32, and on gfx9 the instruction may name one scalar register only -- lane and value would have to share it or go through m0.)
 WDEV void wave_write(uint32_t* v, int dst, uint32_t value) {
