@@ -184,6 +184,16 @@ typedef struct lep_huff_end {
  * The call copies its arrays before it returns and does not wait for the stream. */
 int lep_gpu_huffman_encode_device(lep_gpu *g, const lep_huff_image *images, int nimg, const lep_huff_segment *segs, int nseg,
                                   uint8_t *d_out, uint32_t *d_out_len, lep_huff_end *d_ends, void *hip_stream);
+/* Concatenate n byte runs that lie apart in device memory (lep_pack.h: a prefix-sum kernel of one workgroup, a copy kernel of one
+ * wavefront per run that stores whole dwords to the aligned destination, byte heads and tails).  Run i is d_len[i] bytes at
+ * d_src + src_off[i]; src_off is a host array that the call copies, d_len is device memory.  The runs go to d_dst back to back, in order;
+ * sources and destinations may be aligned in any way.  d_dst_off[0..n] (device) receives the exclusive prefix sum of the lengths,
+ * d_dst_off[n] the total; nothing behind d_dst + d_dst_off[n] is written.  A total beyond d_dst_cap copies nothing, and d_dst_off[n] still
+ * holds the true total.  Enqueues on hip_stream and returns.  n <= 16384.  Its scratch is the current arena set's own and no decode
+ * session's: it may be called while a session is open on that set. */
+int lep_gpu_pack_device(lep_gpu *g, const uint8_t *d_src, const uint64_t *src_off, const uint32_t *d_len, int n,
+                        uint8_t *d_dst, uint64_t d_dst_cap, uint64_t *d_dst_off, void *hip_stream);
+int lep_gpu_stream_pack(lep_gpu *g);   /* 1: lep_decompress_batch_stream packs a band's bytes before it fetches them; LEP_STREAM_PACK=0 when the codec is made: 0 */
 /* The same for PROGRESSIVE files (BASELINE.json configs[4]; replaces the scan loop of recode_jpeg, src/lepton/jpgcoder.cc:3309-3716,
  * with encode_dc_prg_*, encode_ac_prg_fs / _sa, encode_eobrun, encode_crbits :4991-5400): every scan of a progressive file is a
  * function of the finished frame alone, so its bytes (FF00-stuffed, restart markers included) are written to d_out +
@@ -407,6 +417,8 @@ int lep_file_recode(lep_file *f, lep_bytes *out);
  * eligible (*gpu_ok = 1), fills the image / per-segment parameters (blocks[], image index and out_off are the caller's to
  * set; out_cap is the segment's byte bound); _finish glues header, the segments' scan bytes and the trailer together. */
 int lep_file_recode_plan(lep_file *f, lep_huff_image *image, lep_huff_segment *segs, int *nseg, int *gpu_ok);
+/* after _plan: the bytes in front of the scan, as _finish will write them (they stay the file's) */
+int lep_file_recode_head(const lep_file *f, const uint8_t **data, size_t *len);
 /* ends: the kernel's per-segment end states (NULL: only the byte counts are held against the hand-offs) */
 int lep_file_recode_finish(lep_file *f, const lep_bytes *seg_bytes, const lep_huff_end *ends, int nseg, lep_bytes *out);
 /* progressive files: _plan fills the image and up to `cap` scan descriptors (out_cap / corr_cap = what each scan may need;
@@ -512,6 +524,38 @@ int lep_compress_batch_slices(lep_gpu *g, const lep_bytes *jpgs, const lep_slice
                               const lep_batch_options *opt, lep_batch_stats *stats);
 int lep_decompress_batch(lep_gpu *g, const lep_bytes *leps, int n, lep_bytes *outs, int32_t *status,
                          const lep_batch_options *opt, lep_batch_stats *stats);
+/* lep_decompress_batch with every file's bytes handed to `sink` as they become final.  The files lep_decompress_stream streams (one whole
+ * baseline file, one interleaved scan of two or three components, not truncated, not chained, taken by the split re-coder) are decoded in
+ * sessions (lep_gpu_decode_rows_*) of at most LEP_STREAM_SESSION_FILES files (environment, default 64) and 16384 thread segments, one session
+ * after another: `begin` takes all files of a session as one launch, each file's header bytes go out before the first advance, and after
+ * every advance of band_mcu_rows MCU rows (<= 0: one advance) ONE lep_gpu_huffman_encode_device launch writes the rows every segment
+ * completed -- each segment from the end state of its band before, appended to its slot --, lep_gpu_pack_device moves the new bytes back to
+ * back, and two copies bring them down (LEP_STREAM_PACK=0: one copy per segment).  Only scan bytes cross PCIe: frames and streams are device
+ * memory of the call.  A file's front segment goes out as it comes, a later segment's bytes once the segments in front of it are complete.
+ * At the end lep_file_recode_finish's checks run over the segments' bytes and end states and supply the tail; what went out must be the
+ * front of that result (else LEP_ASSERTION_FAILURE).  A file whose writer outgrew its byte bound, or whose finish does not succeed (declined, or a
+ * hand-off check that fails: any non-zero answer, as in lep_decompress_stream, so that exit codes stay lep_decompress's -- a check that failed on
+ * good data would show only as frame_bytes_down > 0), has its frame
+ * downloaded (stats->frame_bytes_down) and is finished by the host re-coder under the same check.  Every other file of the call goes through
+ * ONE lep_decompress_batch call, after the sessions, and gets one sink call.
+ * For every file with status[i] == 0 the pieces given to sink(user, i, ...) concatenate to what lep_decompress returns; status[i] is
+ * lep_decompress's exit code.  A file that fails leaves the others untouched; what it has sunk by then are bytes of rows in front of the
+ * failing block.  != 0 from the sink: that file's receiver is gone -- its remaining pieces are dropped, status[i] = LEP_OS_ERROR, the others go on.
+ * Workspaces: a session holds the models, rings, descriptors and records of its arena set (coder launches and a second `begin` on that set are
+ * refused); the scan writers', the scan decoders' and the pack kernels' workspaces of the same set stay usable, and this call uses them.
+ * Sessions run one after another and do not overlap chunks as lep_decompress_batch does: the call buys time to first byte with throughput. */
+typedef int (*lep_batch_sink)(void *user, int file, const uint8_t *data, size_t len);
+typedef struct lep_batch_stream_stats {
+    int32_t  files_streamed, files_whole;            /* through a session / through lep_decompress_batch, one piece */
+    int32_t  sessions, advances, writer_launches;
+    uint64_t scan_bytes_down, frame_bytes_down;      /* PCIe, device -> host */
+    int32_t  files_first_scan_byte_before_last_advance;   /* streamed files whose first scan byte reached the sink before the last advance their
+                                                             front segment took part in */
+    double   wall_s, first_piece_s;                  /* first_piece_s: first piece of any file that holds scan bytes */
+} lep_batch_stream_stats;
+int lep_decompress_batch_stream(lep_gpu *g, const lep_bytes *leps, int n, int band_mcu_rows,
+                                lep_batch_sink sink, void *user, int32_t *status,
+                                const lep_batch_options *opt, lep_batch_stream_stats *stats);
 /* the chunking lep_compress_batch will apply: file_bytes[i] / frame_bytes[i] (lep_jpeg_peek_frame_bytes; 0 = not a usable file)
  * -> chunk k holds files [chunk_first[k], chunk_first[k + 1]); returns the number of chunks (cap = entries of chunk_first) */
 int lep_batch_plan(const size_t *file_bytes, const size_t *frame_bytes, int n, const lep_batch_options *opt, int *chunk_first, int cap);
@@ -542,6 +586,13 @@ void lep_batch_debug_poison(int value);
  * -maxchildren's part (further clients wait in the listen backlog).  One server per GPU: run one process per device. */
 typedef int (*lep_serve_process_fn)(void *user, int kind /* 0: JPEG -> .lep, 1: .lep -> JPEG */, const lep_bytes *in, int n,
                                     lep_bytes *outs /* malloc'd by the callee */, int32_t *status);
+/* stream_band_mcu_rows > 0: decompress requests that did not arrive on a zlib listener or under the ce b6 magic are answered through
+ * lep_decompress_batch_stream, band by band: the batcher's sink appends to the connection's output, which is sent as it grows; the
+ * connection is closed when its file is finished and everything is sent.  A file that fails after bytes went out gets the close and
+ * counts as failed (the reference's worker dies the same way); a client that went away makes the sink return non-zero for that file only.
+ * Compress requests and zlib answers take the whole-answer path, and so does everything when the option is 0.  Sessions run one after
+ * another: the option trades throughput for time to first byte.  The test callback receives the files, a sink and its user, and fills status. */
+typedef int (*lep_serve_stream_fn)(void *user, const lep_bytes *in, int n, lep_batch_sink sink, void *sink_user, int32_t *status);
 typedef struct lep_serve_options {
     const char *uds_path;        /* -socket=<name>; the zlib socket is <name>.z0, the lock file <name>.lock; NULL = no UDS */
     const char *zlib_uds_path;   /* NULL = <uds_path>.z0 (the reference's random names are /tmp/<id>.uport and /tmp/<id>.z0) */
@@ -557,12 +608,18 @@ typedef struct lep_serve_options {
     lep_batch_options batch;     /* passed through to lep_*_batch (verify = the reference's default round-trip check) */
     lep_serve_process_fn process;   /* NULL = the GPU batch pipeline; tests substitute the CPU oracle here */
     void *process_user;
+    int32_t stream_band_mcu_rows;   /* -streamband; 0 = off */
+    lep_serve_stream_fn stream_process;   /* NULL = lep_decompress_batch_stream on gpu; tests substitute a callback.  The two callbacks go together: with
+                                             `process` set and this one NULL there is no device to stream from, and the option is ignored (whole answers from `process`) */
+    void *stream_user;
 } lep_serve_options;
 typedef struct lep_serve_stats {
     uint64_t accepted, answered, failed, timed_out, rejected;   /* connections */
     uint64_t batches, largest_batch;
     uint64_t bytes_in, bytes_out;
     int32_t last_failure_code;   /* exit code of the most recent failed request */
+    uint64_t streamed;              /* connections answered in pieces */
+    uint64_t bytes_out_before_done; /* bytes sent while the file's batch call had not yet returned */
 } lep_serve_stats;
 typedef struct lep_server lep_server;
 /* binds and starts the IO + batcher threads; LEP_OS_ERROR if a socket cannot be bound (or the lock is held: another

@@ -108,6 +108,15 @@ class StreamStats(C.Structure):
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)
 
 
+class BatchStreamStats(C.Structure):
+    _fields_ = [("files_streamed", C.c_int32), ("files_whole", C.c_int32), ("sessions", C.c_int32), ("advances", C.c_int32),
+                ("writer_launches", C.c_int32), ("scan_bytes_down", C.c_uint64), ("frame_bytes_down", C.c_uint64),
+                ("files_first_scan_byte_before_last_advance", C.c_int32), ("wall_s", C.c_double), ("first_piece_s", C.c_double)]
+
+
+BATCH_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_size_t)
+
+
 class BatchOptions(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("verify", C.c_int32), ("chunk_frame_bytes", C.c_size_t), ("host_huffman", C.c_int32), ("chunk_images", C.c_int32), ("overlap_launches", C.c_int32)]
 
@@ -123,19 +132,21 @@ class BatchStats(C.Structure):
 
 
 SERVE_PROCESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(Bytes), C.c_int, C.POINTER(Bytes), C.POINTER(C.c_int32))
+SERVE_STREAM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Bytes), C.c_int, BATCH_SINK_FN, C.c_void_p, C.POINTER(C.c_int32))
 
 
 class ServeOptions(C.Structure):
     _fields_ = [("uds_path", C.c_char_p), ("zlib_uds_path", C.c_char_p), ("tcp_port", C.c_int32), ("zlib_tcp_port", C.c_int32),
                 ("listen_backlog", C.c_int32), ("max_connections", C.c_int32), ("max_file_bytes", C.c_uint32),
                 ("time_bound_ms", C.c_uint32), ("max_batch", C.c_int32), ("batch_window_us", C.c_int32), ("gpu", C.c_void_p),
-                ("batch", BatchOptions), ("process", SERVE_PROCESS_FN), ("process_user", C.c_void_p)]
+                ("batch", BatchOptions), ("process", SERVE_PROCESS_FN), ("process_user", C.c_void_p),
+                ("stream_band_mcu_rows", C.c_int32), ("stream_process", SERVE_STREAM_FN), ("stream_user", C.c_void_p)]
 
 
 class ServeStats(C.Structure):
     _fields_ = [("accepted", C.c_uint64), ("answered", C.c_uint64), ("failed", C.c_uint64), ("timed_out", C.c_uint64),
                 ("rejected", C.c_uint64), ("batches", C.c_uint64), ("largest_batch", C.c_uint64), ("bytes_in", C.c_uint64),
-                ("bytes_out", C.c_uint64), ("last_failure_code", C.c_int32)]
+                ("bytes_out", C.c_uint64), ("last_failure_code", C.c_int32), ("streamed", C.c_uint64), ("bytes_out_before_done", C.c_uint64)]
 
 
 _lib = None
@@ -199,6 +210,11 @@ def lib():
             L.lep_gpu_decode_rows_advance.argtypes = [vp, C.c_int, P(DecodeProgress), P(C.c_int)]
             L.lep_gpu_decode_rows_end.argtypes = [vp]
             L.lep_decompress_stream.argtypes = [vp, vp, C.c_size_t, C.c_int, SINK_FN, vp, P(StreamStats)]
+        if hasattr(L, "lep_decompress_batch_stream"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_gpu_pack_device.argtypes = [vp, vp, P(C.c_uint64), vp, C.c_int, vp, C.c_uint64, vp, vp]
+            L.lep_gpu_stream_pack.argtypes = [vp]
+            L.lep_file_recode_head.argtypes = [vp, P(vp), P(C.c_size_t)]
+            L.lep_decompress_batch_stream.argtypes = [vp, P(Bytes), C.c_int, C.c_int, BATCH_SINK_FN, vp, P(C.c_int32), P(BatchOptions), P(BatchStreamStats)]
         L.lep_gpu_use_arena.argtypes = [vp, C.c_int]
         L.lep_gpu_sync.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
@@ -280,4 +296,5 @@ EXPORTS = [
     "lep_jpeg_plan_progressive_check", "lep_gpu_last_stage_ms", "lep_jpeg_set_container_version", "lep_container_can_write_version", "lep_jpeg_plan_scan_check", "lep_jpeg_scan_file_range",
     "lep_gpu_huffman_progressive_encode_forms", "lep_compress_batch_slices",
     "lep_gpu_decode_rows_begin", "lep_gpu_decode_rows_advance", "lep_gpu_decode_rows_end", "lep_decompress_stream",
+    "lep_gpu_pack_device", "lep_gpu_stream_pack", "lep_file_recode_head", "lep_decompress_batch_stream",
 ]

@@ -338,6 +338,31 @@ class GpuCodec:
         on the GPU for eligible files unless host_huffman is set"""
         return self._batch(self._L.lep_decompress_batch, leps, False, threads, chunk_bytes, chunk_images, host_huffman)
 
+    def decompress_batch_stream(self, leps, band_mcu_rows, threads=0):
+        """lep_decompress_batch_stream: (pieces, status, stats) -- per file the byte strings its sink calls received, in order, the
+        exit code per file, and the call's statistics as a dict"""
+        n = len(leps)
+        ins = (abi.Bytes * max(1, n))()
+        keep = []
+        for i, b in enumerate(leps):
+            buf = C.create_string_buffer(bytes(b), max(1, len(b)))
+            keep.append(buf)
+            ins[i].data = C.cast(buf, C.c_void_p).value
+            ins[i].len = ins[i].cap = len(b)
+        pieces = [[] for _ in range(n)]
+
+        def sink(user, i, data, k):
+            pieces[i].append(C.string_at(data, k))
+            return 0
+
+        status = (C.c_int32 * max(1, n))()
+        opt = abi.BatchOptions(threads, 0, 0, 0, 0)
+        stats = abi.BatchStreamStats()
+        rc = self._L.lep_decompress_batch_stream(self.handle, ins, n, band_mcu_rows, abi.BATCH_SINK_FN(sink), None, status, C.byref(opt), C.byref(stats))
+        if rc:
+            raise LeptonError(rc, "lep_decompress_batch_stream [%s]" % self.last_error())
+        return pieces, list(status)[:n], {k: getattr(stats, k) for k, _ in abi.BatchStreamStats._fields_}
+
     def scan_second_chances(self):
         """sequential scans the batch compressor handed to the single-wave kernel since the process started, after the
         lane-per-subsequence scan decoder had answered with a status (process-wide, not per codec object)"""

@@ -492,6 +492,12 @@ int lep_file_recode_plan(lep_file* f, lep_huff_image* image, lep_huff_segment* s
     return 0;
 }
 
+int lep_file_recode_head(const lep_file* f, const uint8_t** data, size_t* len) {
+    if (!f->planned) return LEP_ASSERTION_FAILURE;
+    *data = f->plan.head.data(); *len = f->plan.head.size();
+    return 0;
+}
+
 int lep_file_recode_plan_progressive(lep_file* f, lep_huffprog_image* image, lep_huffprog_scan* scans, int cap, int* nscan, int* gpu_ok) {
     *gpu_ok = 0; *nscan = 0;
     int rc = lep::recode_progressive_prepare(&f->lf, &f->prog);

@@ -31,6 +31,7 @@
 #include "lep_huffprogdec_win.h"
 #include "lep_huffprogdec_rst.h"
 #include "lep_scan_decode_plan.h"
+#include "lep_pack.h"
 
 using namespace lepdev;
 
@@ -336,6 +337,16 @@ __global__ __launch_bounds__(64, 8) void lep_huffman_encode_kernel(const lephuff
 __global__ __launch_bounds__(256) void lep_zero_kernel(uint4* p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = uint4{0u, 0u, 0u, 0u};
 }
+// byte runs that lie apart moved back to back (lep_pack.h): offsets, then one wavefront per run
+__global__ __launch_bounds__(leppack::kScanLanes) void lep_pack_offsets_kernel(const uint32_t* __restrict__ len, int n, uint64_t* __restrict__ dst_off) {
+    leppack::offsets(len, n, dst_off);
+}
+__global__ __launch_bounds__(64) void lep_pack_copy_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ len,
+                                                           int n, uint8_t* __restrict__ dst, uint64_t dst_cap, const uint64_t* __restrict__ dst_off) {
+    if (dst_off[n] > dst_cap) return;
+    const int i = (int)blockIdx.x;
+    leppack::copy_run(src + src_off[i], dst + dst_off[i], len[i], threadIdx.x & 63u);
+}
 // ... with one lane per run of MCUs (lep_huff_simt.h): count / place / code / stuff
 template <bool WRITE>
 __global__ __launch_bounds__(64) void lep_huffman_simt_encode_units_kernel(const lephuff::HuffImage* __restrict__ images, const lephuff::HuffSegment* __restrict__ segs,
@@ -540,6 +551,7 @@ struct lep_gpu {
     int huffprog_simt = 1;              // LEP_HUFFPROG_SIMT=0: every progressive scan's bytes from the wavefront-per-scan kernel (lep_huffprog.h)
     int huffprog_simt_rst = 1;          // LEP_HUFFPROG_SIMT_RST=0: scans with a restart interval from the wavefront-per-scan kernel
     uint32_t huffprog_forms[4] = {0, 0, 0, 0};   // the last progressive write's scans by form: lane, lane with intervals, wavefront, sequential
+    int stream_pack = 1;                // LEP_STREAM_PACK=0: lep_decompress_batch_stream fetches a band's bytes with one copy per segment, not packed (lep_pack.h)
     int huffenc_simt = 1;               // LEP_HUFFENC_SIMT=0: every segment's scan bytes from the wavefront-per-segment kernel (lep_huff.h)
     int simt_sub_bits = 0;              // LEP_HUFFDEC_SIMT_BITS: bits per subsequence of the lane-per-subsequence scan decoder (0 = from the launch's size)
     int huffprog_pipeline_max = 16384;  // LEP_HUFFPROG_PIPELINE_MAX: scans per launch up to which the levels go out as one pipelined launch (measured to 10240:
@@ -619,6 +631,7 @@ struct lep_gpu {
         W_HUFFPROGRST,              // files with scans of lep_huffprogdec_rst.h: ProgDecScan[], ProgRstScan[], ProgRstOut[]
         W_HUFFDEC,                  // HuffDecImage[]
         W_HUFFPAR,                  // the lane-per-subsequence scan decoder's records (SimtImage | SimtWave | SimtSub x 2 | SimtPlace)
+        W_PACK, W_PACK_1,           // lep_gpu_pack_device: the runs' source offsets (one per arena set, like W_HUFF)
         W_COUNT
     };
     lepbuf::DevBuf<> ws[W_COUNT];
@@ -1121,6 +1134,7 @@ int lep_gpu_create(int device, lep_gpu** out) {
     if (const char* e = getenv("LEP_HUFFPROG_PIPELINE_MAX")) g->huffprog_pipeline_max = atoi(e);
     if (const char* e = getenv("LEP_HUFFDEC_SIMT_BITS")) g->simt_sub_bits = std::max(0, atoi(e));
     if (const char* e = getenv("LEP_HUFFENC_SIMT")) g->huffenc_simt = atoi(e) != 0;
+    if (const char* e = getenv("LEP_STREAM_PACK")) g->stream_pack = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROG_SIMT")) g->huffprog_simt = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROG_SIMT_RST")) g->huffprog_simt_rst = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_WIN")) g->huffprogdec_win = atoi(e) != 0;
@@ -1322,6 +1336,28 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
     g->last_kernel = es.empty() ? "lep_huffman_encode_kernel" : "lep_huffman_simt_encode_{units,place,stuff}_kernel";
+    return 0;
+}
+
+// Byte runs moved back to back (lep_pack.h).  Its one workspace, W_PACK of the current arena set, is no decode session's: like the scan
+// writer above (W_HUFF, W_HUFFENC) it may be launched on a set whose session is open.
+int lep_gpu_pack_device(lep_gpu* g, const uint8_t* d_src, const uint64_t* src_off, const uint32_t* d_len, int n, uint8_t* d_dst, uint64_t d_dst_cap,
+                        uint64_t* d_dst_off, void* hip_stream) {
+    if (!g) return LEP_GPU_ERROR;
+    if (n < 0 || n > leppack::kMaxRuns || !d_dst_off || (n > 0 && (!src_off || !d_len || !d_src || !d_dst))) {
+        g->err = "lep_gpu_pack_device: 0 <= n <= 16384 runs, with their arrays";
+        return LEP_ASSERTION_FAILURE;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
+    HIPCHK(g, hipSetDevice(g->device));
+    if (n == 0) { HIPCHK(g, hipMemsetAsync(d_dst_off, 0, sizeof(uint64_t), st)); return 0; }
+    Workspace& ws = g->ws[lep_gpu::W_PACK + (g->cur & 1)];
+    if (int rc = ensure(g, ws, (size_t)n * sizeof(uint64_t))) return rc;
+    if (int rc = upload(g, ws.p, src_off, (size_t)n * sizeof(uint64_t), st)) return rc;
+    hipLaunchKernelGGL(lep_pack_offsets_kernel, dim3(1), dim3(leppack::kScanLanes), 0, st, d_len, n, d_dst_off);
+    hipLaunchKernelGGL(lep_pack_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, ws.at<uint64_t>(0), d_len, n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
+    HIPCHK(g, hipGetLastError());
+    g->last_kernel = "lep_pack_{offsets,copy}_kernel";
     return 0;
 }
 
@@ -1632,6 +1668,7 @@ int lep_gpu_huffman_progressive_encode_forms(lep_gpu* g, uint32_t counts[4]) {
     return 0;
 }
 int lep_gpu_device(lep_gpu* g) { return g ? g->device : -1; }
+int lep_gpu_stream_pack(lep_gpu* g) { return g ? g->stream_pack : 0; }
 // "0000:c1:00.0" of the device the object was created on (hipDeviceGetPCIBusId): which physical GPU a rank of a multi-GPU run drives
 int lep_gpu_pci_bus_id(lep_gpu* g, char* out, int cap) {
     if (!g || !out || cap < 16) return LEP_ASSERTION_FAILURE;

@@ -5,6 +5,9 @@
 // thread turns whatever has arrived into ONE lep_compress_batch + ONE lep_decompress_batch call; while that batch is on
 // the GPU the IO thread keeps receiving the next one.  Wire behaviour is the reference's: whole file in, half-close,
 // whole file out, close; nothing but the close on failure; <name>.z0 / -zliblisten answers with stored-block zlib.
+// With stream_band_mcu_rows set, plain decompress requests are answered in pieces (lep_decompress_batch_stream): the batcher's sink
+// appends to the connection's output under the connection's lock and wakes the IO thread, which sends what is there; the connection turns
+// WRITING with its first piece and is closed when its file is finished and everything is sent.
 #include <arpa/inet.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -47,6 +50,12 @@ struct Conn {
     bool has_deadline = false;
     Clock::time_point deadline;
     std::atomic<bool> dead{false};         // closed by the IO thread while the batcher held it
+    // answered in pieces: `out` grows under omu while the IO thread sends it; piece_io is the IO thread's own
+    std::mutex omu;
+    bool pieces = false;                   // omu: the sink has given at least one piece
+    bool finished = false;                 // omu: the file's batch call has returned
+    bool piece_failed = false;             // omu: ... with a failure for this file
+    bool piece_io = false;                 // IO thread: turned WRITING by its first piece
 };
 using ConnPtr = std::shared_ptr<Conn>;
 
@@ -71,6 +80,7 @@ struct lep_server {
     std::mutex mu;
     std::condition_variable cv;
     std::deque<ConnPtr> ready, done;       // IO -> batcher, batcher -> IO
+    std::deque<ConnPtr> started;           // batcher -> IO: connections whose first piece is there
     std::atomic<bool> stop{false};
     lep_serve_stats stats{};
     std::vector<ConnPtr> conns;            // IO thread only
@@ -80,6 +90,7 @@ struct lep_server {
     void batch_loop();
     void drop(const ConnPtr& c, uint64_t lep_serve_stats::*counter);
     void finish_upload(const ConnPtr& c);
+    void answer_in_pieces(const std::vector<ConnPtr>& group);
 };
 
 namespace {
@@ -89,6 +100,37 @@ int default_process(void* user, int kind, const lep_bytes* in, int n, lep_bytes*
     if (!s->opt.gpu) return LEP_GPU_ERROR;   // no CPU fallback: a server without a device answers nothing
     return kind == 0 ? lep_compress_batch(s->opt.gpu, in, n, outs, status, &s->opt.batch, nullptr)
                      : lep_decompress_batch(s->opt.gpu, in, n, outs, status, &s->opt.batch, nullptr);
+}
+
+// (a weak reference: the sanitizer harnesses under tests/fuzz link this file alone, with stand-ins for the batch calls they know of and a
+// processor of their own; in the library the call is lep_batch_stream.cc's)
+extern "C" __attribute__((weak)) int lep_decompress_batch_stream(lep_gpu* g, const lep_bytes* leps, int n, int band_mcu_rows, lep_batch_sink sink, void* user,
+                                                                 int32_t* status, const lep_batch_options* opt, lep_batch_stream_stats* stats);
+int default_stream_process(void* user, const lep_bytes* in, int n, lep_batch_sink sink, void* sink_user, int32_t* status) {
+    lep_server* s = static_cast<lep_server*>(user);
+    if (!s->opt.gpu || !lep_decompress_batch_stream) return LEP_GPU_ERROR;
+    return lep_decompress_batch_stream(s->opt.gpu, in, n, s->opt.stream_band_mcu_rows, sink, sink_user, status, &s->opt.batch, nullptr);
+}
+
+struct PieceSink { lep_server* s; const std::vector<ConnPtr>* group; };
+
+// lep_batch_sink of the batcher: the piece goes behind the connection's output; the first one hands the connection to the IO thread
+int piece_sink(void* user, int file, const uint8_t* data, size_t len) {
+    PieceSink* p = static_cast<PieceSink*>(user);
+    if (file < 0 || (size_t)file >= p->group->size()) return 1;
+    const ConnPtr& c = (*p->group)[(size_t)file];
+    if (c->dead.load()) return 1;   // the client went away (or ran into its time bound): this file only
+    if (!len) return 0;
+    bool first;
+    {
+        std::lock_guard<std::mutex> g(c->omu);
+        first = !c->pieces;
+        c->pieces = true;
+        c->out.insert(c->out.end(), data, data + len);
+    }
+    if (first) { std::lock_guard<std::mutex> g(p->s->mu); p->s->started.push_back(c); }
+    p->s->wake();
+    return 0;
 }
 
 int listen_uds(const std::string& path, int backlog) {
@@ -168,7 +210,14 @@ void lep_server::io_loop() {
         for (size_t i = 0; i < conns.size(); ++i) {
             Conn& c = *conns[i];
             if (c.state == Conn::READING) { pf.push_back({c.fd, POLLIN, 0}); who.push_back((int)i); }
-            else if (c.state == Conn::WRITING) { pf.push_back({c.fd, POLLOUT, 0}); who.push_back((int)i); }
+            else if (c.state == Conn::WRITING) {
+                short ev = POLLOUT;
+                if (c.piece_io) {   // nothing to send until the next piece (the sink wakes us); a hang-up is still reported
+                    std::lock_guard<std::mutex> g(c.omu);
+                    if (c.out_pos == c.out.size() && !c.finished) ev = 0;
+                }
+                pf.push_back({c.fd, ev, 0}); who.push_back((int)i);
+            }
             if (c.has_deadline) {
                 const long ms = (long)std::chrono::duration_cast<std::chrono::milliseconds>(c.deadline - now0).count();
                 timeout = (int)std::max(0l, std::min<long>(timeout, ms + 1));
@@ -221,14 +270,25 @@ void lep_server::io_loop() {
                         break;
                     }
                 } else if (c->state == Conn::WRITING) {
+                    std::unique_lock<std::mutex> ol(c->omu, std::defer_lock);
+                    if (c->piece_io) {
+                        if ((pf[k].revents & (POLLHUP | POLLERR)) && !(pf[k].revents & POLLOUT)) { drop(c, &lep_serve_stats::failed); continue; }   // the client left between two pieces
+                        ol.lock();
+                    }
                     for (;;) {
                         if (c->out_pos == c->out.size()) {
-                            { std::lock_guard<std::mutex> g(mu); ++stats.answered; stats.bytes_out += c->out.size(); }
+                            if (c->piece_io && !c->finished) break;   // more pieces to come
+                            if (c->piece_io && c->piece_failed) { drop(c, &lep_serve_stats::failed); break; }   // failed after bytes went out: the close
+                            { std::lock_guard<std::mutex> g(mu); ++stats.answered; stats.bytes_out += c->out.size(); if (c->piece_io) ++stats.streamed; }
                             drop(c, nullptr);
                             break;
                         }
                         const ssize_t n = send(c->fd, c->out.data() + c->out_pos, c->out.size() - c->out_pos, MSG_NOSIGNAL);
-                        if (n > 0) { c->out_pos += (size_t)n; continue; }
+                        if (n > 0) {
+                            c->out_pos += (size_t)n;
+                            if (c->piece_io && !c->finished) { std::lock_guard<std::mutex> g(mu); stats.bytes_out_before_done += (uint64_t)n; }
+                            continue;
+                        }
                         if (n < 0 && errno == EINTR) continue;
                         if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
                         drop(c, &lep_serve_stats::failed);   // the client went away
@@ -238,11 +298,23 @@ void lep_server::io_loop() {
             }
         }
 
-        // answers from the batcher
-        std::deque<ConnPtr> fin;
-        { std::lock_guard<std::mutex> g(mu); fin.swap(done); }
+        // answers from the batcher: first pieces, then finished requests
+        std::deque<ConnPtr> fin, begun;
+        { std::lock_guard<std::mutex> g(mu); fin.swap(done); begun.swap(started); }
+        for (const ConnPtr& c : begun) {
+            if (c->dead.load() || c->fd < 0 || c->state != Conn::QUEUED) continue;
+            c->state = Conn::WRITING;
+            c->piece_io = true;
+            c->out_pos = 0;
+        }
         for (const ConnPtr& c : fin) {
             if (c->dead.load() || c->fd < 0) continue;
+            if (c->piece_io) {   // sending already: a file that failed after bytes went out gets the close; the others end when all is sent
+                bool failed_late;
+                { std::lock_guard<std::mutex> g(c->omu); failed_late = c->piece_failed; }
+                if (failed_late) drop(c, &lep_serve_stats::failed);
+                continue;
+            }
             if (c->out.empty()) { drop(c, &lep_serve_stats::failed); continue; }   // the reference's child died with a code: just the close
             c->state = Conn::WRITING;
             c->out_pos = 0;
@@ -279,10 +351,17 @@ void lep_server::batch_loop() {
             while (!ready.empty() && batch.size() < max_batch) { batch.push_back(ready.front()); ready.pop_front(); }
         }
         size_t live = 0;
+        std::vector<ConnPtr> in_pieces;   // plain decompress requests with the option on
+        // (a server whose whole answers come from a callback has no device behind it: without a stream callback too it keeps whole answers)
+        const bool pieces_on = opt.stream_band_mcu_rows > 0 && (opt.stream_process || !opt.process);
+        if (pieces_on)
+            for (const ConnPtr& c : batch)
+                if (c->kind == 1 && !c->zlib && !c->dead.load()) in_pieces.push_back(c);
+        if (!in_pieces.empty()) { live += in_pieces.size(); answer_in_pieces(in_pieces); }
         for (int kind = 0; kind < 2; ++kind) {
             std::vector<Conn*> group;
             for (const ConnPtr& c : batch)
-                if (c->kind == kind && !c->dead.load()) group.push_back(c.get());
+                if (c->kind == kind && !c->dead.load() && !(kind == 1 && pieces_on && !c->zlib)) group.push_back(c.get());
             if (group.empty()) continue;
             live += group.size();
             const int n = (int)group.size();
@@ -316,6 +395,33 @@ void lep_server::batch_loop() {
             for (const ConnPtr& c : batch) done.push_back(c);
         }
         wake();
+    }
+}
+
+// One lep_decompress_batch_stream call (or the test callback) over the group; the sink feeds the connections while it runs.
+void lep_server::answer_in_pieces(const std::vector<ConnPtr>& group) {
+    const int n = (int)group.size();
+    std::vector<lep_bytes> in((size_t)n);
+    std::vector<int32_t> status((size_t)n, LEP_CODING_ERROR);
+    for (int i = 0; i < n; ++i) in[(size_t)i] = {group[(size_t)i]->in.data(), group[(size_t)i]->in.size(), group[(size_t)i]->in.size()};
+    PieceSink ps{this, &group};
+    lep_serve_stream_fn fn = opt.stream_process ? opt.stream_process : default_stream_process;
+    const int rc = fn(opt.stream_process ? opt.stream_user : this, in.data(), n, piece_sink, &ps, status.data());
+    for (int i = 0; i < n; ++i) {
+        Conn& c = *group[(size_t)i];
+        const int code = rc ? rc : status[(size_t)i];
+        {
+            std::lock_guard<std::mutex> g(c.omu);
+            c.finished = true;
+            c.piece_failed = code != 0;
+            if (code != 0 && !c.pieces) c.out.clear();
+        }
+        if (code != 0) {
+            fprintf(stderr, "request (%zu bytes, lepton, in pieces) failed with code %d\n", c.in.size(), code);
+            std::lock_guard<std::mutex> g(mu);
+            stats.last_failure_code = code;
+        }
+        std::vector<uint8_t>().swap(c.in);
     }
 }
 

@@ -2,7 +2,9 @@
 // (src/lepton/jpgcoder.cc:1026-1186, help text :2089-2110) in front of the GPU batch pipeline.  One process per GPU.
 //   lepton_served -socket[=name] [-listen[=port]] [-zliblisten=port] [-listenbacklog=n] [-maxchildren=n]
 //                 [-timebound=<n>ms|s|us] [-skipverify|-verify] [-device=k | -devices=a,b,...] [-maxbatch=n]
-//                 [-batchwindow=<us>] [-hosthuffman]
+//                 [-batchwindow=<us>] [-hosthuffman] [-streamband=<MCU rows>]
+// -streamband=n: decompress requests are answered in pieces, n MCU rows of decode at a time (lep_decompress_batch_stream): the first bytes
+// leave the socket while later rows decode, at the price of throughput -- sessions run one after another.  0 / absent: whole answers.
 // -devices=0,1,...: one serving process per GPU (forked before any HIP call), sockets <name>.<device> (TCP: port + device,
 // zlib port + device); the parent only waits and passes SIGTERM / SIGINT / SIGQUIT on.
 // Prints the socket name on stdout once it is listening (socket_serve.cc:383-384) and serves until SIGINT / SIGTERM /
@@ -54,6 +56,7 @@ int main(int argc, char** argv) {
         else if (starts(a, "-maxbatch=")) o.max_batch = atoi(a + 10);
         else if (starts(a, "-batchwindow=")) o.batch_window_us = atoi(a + 13);
         else if (!strcmp(a, "-hosthuffman")) o.batch.host_huffman = 1;
+        else if (starts(a, "-streamband=")) o.stream_band_mcu_rows = atoi(a + 12);
         else if (!strcmp(a, "-preload") || !strcmp(a, "-unjailed") || !strcmp(a, "-allowprogressive") || !strcmp(a, "-singlethread")) {}   // no-ops here
         else { fprintf(stderr, "lepton_served: unknown option %s\n", a); return 1; }
     }
@@ -149,8 +152,8 @@ int main(int argc, char** argv) {
     lep_serve_stop(srv);
     lep_batch_release();
     if (gpu) lep_gpu_destroy(gpu);
-    fprintf(stderr, "lepton_served: %llu accepted, %llu answered, %llu failed, %llu timed out, %llu batches (largest %llu)\n",
+    fprintf(stderr, "lepton_served: %llu accepted, %llu answered, %llu failed, %llu timed out, %llu batches (largest %llu), %llu answered in pieces\n",
             (unsigned long long)st.accepted, (unsigned long long)st.answered, (unsigned long long)st.failed,
-            (unsigned long long)st.timed_out, (unsigned long long)st.batches, (unsigned long long)st.largest_batch);
+            (unsigned long long)st.timed_out, (unsigned long long)st.batches, (unsigned long long)st.largest_batch, (unsigned long long)st.streamed);
     return 0;
 }

@@ -9,22 +9,16 @@
 #include <vector>
 
 #include "lep_handles.h"
+#include "lep_stream_bands.h"
+#include "lep_stream_session.h"
 
 extern "C" {
 
 // lep_decompress with the bytes handed on as they become final (include/lepton_mi355x.h).  The decode is a session
 // (lep_gpu_decode_rows_*): after every advance the block rows the segments completed are fetched into the host frame and the MCU rows
 // they complete are coded by a SegmentRowCoder per segment; recode_finish, over the same bytes, supplies the checks and the tail.
-namespace {
-struct DeviceMem {   // device allocations of one call, freed when it returns
-    lep_gpu* g;
-    std::vector<void*> ptrs;
-    explicit DeviceMem(lep_gpu* g_) : g(g_) {}
-    ~DeviceMem() { for (void* p : ptrs) lep_gpu_free(g, p); }
-    int get(size_t bytes, void** out) { int rc = lep_gpu_malloc(g, bytes, out); if (!rc) ptrs.push_back(*out); return rc; }
-};
-struct SessionEnd { lep_gpu* g; bool open = false; ~SessionEnd() { if (open) lep_gpu_decode_rows_end(g); } };
-}  // namespace
+using lep::DeviceMem;
+using lep::SessionEnd;
 
 static int decompress_whole_to_sink(lep_gpu* g, const uint8_t* lepdata, size_t len, lep_sink sink, void* user) {
     lep_bytes out = {nullptr, 0, 0};
@@ -46,20 +40,15 @@ int lep_decompress_stream(lep_gpu* g, const uint8_t* lepdata, size_t len, int ba
     lep::LepFile& lf = f->lf;
     lep::JpegFile& jf = lf.jpeg;
     lep::RecodePlan plan;
-    // what is streamed: one whole baseline file with one interleaved scan of two or three components, several thread segments or one --
-    // the files the split re-coder plans (recode_prepare), bar truncated ones (what the re-coder reads behind the cut is not rows of
-    // this decode) and chains of files
-    const bool chained = lep_chained_file_follows(lepdata, len, lep_file_consumed(f)) != 0;
-    if (chained || lf.flag != 'Z' || jf.early_eof || jf.ncomp < 2 || lep::recode_prepare(&lf, &plan) != 0 || !plan.gpu_ok) {
+    lep_image_desc d;
+    lep_segment segs[LEP_MAX_SEGMENTS];
+    lep_bytes streams[LEP_MAX_SEGMENTS];
+    int n = 0;
+    if (!lep::streams_in_session(f, lepdata, len, &plan, segs, streams, &n)) {
         hold.reset();
         return decompress_whole_to_sink(g, lepdata, len, sink, user);
     }
-    lep_image_desc d;
     lep_file_describe(f, &d);
-    lep_segment segs[LEP_MAX_SEGMENTS];
-    lep_bytes streams[LEP_MAX_SEGMENTS];
-    const int n = lep_file_segments(f, segs, streams, 0);
-    if (n <= 0 || (size_t)n != plan.segs.size()) { hold.reset(); return decompress_whole_to_sink(g, lepdata, len, sink, user); }
 
     // device side: a zeroed frame, the streams back to back, their lengths
     DeviceMem mem(g);
@@ -100,7 +89,7 @@ int lep_decompress_stream(lep_gpu* g, const uint8_t* lepdata, size_t len, int ba
     int fetched[LEP_MAX_SEGMENTS][LEP_MAX_COMPONENTS] = {{0}};   // rows_done as of the last fetch
     lep_decode_progress prog[LEP_MAX_SEGMENTS];
     int vs[LEP_MAX_COMPONENTS];
-    for (int c = 0; c < d.ncomp; ++c) vs[c] = std::max(d.height_blocks[c] / std::max(d.mcu_rows, 1), 1);
+    lepbands::block_rows_per_mcu_row(d, vs);
     bool failed = false, scan_byte_out = false;
     for (int running = 1; running > 0;) {
         stats->bytes_before_last_advance = sunk;
@@ -167,3 +156,15 @@ int lep_decompress_stream(lep_gpu* g, const uint8_t* lepdata, size_t len, int ba
 }
 
 }  // extern "C"
+
+bool lep::streams_in_session(lep_file* f, const uint8_t* lepdata, size_t len, RecodePlan* plan, lep_segment* segs, lep_bytes* streams, int* nseg) {
+    LepFile& lf = f->lf;
+    JpegFile& jf = lf.jpeg;
+    *nseg = 0;
+    const bool chained = lep_chained_file_follows(lepdata, len, lep_file_consumed(f)) != 0;
+    if (chained || lf.flag != 'Z' || jf.early_eof || jf.ncomp < 2 || recode_prepare(&lf, plan) != 0 || !plan->gpu_ok) return false;
+    const int n = lep_file_segments(f, segs, streams, 0);
+    if (n <= 0 || (size_t)n != plan->segs.size()) return false;
+    *nseg = n;
+    return true;
+}

@@ -53,10 +53,14 @@ def zlib0_wrap(data):
 
 
 class Server:
-    """lep_serve_start .. lep_serve_stop.  process (tests only): callable(kind, [bytes]) -> [(exit_code, bytes or None)]."""
+    """lep_serve_start .. lep_serve_stop.  process (tests only): callable(kind, [bytes]) -> [(exit_code, bytes or None)].
+    stream_band_mcu_rows > 0: plain decompress requests are answered in pieces, that many MCU rows of decode at a time
+    (lep_decompress_batch_stream); stream_process (tests only): callable([bytes], sink) -> [exit_code], where sink(i, bytes) hands a
+    piece of file i on and returns non-zero once that file's client is gone."""
 
     def __init__(self, uds_path=None, gpu=None, tcp_port=0, zlib_tcp_port=0, time_bound_ms=0, max_batch=0, batch_window_us=0,
-                 max_connections=0, max_file_bytes=0, verify=True, host_huffman=False, process=None, zlib_uds_path=None):
+                 max_connections=0, max_file_bytes=0, verify=True, host_huffman=False, process=None, zlib_uds_path=None,
+                 stream_band_mcu_rows=0, stream_process=None):
         self._L = abi.lib()
         o = abi.ServeOptions()
         self._keep = [uds_path.encode() if isinstance(uds_path, str) else uds_path,
@@ -83,6 +87,18 @@ class Server:
                     return 1
             self._cb = abi.SERVE_PROCESS_FN(thunk)
             o.process = self._cb
+        o.stream_band_mcu_rows = stream_band_mcu_rows
+        if stream_process is not None:
+            def stream_thunk(_user, ins, n, sink, sink_user, status):
+                try:
+                    codes = stream_process([C.string_at(ins[i].data, ins[i].len) for i in range(n)], lambda i, data: sink(sink_user, i, C.cast(C.c_char_p(data), C.POINTER(C.c_uint8)), len(data)))
+                    for i, code in enumerate(codes):
+                        status[i] = code
+                    return 0
+                except Exception:   # a broken callback must not take the server thread down
+                    return 1
+            self._stream_cb = abi.SERVE_STREAM_FN(stream_thunk)
+            o.stream_process = self._stream_cb
         self.handle = C.c_void_p()
         rc = self._L.lep_serve_start(C.byref(o), C.byref(self.handle))
         if rc:

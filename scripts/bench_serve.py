@@ -32,6 +32,32 @@ def client_proc(name, payloads, idxs, threads, q):
     q.put({i: hashlib.md5(v).hexdigest() for i, v in out.items()})
 
 
+def timed_request(name, data, mark=65536):
+    """one request: (ms to the first byte, ms to the first `mark` bytes, ms to the whole answer, the answer)"""
+    import socket
+
+    s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
+    try:
+        t0 = time.perf_counter()
+        s.connect(name)
+        s.sendall(data)
+        s.shutdown(socket.SHUT_WR)
+        parts, n, first, at_mark = [], 0, None, None
+        while True:
+            b = s.recv(1 << 20)
+            if not b:
+                break
+            now = (time.perf_counter() - t0) * 1e3
+            parts.append(b)
+            n += len(b)
+            first = now if first is None else first
+            at_mark = now if at_mark is None and n >= mark else at_mark
+        total = (time.perf_counter() - t0) * 1e3
+        return first, at_mark if at_mark is not None else total, total, b"".join(parts)
+    finally:
+        s.close()
+
+
 def fan(name, payloads, nreq, clients, procs):
     q = mp.Queue()
     per = max(1, clients // procs)
@@ -55,6 +81,7 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--window-us", type=int, default=20000)
     ap.add_argument("--skipverify", action="store_true")
+    ap.add_argument("--streamband", type=int, default=0, help="lepton_served -streamband=<n>: decompress answers in pieces, n MCU rows of decode at a time")
     args = ap.parse_args()
     import hashlib
     import __graft_entry__ as ge
@@ -67,6 +94,8 @@ def main():
     cmd = [os.path.join(ROOT, "lepton_amd", "lepton_served"), "-socket=" + name, "-batchwindow=%d" % args.window_us, "-listenbacklog=4096"]
     if args.skipverify:
         cmd.append("-skipverify")
+    if args.streamband:
+        cmd.append("-streamband=%d" % args.streamband)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     try:
         assert proc.stdout.readline().strip().decode() == name
@@ -81,6 +110,14 @@ def main():
                 t0 = time.perf_counter(); request(name, payloads[i % len(payloads)], timeout=600); ts.append((time.perf_counter() - t0) * 1e3)
             ts.sort()
             lat[label] = {"p50_ms": round(ts[len(ts) // 2], 1), "min_ms": round(ts[0], 1), "max_ms": round(ts[-1], 1)}
+        # the same lone decompress client, with the time at which the answer's first byte and its first 64 KB were in hand
+        rows = []
+        for i in range(12):
+            first, at64k, total, got = timed_request(name, leps[i % len(leps)])
+            assert got == uniq[i % len(uniq)]
+            rows.append((first, at64k, total))
+        med = lambda k: round(sorted(r[k] for r in rows)[len(rows) // 2], 1)
+        lat["decompress_first_bytes"] = {"first_byte_p50_ms": med(0), "first_64KB_p50_ms": med(1), "whole_p50_ms": med(2)}
         fan(name, uniq, min(args.requests, 1024), args.clients, args.procs)   # staging buffers of the batch pipeline
         mb = sum(len(uniq[i % len(uniq)]) for i in range(args.requests)) / 1e6
         tc, rc = fan(name, uniq, args.requests, args.clients, args.procs)
@@ -95,7 +132,7 @@ def main():
         proc.wait()
     print(json.dumps({
         "workload": "%d requests of %dx%d JPEGs (%d distinct) over a Unix socket, %d concurrent clients, lepton_served %s" % (
-            args.requests, args.width, args.height, len(uniq), args.clients, "without verification" if args.skipverify else "with on-GPU round-trip verification"),
+            args.requests, args.width, args.height, len(uniq), args.clients, ("without verification" if args.skipverify else "with on-GPU round-trip verification") + (", -streamband=%d" % args.streamband if args.streamband else "")),
         "jpeg_MB": round(mb, 1), "compress_MBps": round(mb / tc, 1), "compress_requests_per_s": round(args.requests / tc, 1),
         "decompress_MBps": round(mb / td, 1), "decompress_requests_per_s": round(args.requests / td, 1),
         "one_client_latency": lat,
