@@ -193,6 +193,11 @@ int lep_gpu_huffman_encode_device(lep_gpu *g, const lep_huff_image *images, int 
  * session's: it may be called while a session is open on that set. */
 int lep_gpu_pack_device(lep_gpu *g, const uint8_t *d_src, const uint64_t *src_off, const uint32_t *d_len, int n,
                         uint8_t *d_dst, uint64_t d_dst_cap, uint64_t *d_dst_off, void *hip_stream);
+/* Progressive files that END INSIDE A SCAN (no EOI) in lep_compress_batch / lep_decompress_batch: on = 1 sends them to the scan kernels
+ * (lep_jpeg_open_gpu_progressive_cut, lep_file_recode_plan_progressive_cut), on = 0 -- what a codec starts with, unless
+ * LEP_CUT_PROGRESSIVE=1 was set when it was made -- keeps them with the host parser and re-coder, where every earlier release had them;
+ * on < 0 changes nothing.  Returns the setting.  Same bytes and statuses either way. */
+int lep_gpu_cut_progressive(lep_gpu *g, int on);
 int lep_gpu_stream_pack(lep_gpu *g);   /* 1: lep_decompress_batch_stream packs a band's bytes before it fetches them; LEP_STREAM_PACK=0 when the codec is made: 0 */
 /* The same for PROGRESSIVE files (BASELINE.json configs[4]; replaces the scan loop of recode_jpeg, src/lepton/jpgcoder.cc:3309-3716,
  * with encode_dc_prg_*, encode_ac_prg_fs / _sa, encode_eobrun, encode_crbits :4991-5400): every scan of a progressive file is a
@@ -200,7 +205,12 @@ int lep_gpu_stream_pack(lep_gpu *g);   /* 1: lep_decompress_batch_stream packs a
  * scans[i].out_off by one LANE per 32 blocks (lep_huffprog_simt.h: count / place / assign / code / stuff; in a scan with a restart
  * interval the units are cut at the intervals' ends); d_out_len[i] = byte count, bit 31 set = the scan outgrew its slot or its
  * scratch (let the host re-coder do that file).  d_corr: scratch for correction bits held back behind end-of-band runs
- * (scans[i].corr_off / corr_cap dwords).  lep_file_recode_plan_progressive fills both structs. */
+ * (scans[i].corr_off / corr_cap dwords).  lep_file_recode_plan_progressive fills both structs.
+ * A file that ENDS INSIDE A SCAN (no EOI; no restart intervals): every scan is written whole from the frame, which is zero behind the
+ * cut, and lep_file_recode_finish_progressive's byte bound cuts the output.  The scan the file ends in can be many times what the file
+ * kept of it: its out_cap is what its geometry bounds it by, file_bound that much on top of the file's size.  A caller that decoded such
+ * a file from ONE thread segment clears the frame from block coded_blocks[c] of every component on (lep_image_desc) in front of this
+ * call: the reference's re-coder reads zeros there even where the stream coded a row's first block. */
 typedef struct lep_huffprog_image {
     int32_t ncomp, mcuh, mcuv, mcuc;
     int32_t rsti, padbit;
@@ -274,6 +284,12 @@ int lep_gpu_huffman_decode_device(lep_gpu *g, const lep_huffdec_image *images, i
  * zero-filled frame t.blocks, the first scan of a file also one record per MCU row at d_rows + t.rows_off, and every scan a
  * final record {bits consumed, last DC, pad bits | status << 8} at d_rows + result_off; a non-zero status anywhere sends the
  * whole file to the host parser.  lep_jpeg_open_gpu_progressive fills the descriptors.
+ * A file that ENDS INSIDE A SCAN (no EOI): its last descriptor, and no other, carries LEP_HUFFDEC_EARLY_EOF in t.flags.  That scan is
+ * decoded up to the block that reads the data's last bit -- every bit at or behind t.scan_len * 8 is zero by position, whatever the slot
+ * holds there -- and its final record says LEP_HUFFDEC_ROW_TRUNCATED, .bitpos = the blocks of the scan's order up to and including that
+ * one (a one-component scan: the position the block started at, + 1).  A block that meets the end and does not decode is a status like
+ * any other.  Only lep_huffprogdec_win.h knows the cut: a flagged scan that form does not take (a restart interval, a slot that is not
+ * 16-byte aligned, LEP_HUFFPROGDEC_WIN=0) goes to no kernel, its final record is filled with 0x80 bytes, the file goes to the host parser.
  * LEP_HUFFDEC_RST_TABLE in t.flags is the contract the sequential side has: a caller that passes a descriptor with the flag HAS PUT the
  * scan's marker positions (lep_jpeg_scan_restarts_of: uint32 offsets into this scan's un-stuffed bytes) behind the scan's slot, at
  * t.scan + LEP_HUFFPROGDEC_SCAN_ROOM(t.scan_len); a caller that has not put them there CLEARS the flag, and the scan goes to
@@ -352,15 +368,25 @@ int lep_compress_embedded(lep_gpu *g, const uint8_t *blob, size_t len, size_t of
  * after lep_jpeg_open_gpu answered *eligible = 0.  Fills up to `cap` scan descriptors (t.scan = byte offset of
  * the scan inside lep_jpeg_scan_bytes, t.rows_off / result_off relative to the file's first record -- the caller adds its arena
  * offsets and sets t.blocks); *rows_needed = records the file needs in the row arena.  _finish turns the kernels' records into
- * the hand-offs and bookkeeping of the .lep header (non-zero: irregular, use the host parser). */
+ * the hand-offs and bookkeeping of the .lep header (non-zero: irregular, use the host parser).
+ * A file that ends inside a scan: *eligible = 0, as ever.  lep_jpeg_open_gpu_progressive_cut takes PROGRESSIVE files of that kind too,
+ * their last scan flagged LEP_HUFFDEC_EARLY_EOF -- unless a scan of the file has a restart interval or the last scan holds no byte of
+ * data (cut sequential frames in several scans stay with the host parser): for a caller that launches the descriptors through
+ * lep_gpu_huffman_progressive_decode_device, which knows the flag.  lep_compress_batch is that caller. */
 int lep_jpeg_open_gpu_progressive(lep_jpeg *j, lep_huffprogdec_scan *scans, int cap, int *nscan, int *rows_needed, int *eligible);
+int lep_jpeg_open_gpu_progressive_cut(lep_jpeg *j, lep_huffprogdec_scan *scans, int cap, int *nscan, int *rows_needed, int *eligible);
 int lep_jpeg_finish_gpu_progressive(lep_jpeg *j, const lep_huffprogdec_scan *scans, int nscan, const lep_huffdec_row *rows);
 /* The Huffman half of the round-trip check (validation.cc:97-218) for a file whose scans lep_jpeg_open_gpu_progressive took:
  * the plan that writes every scan of the parsed file again on the GPU (lep_gpu_huffman_progressive_encode_device; the caller
  * sets image->blocks, out_off, corr_off) and where each scan's own bytes lie in the file (first byte, length -- up to the
- * marker that ends the scan), to be compared with what the kernel wrote.  *eligible = 0: check on the host instead. */
+ * marker that ends the scan), to be compared with what the kernel wrote.  *eligible = 0: check on the host instead.
+ * A file that ends inside a scan: *eligible = 0.  lep_jpeg_plan_progressive_check_cut plans those too: the length of the scan the file
+ * ends in is what the file kept of it less the file's last two bytes (which the container stores as they are); the kernel writes that
+ * scan whole -- its out_cap is its geometry's -- and its FIRST file_len bytes are the ones to compare. */
 int lep_jpeg_plan_progressive_check(lep_jpeg *j, size_t jpeg_len, lep_huffprog_image *image, lep_huffprog_scan *scans,
                                     uint32_t *file_first, uint32_t *file_len, int cap, int *nscan, int *eligible);
+int lep_jpeg_plan_progressive_check_cut(lep_jpeg *j, size_t jpeg_len, lep_huffprog_image *image, lep_huffprog_scan *scans,
+                                        uint32_t *file_first, uint32_t *file_len, int cap, int *nscan, int *eligible);
 int lep_jpeg_scan_bytes(const lep_jpeg *j, const uint8_t **data, size_t *len);
 /* The restart markers of a file lep_jpeg_open_gpu flagged LEP_HUFFDEC_RST_TABLE: the offset in the un-stuffed scan bytes at which
  * each stood.  The caller puts them, as uint32, at scan + LEP_HUFFDEC_SCAN_ROOM(scan_len) on the device. */
@@ -373,6 +399,10 @@ int lep_jpeg_finish_gpu(lep_jpeg *j, const lep_huffdec_row *rows);
 void lep_jpeg_close(lep_jpeg *j);
 int lep_jpeg_describe(const lep_jpeg *j, lep_image_desc *desc);          /* host pointers into j */
 int lep_jpeg_is_progressive(const lep_jpeg *j);   /* 1: not a single interleaved sequential scan (needs the progressive re-coder) */
+/* A file that ends inside its scan, parsed by the host parser (lep_jpeg_open and its kin): 1 when the block that met the end of the data had
+ * failed to decode -- bits that are no code, a run that leaves its band -- and was kept all the same, as the reference keeps it; 0 otherwise,
+ * and for every file a GPU scan decoder finished.  Those decoders leave exactly such files to the host parser. */
+int lep_jpeg_cut_block_irregular(const lep_jpeg *j);
 /* segment choice of write_ujpg (src/lepton/jpgcoder.cc:3856-3934); returns count, fills segs */
 int lep_jpeg_plan(const lep_jpeg *j, int max_threads, lep_segment *segs, int image_index);
 /* -maxencodethreads / -minencodethreads / -evensplit (jpgcoder.cc:1064-1095): they change how many thread segments a file gets
@@ -436,6 +466,10 @@ int lep_jpeg_plan_scan_check(lep_jpeg *j, size_t jpeg_len, lep_huff_image *image
                              int *nseg, int *eligible);
 int lep_jpeg_scan_file_range(const lep_jpeg *j, uint32_t *first, uint32_t *len);
 int lep_file_recode_plan_progressive(lep_file *f, lep_huffprog_image *image, lep_huffprog_scan *scans, int cap, int *nscan, int *gpu_ok);
+/* The same, and progressive files that END INSIDE A SCAN too (the plain entry answers *gpu_ok = 0 for those, as it always has): for a caller
+ * that sizes its slots by the descriptors' out_cap / file_bound -- the cut scan's are its geometry's, not the file's -- and clears the frame
+ * behind coded_blocks of a file of one thread segment (lep_huffprog_image, above).  lep_decompress_batch is that caller. */
+int lep_file_recode_plan_progressive_cut(lep_file *f, lep_huffprog_image *image, lep_huffprog_scan *scans, int cap, int *nscan, int *gpu_ok);
 int lep_file_recode_finish_progressive(lep_file *f, const lep_bytes *scan_bytes, int nscan, lep_bytes *out);
 
 

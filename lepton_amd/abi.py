@@ -235,6 +235,8 @@ def lib():
         L.lep_compress.argtypes = [vp, vp, C.c_size_t, P(Bytes)]
         L.lep_decompress.argtypes = [vp, vp, C.c_size_t, P(Bytes)]
         L.lep_jpeg_is_progressive.argtypes = [vp]
+        if hasattr(L, "lep_jpeg_cut_block_irregular"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_jpeg_cut_block_irregular.argtypes = [vp]
         L.lep_compress_batch.argtypes = [vp, P(Bytes), C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(BatchStats)]
         if hasattr(L, "lep_compress_batch_slices"):   # (absent from an older build named by LEP_LIB_PATH)
             L.lep_compress_batch_slices.argtypes = [vp, P(Bytes), P(Slice), C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(BatchStats)]
@@ -253,6 +255,11 @@ def lib():
         L.lep_batch_footprint.restype = None
         L.lep_file_recode_plan_progressive.argtypes = [vp, P(HuffProgImage), P(HuffProgScan), C.c_int, P(C.c_int), P(C.c_int)]
         L.lep_file_recode_finish_progressive.argtypes = [vp, P(Bytes), C.c_int, P(Bytes)]
+        if hasattr(L, "lep_file_recode_plan_progressive_cut"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_file_recode_plan_progressive_cut.argtypes = [vp, P(HuffProgImage), P(HuffProgScan), C.c_int, P(C.c_int), P(C.c_int)]
+            L.lep_gpu_cut_progressive.argtypes = [vp, C.c_int]
+            L.lep_jpeg_open_gpu_progressive_cut.argtypes = [vp, P(HuffProgDecScan), C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
+            L.lep_jpeg_plan_progressive_check_cut.argtypes = [vp, C.c_size_t, P(HuffProgImage), P(HuffProgScan), P(C.c_uint32), P(C.c_uint32), C.c_int, P(C.c_int), P(C.c_int)]
         L.lep_gpu_huffman_progressive_encode_device.argtypes = [vp, P(HuffProgImage), C.c_int, P(HuffProgScan), C.c_int, vp, vp, vp, vp]
         if hasattr(L, "lep_gpu_huffman_progressive_encode_forms"):   # (absent from an older build named by LEP_LIB_PATH)
             L.lep_gpu_huffman_progressive_encode_forms.argtypes = [vp, P(C.c_uint32 * 4)]   # scans of the last call by writer: lane, lane with intervals, wavefront, sequential
@@ -297,4 +304,5 @@ EXPORTS = [
     "lep_gpu_huffman_progressive_encode_forms", "lep_compress_batch_slices",
     "lep_gpu_decode_rows_begin", "lep_gpu_decode_rows_advance", "lep_gpu_decode_rows_end", "lep_decompress_stream",
     "lep_gpu_pack_device", "lep_gpu_stream_pack", "lep_file_recode_head", "lep_decompress_batch_stream",
+    "lep_jpeg_cut_block_irregular", "lep_file_recode_plan_progressive_cut", "lep_jpeg_plan_progressive_check_cut", "lep_jpeg_open_gpu_progressive_cut", "lep_gpu_cut_progressive",
 ]

@@ -137,6 +137,10 @@ class GpuCodec:
         if rc:
             raise LeptonError(rc, "lep_gpu_create (no gfx950 device / HIP runtime: there is no CPU fallback)")
 
+    def cut_progressive(self, on=True):
+        """lep_gpu_cut_progressive: the batch calls of this codec take progressive files that end inside a scan on the scan kernels"""
+        return self._L.lep_gpu_cut_progressive(self.handle, 1 if on else 0)
+
     def last_error(self):
         return (self._L.lep_gpu_last_error(self.handle) or b"").decode()
 

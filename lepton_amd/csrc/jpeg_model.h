@@ -89,6 +89,7 @@ struct JpegFile {
     std::vector<std::vector<uint32_t>> scan_rst_pos;   // every scan: the same offsets, relative to the scan's own first byte (scan_start)
     std::vector<uint8_t> rst_err;   // wrongly placed RST markers at scan end, per scan
     bool early_eof = false;
+    bool cut_block_irregular = false;   // parse_jpeg only: the block that met the end of the data had FAILED to decode and was kept all the same (lep_jpeg_cut_block_irregular)
     int padbit = -1;
     // -startbyte=<n> (jpgcoder.cc:364, 1132-1133, 3801-3843): the .lep restores only the bytes from start_byte on; set before
     // parse_jpeg.  prefix_garbage = the raw bytes from start_byte up to the first MCU row that starts at or after it.
@@ -189,7 +190,7 @@ struct ProgScanDecodePlan {
 };
 // after parse_jpeg_prepare_gpu said "not eligible" for a progressive file: one plan per scan (t.scan = offset into jf->scan as a
 // pointer-sized integer, t.scan_len, t.rows_off / result_off relative to the file's first record; rows_needed records in all)
-int parse_jpeg_prepare_gpu_progressive(JpegFile* jf, std::vector<ProgScanDecodePlan>* scans, int* rows_needed, bool* eligible);
+int parse_jpeg_prepare_gpu_progressive(JpegFile* jf, std::vector<ProgScanDecodePlan>* scans, int* rows_needed, bool* eligible, bool allow_cut = false);   // allow_cut: files that end inside a scan too
 int parse_jpeg_finish_gpu_progressive(JpegFile* jf, const std::vector<ProgScanDecodePlan>& scans, const ScanDecodeRow* rows);
 uint64_t prog_wait_timeouts();   // scans that ended with status 4 (gave up waiting) since the process started
 

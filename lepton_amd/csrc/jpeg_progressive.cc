@@ -188,7 +188,7 @@ int decode_progressive_scan(JpegFile* jf, BitReader& br, int* lastdc, int* sta_i
                 const int old_mcu = mcu;
                 if (sta != -1) sta = next_mcupos(*jf, &mcu, &cmp, &csc, &sub, &dpos, &rstw, jf->cs_cmpc);
                 if (mcu % jf->mcuh == 0 && old_mcu != mcu) *do_handoff = true;
-                if (br.eof) { sta = 2; break; }
+                if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
             }
         } else {
             while (sta == 0) {
@@ -196,7 +196,7 @@ int decode_progressive_scan(JpegFile* jf, BitReader& br, int* lastdc, int* sta_i
                 const int bit = (int)br.read(1);
                 dc_of(cmp, dpos) = (int16_t)(dc_of(cmp, dpos) + (int16_t)(bit << sal));
                 sta = next_mcupos(*jf, &mcu, &cmp, &csc, &sub, &dpos, &rstw, jf->cs_cmpc);
-                if (br.eof) { sta = 2; break; }
+                if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
             }
         }
     } else if (to == 0) {    // non-interleaved DC
@@ -214,7 +214,7 @@ int decode_progressive_scan(JpegFile* jf, BitReader& br, int* lastdc, int* sta_i
                 dc_of(cmp, dpos) = (int16_t)((uint16_t)v << sal);
                 if (sta != -1) sta = next_mcuposn(*jf, cmp, &dpos, &rstw);
                 if (cmp == 0 && dpos % jf->comp[cmp].bch == 0) *do_handoff = true;
-                if (br.eof) { sta = 2; break; }
+                if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
             }
         } else {
             while (sta == 0) {
@@ -222,7 +222,7 @@ int decode_progressive_scan(JpegFile* jf, BitReader& br, int* lastdc, int* sta_i
                 const int bit = (int)br.read(1);
                 dc_of(cmp, dpos) = (int16_t)(dc_of(cmp, dpos) + (int16_t)(bit << sal));
                 sta = next_mcuposn(*jf, cmp, &dpos, &rstw);
-                if (br.eof) { sta = 2; break; }
+                if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
             }
         }
     } else {                 // non-interleaved AC
@@ -237,7 +237,7 @@ int decode_progressive_scan(JpegFile* jf, BitReader& br, int* lastdc, int* sta_i
                 if (eob < 0) sta = -1;
                 else sta = skip_eobrun(*jf, cmp, &dpos, &rstw, &eobrun);
                 if (sta == 0) sta = next_mcuposn(*jf, cmp, &dpos, &rstw);
-                if (br.eof) { sta = 2; break; }
+                if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
             }
         } else {
             while (sta == 0) {
@@ -256,7 +256,7 @@ int decode_progressive_scan(JpegFile* jf, BitReader& br, int* lastdc, int* sta_i
                 for (int b = from; b <= to; ++b) dst[kZigzagToAligned[b]] = (int16_t)(dst[kZigzagToAligned[b]] + (int16_t)((uint16_t)blk[b] << sal));
                 if (eob < 0) sta = -1;
                 else sta = next_mcuposn(*jf, cmp, &dpos, &rstw);
-                if (br.eof) { sta = 2; break; }
+                if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
             }
         }
     }
@@ -515,11 +515,11 @@ int recode_progressive(LepFile* lf, std::vector<uint8_t>* result) {
 }
 
 // ---- the same with the scans coded on the GPU (lep_huffprog.h) ---------------------------------------------------------------------
-int recode_progressive_prepare(LepFile* lf, ProgPlan* plan) {
+int recode_progressive_prepare(LepFile* lf, ProgPlan* plan, bool allow_cut) {
     plan->gpu_ok = false;
     plan->scans.clear(); plan->scan_hdr_end.clear(); plan->markers.clear();
     if (lf->flag == 'Z' || (lf->flag & 1) == ('Y' & 1)) return 0;   // the baseline re-coder's files
-    if (int rc = progressive_plan(&lf->jpeg, lf->jpeg_size, lf->rst_cnt_set, plan)) return rc;   // (what is wrong with the tables comes first, as in recode_progressive)
+    if (int rc = progressive_plan(&lf->jpeg, lf->jpeg_size, lf->rst_cnt_set, plan, allow_cut)) return rc;   // (what is wrong with the tables comes first, as in recode_progressive)
     if ((int32_t)lf->jpeg_size <= (int32_t)lf->jpeg.garbage.size()) return EX_ASSERTION_FAILURE;
     return 0;
 }
@@ -528,17 +528,23 @@ int recode_progressive_prepare(LepFile* lf, ProgPlan* plan) {
 // compressor's round-trip check (lep_batch.hip: the scans of the frame it has just coded are written again on the GPU and
 // compared with the file's own bytes).  Walks the header's DHT / DRI / SOS segments once more, leaving the tables in their
 // end-of-file state (what the parser left them in).
-int progressive_plan(JpegFile* jfp, size_t jpeg_size, bool rst_cnt_set, ProgPlan* plan) {
+int progressive_plan(JpegFile* jfp, size_t jpeg_size, bool rst_cnt_set, ProgPlan* plan, bool allow_cut) {
     JpegFile& jf = *jfp;
     plan->gpu_ok = false;
     plan->scans.clear(); plan->scan_hdr_end.clear(); plan->markers.clear();
     // eligibility: whole progressive frames of up to three components; everything else keeps the host coder
     // (... and SEQUENTIAL frames coded in several scans: the same walk, every scan a descriptor with from 0 / to 63 that the sequential scan
     // encoders write -- lep_huffprog.h sequential_scan_segment)
+    // (... and progressive files that END INSIDE A SCAN, early_eof: the reference writes every scan whole from the frame -- zero behind the
+    // cut -- and lets the byte bound cut the output, as recode_progressive_finish does.  Their caps: below.  Restart intervals in such a
+    // file, and cut sequential frames in several scans, keep the host coder -- as does every such file for a caller that did not say
+    // allow_cut: it has to size its slots by the caps below, and to clear the lazy tail of a file of one thread segment, lep_batch.hip)
     const bool sequential = jf.jpegtype == 1;
-    bool ok = (jf.jpegtype == 2 || sequential) && !jf.early_eof && jf.ncomp >= 1 && jf.ncomp <= 3 && jf.mcuh > 0 && jf.mcuv > 0;
-    for (int c = 0; c < jf.ncomp; ++c) ok = ok && jf.trunc_bcv[c] >= jf.comp[c].bcv && jf.comp[c].nch > 0 && jf.comp[c].ncv > 0;
+    const bool cut = jf.early_eof;
+    bool ok = (jf.jpegtype == 2 || sequential) && !(cut && (sequential || !allow_cut)) && jf.ncomp >= 1 && jf.ncomp <= 3 && jf.mcuh > 0 && jf.mcuv > 0;
+    for (int c = 0; c < jf.ncomp; ++c) ok = ok && (cut || jf.trunc_bcv[c] >= jf.comp[c].bcv) && jf.comp[c].nch > 0 && jf.comp[c].ncv > 0;
     if (!ok) return 0;
+    size_t geo_last = 0;
     ProgImage& im = plan->image;
     memset(&im, 0, sizeof im);
     im.ncomp = jf.ncomp; im.mcuh = jf.mcuh; im.mcuv = jf.mcuv; im.mcuc = jf.mcuc; im.padbit = jf.padbit;
@@ -563,6 +569,7 @@ int progressive_plan(JpegFile* jfp, size_t jpeg_size, bool rst_cnt_set, ProgPlan
         if (type != 0xDA) break;
         plan->scan_hdr_end.push_back(hpos);
         rsti_seen = jf.rsti;
+        if (cut && jf.rsti > 0) return 0;
         ProgScan sc;
         memset(&sc, 0, sizeof sc);
         sc.rsti = jf.rsti;                                     // (a DRI in front of any scan: phone cameras set one per scan -- the reference's androidprogressive.jpg, iphoneprogressive2.jpg)
@@ -615,6 +622,7 @@ int progressive_plan(JpegFile* jfp, size_t jpeg_size, bool rst_cnt_set, ProgPlan
         if (rst_cnt_set && nmark > 0 && !(jf.rst_cnt.size() > scan_index && nmark <= jf.rst_cnt[scan_index])) return 0;   // markers withheld: host
         plan->markers.push_back((uint32_t)nmark);
         const size_t geo = blocks * ((dc && !sequential) ? 8 : 432) + nmark * 2 + units / 4 + 64;
+        geo_last = geo;
         sc.out_cap = (uint32_t)std::min<size_t>(std::min<size_t>(jpeg_size + 16, geo), 0xfffffff0u);
         sc.corr_cap = (!dc && sc.sah != 0) ? (uint32_t)std::min<size_t>(blocks * 2 + 8, 0x7fffffffu) : 0u;
         sc.file_bound = (uint32_t)std::min<size_t>(jpeg_size + 16, 0xfffffff0u);   // what ALL scans of the file come to at most: they are parts of it
@@ -622,6 +630,15 @@ int progressive_plan(JpegFile* jfp, size_t jpeg_size, bool rst_cnt_set, ProgPlan
         if (plan->scans.size() > 256) return 0;
     }
     if (plan->scans.empty()) return 0;
+    if (cut) {
+        // Sizes derived from the file's byte count do not hold for the scan the file ends in: written whole, it can be many times what the
+        // file kept of it (a file cut in its first DC scan: a kilobyte of file, every block of the frame still to code).  That scan gets
+        // what its geometry bounds it by, and the file's region that much on top of what the whole scans in front took: "outgrew" must
+        // not be raised by the tail nobody keeps.
+        plan->scans.back().out_cap = (uint32_t)std::min<size_t>(geo_last, 0xfffffff0u);
+        const uint32_t region = (uint32_t)std::min<size_t>(jpeg_size + 16 + geo_last, 0xfffffff0u);
+        for (ProgScan& sc : plan->scans) sc.file_bound = region;
+    }
     im.rsti = jf.rsti;
     plan->gpu_ok = true;
     return 0;

@@ -537,7 +537,7 @@ static int decode_scans(JpegFile* jf, bool allow_progressive) {
                     if (eob < 0) sta = -1;
                     else sta = next_mcupos(*jf, &mcu, &cmp, &csc, &sub, &dpos, &rstw, jf->cs_cmpc);
                     if (mcu % jf->mcuh == 0 && old_mcu != mcu) do_handoff = true;
-                    if (br.eof) { sta = 2; break; }
+                    if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
                 }
             } else if (jf->jpegtype == 1) {
                 const int vmul = jf->comp[0].bcv / jf->mcuv, hmul = jf->comp[0].bch / jf->mcuh;
@@ -556,7 +556,7 @@ static int decode_scans(JpegFile* jf, bool allow_progressive) {
                     else sta = next_mcuposn(*jf, cmp, &dpos, &rstw);
                     mcu = dpos / (hmul * vmul);
                     if (cmp == 0 && (mcu % jf->mcuh == 0) && (dpos % (hmul * vmul) == 0)) do_handoff = true;
-                    if (br.eof) { sta = 2; break; }
+                    if (br.eof) { if (sta == -1) jf->cut_block_irregular = true; sta = 2; break; }
                 }
             } else {
                 int rc = decode_progressive_scan(jf, br, lastdc, &sta, &cmp, &dpos, &mcu, &csc, &sub, &rstw, &eobrun,
@@ -950,11 +950,16 @@ static int finish_gpu_sequential_scans(JpegFile* jf, const std::vector<ProgScanD
     return 0;
 }
 
-int parse_jpeg_prepare_gpu_progressive(JpegFile* jf, std::vector<ProgScanDecodePlan>* scans, int* rows_needed, bool* eligible) {
+int parse_jpeg_prepare_gpu_progressive(JpegFile* jf, std::vector<ProgScanDecodePlan>* scans, int* rows_needed, bool* eligible, bool allow_cut) {
     *eligible = false;
     scans->clear();
     if (jf->jpegtype == 1) return prepare_gpu_sequential_scans(jf, scans, rows_needed, eligible);
-    if (jf->early_eof || jf->jpegtype != 2 || jf->ncomp < 1 || jf->ncomp > 3 || jf->scan.empty() || jf->start_byte) return 0;
+    // (a file that ends inside a scan -- early_eof, no EOI: only its LAST scan can meet the end of the data, every scan in front of it is
+    // whole and none depends on it.  That scan carries kScanEarlyEof: the window decoder, the one form that knows the cut, decodes up to the
+    // block that reads the data's last bit and says how far it came; anything odd in that block is left to the host parser.  A restart
+    // interval anywhere keeps such a file on the host -- and so does a caller that did not say allow_cut: it may launch the descriptors
+    // through kernels of its own choosing, and only the window form knows the flag)
+    if ((jf->early_eof && !allow_cut) || jf->jpegtype != 2 || jf->ncomp < 1 || jf->ncomp > 3 || jf->scan.empty() || jf->start_byte) return 0;
     const uint8_t* h = jf->hdr.data();
     const size_t hdrs = jf->hdr.size();
     size_t hpos = 0;
@@ -1044,6 +1049,11 @@ int parse_jpeg_prepare_gpu_progressive(JpegFile* jf, std::vector<ProgScanDecodeP
         scans->push_back(sc);
     }
     if (scans->empty() || scans->size() != jf->scan_start.size()) return 0;
+    if (jf->early_eof) {
+        for (const ProgScanDecodePlan& sc : *scans) if (sc.t.rsti > 0) return 0;
+        if (scans->back().t.scan_len >= (1u << 27)) return 0;                   // (prog_win_takes)
+        scans->back().t.flags |= kScanEarlyEof;
+    }
     *rows_needed = nrows + 1 + (int)scans->size();
     *eligible = true;
     return 0;
@@ -1058,11 +1068,21 @@ int parse_jpeg_finish_gpu_progressive(JpegFile* jf, const std::vector<ProgScanDe
     const int luma_mul = jf->comp[0].bcv / jf->mcuv;
     int padbit = -1;
     jf->max_bpos = 0; jf->max_sah = 0; jf->max_cmp = 0;
+    // A file that ends inside its last scan: that scan's final record says kScanRowTruncated and, in bitpos, the blocks of the scan's order
+    // up to and including the one that read the data's last bit (a scan of one component: the position that block started at, + 1).  Any
+    // other scan that says so, a count of no block or of more than the scan has, or a file that is whole: the host parser's.
+    bool truncated = false;
+    uint32_t done = 0;
     for (size_t k = 0; k < scans.size(); ++k) {
         const ScanDecodeRow& fin = rows[scans[k].result_off];
-        if ((fin.aux >> 8) == 4) g_prog_wait_timeouts.fetch_add(1, std::memory_order_relaxed);
-        if (fin.aux >> 8) return -1;                                       // irregular somewhere in this scan
-        if (fin.bitpos != scans[k].t.scan_len * 8u) return -1;
+        if (fin.aux < 0) return -1;                                        // not written: no kernel took the scan (ProgDecPlan::declined)
+        const int status = (fin.aux >> 8) & 0x3fffff;
+        if (status == 4) g_prog_wait_timeouts.fetch_add(1, std::memory_order_relaxed);
+        if (status) return -1;                                             // irregular somewhere in this scan
+        if (fin.aux & kScanRowTruncated) {
+            if (!jf->early_eof || k + 1 != scans.size() || !(scans[k].t.flags & kScanEarlyEof) || fin.bitpos == 0) return -1;
+            truncated = true; done = fin.bitpos;
+        } else if (fin.bitpos != scans[k].t.scan_len * 8u) return -1;
         const int pb = (int8_t)(fin.aux & 255);
         if (pb != -1) { if (padbit == -1) padbit = pb; else if (padbit != pb) return -1; }   // "inconsistent use of padbits"
         jf->max_bpos = std::max(jf->max_bpos, scans[k].to);
@@ -1070,7 +1090,22 @@ int parse_jpeg_finish_gpu_progressive(JpegFile* jf, const std::vector<ProgScanDe
         for (int i = 0; i < scans[k].cmpc; ++i) jf->max_cmp = std::max(jf->max_cmp, scans[k].cmp[i]);
     }
     const ProgScanDecodePlan& first = scans[0];
-    const int row_count = first.cmpc > 1 ? jf->mcuv : jf->comp[0].ncv;   // rows the first scan started
+    const ProgScanDecodePlan& last = scans.back();
+    int nphase = 0;                                                        // blocks of an MCU of the last scan
+    for (int i = 0; i < last.cmpc; ++i) {
+        if (last.cmp[i] < 0 || last.cmp[i] >= jf->ncomp) return -1;
+        nphase += jf->comp[last.cmp[i]].mbs;
+    }
+    if (jf->mcuh < 1 || nphase < 1) return -1;
+    if (truncated) {
+        const uint64_t all = last.cmpc > 1 ? (uint64_t)jf->mcuc * (uint64_t)nphase : (uint64_t)jf->comp[last.cmp[0]].bc;
+        if (done > all) return -1;
+    }
+    int row_count = first.cmpc > 1 ? jf->mcuv : jf->comp[0].ncv;         // rows the first scan started
+    if (truncated && scans.size() == 1) {                                  // ... the rows it entered before the data ended
+        const int entered = first.cmpc > 1 ? (int)(((done - 1) / (uint32_t)nphase) / (uint32_t)jf->mcuh) + 1 : (int)((done - 1) / (uint32_t)jf->comp[0].bch) + 1;
+        row_count = std::min(row_count, entered);
+    }
     jf->rows.clear();
     const auto& offs = jf->scan_to_file;
     auto record = [&](uint32_t bit_in_all, const int16_t* last_dc, int mcu_y) {
@@ -1094,16 +1129,37 @@ int parse_jpeg_finish_gpu_progressive(JpegFile* jf, const std::vector<ProgScanDe
         if (rows[r].bitpos > first.t.scan_len * 8u) return -1;
         record(base0 + rows[r].bitpos, rows[r].last_dc, r);
     }
-    // the record after the last scan (decode_scans' final make_handoff): end of all data, the last scan's DC predictors, and
-    // the MCU row its MCU counter stood at -- which only interleaved scans advance
-    const ProgScanDecodePlan& last = scans.back();
+    // the record after the last scan (decode_scans' final make_handoff): end of all data (a cut scan: the reader has read every bit, nothing
+    // overhangs), the last scan's DC predictors, and the MCU row its MCU counter stood at -- which only interleaved scans advance
     const ScanDecodeRow& fin = rows[last.result_off];
-    record((uint32_t)jf->scan.size() * 8u, fin.last_dc, last.cmpc > 1 ? jf->mcuc / jf->mcuh : 0);
+    const int mcu_after = last.cmpc > 1 ? (truncated ? (int)(done / (uint32_t)nphase) : jf->mcuc) : 0;
+    record((uint32_t)jf->scan.size() * 8u, fin.last_dc, mcu_after / jf->mcuh);
     for (size_t i = 1; i < jf->rows.size(); ++i)
         if (jf->rows[i].luma_y_start < jf->rows[i - 1].luma_y_end) jf->rows[i].luma_y_start = jf->rows[i - 1].luma_y_end;
-    jf->padbit = (int8_t)padbit;
+    jf->padbit = (int8_t)padbit;                                           // (a cut scan adds nothing: unpad returns the fill bit unchanged at the end of the data)
     jf->scan_count = (int)scans.size();
+    // max_dpos: the largest position at which a block of the component started (decode_scans notes it in front of every block, over all
+    // scans).  The first scan covers every component whole unless it is the cut one
     for (int c = 0; c < jf->ncomp; ++c) jf->max_dpos[c] = jf->comp[c].bc - 1;
+    if (truncated && scans.size() == 1) {
+        if (first.cmpc == 1) jf->max_dpos[first.cmp[0]] = (int)done - 1;
+        else {
+            const uint32_t mcu_last = (done - 1) / (uint32_t)nphase;
+            const int row = (int)(mcu_last / (uint32_t)jf->mcuh);
+            for (int c = 0; c < jf->ncomp; ++c) jf->max_dpos[c] = row > 0 ? row * jf->comp[c].vs * jf->comp[c].bch - 1 : 0;
+            for (uint32_t b = (uint32_t)row * (uint32_t)jf->mcuh * (uint32_t)nphase; b < done; ++b) {
+                const int mx = (int)((b / (uint32_t)nphase) % (uint32_t)jf->mcuh);
+                int ph = (int)(b % (uint32_t)nphase);
+                for (int ci = 0; ci < first.cmpc; ++ci) {
+                    const int c = first.cmp[ci];
+                    const Component& q = jf->comp[c];
+                    if (ph < q.mbs) { jf->max_dpos[c] = std::max(jf->max_dpos[c], (row * q.vs + ph / q.hs) * q.bch + mx * q.hs + ph % q.hs); break; }
+                    ph -= q.mbs;
+                }
+            }
+        }
+    }
+    if (jf->early_eof) note_truncation(jf);
     jf->progressive_needed = true;
     return 0;
 }

@@ -116,17 +116,23 @@ int lep_jpeg_open_embedded(const uint8_t* blob, size_t len, size_t offset, lep_j
 int lep_jpeg_open_gpu(const uint8_t* jpg, size_t len, lep_jpeg** out, lep_huffdec_image* image, int* eligible) {
     return lep_jpeg_open_gpu_slice(jpg, len, 0, out, image, eligible);
 }
-int lep_jpeg_open_gpu_progressive(lep_jpeg* j, lep_huffprogdec_scan* scans, int cap, int* nscan, int* rows_needed, int* eligible) {
+static int open_gpu_progressive(lep_jpeg* j, lep_huffprogdec_scan* scans, int cap, int* nscan, int* rows_needed, int* eligible, bool allow_cut) {
     *eligible = 0; *nscan = 0; *rows_needed = 0;
     std::vector<lep::ProgScanDecodePlan> v;
     bool ok = false;
     int need = 0;
-    int rc = lep::parse_jpeg_prepare_gpu_progressive(&j->jf, &v, &need, &ok);
+    int rc = lep::parse_jpeg_prepare_gpu_progressive(&j->jf, &v, &need, &ok, allow_cut);
     if (rc) return rc;
     if (!ok || (int)v.size() > cap) return 0;
     memcpy(scans, v.data(), v.size() * sizeof(lep_huffprogdec_scan));
     *nscan = (int)v.size(); *rows_needed = need; *eligible = 1;
     return 0;
+}
+int lep_jpeg_open_gpu_progressive(lep_jpeg* j, lep_huffprogdec_scan* scans, int cap, int* nscan, int* rows_needed, int* eligible) {
+    return open_gpu_progressive(j, scans, cap, nscan, rows_needed, eligible, false);
+}
+int lep_jpeg_open_gpu_progressive_cut(lep_jpeg* j, lep_huffprogdec_scan* scans, int cap, int* nscan, int* rows_needed, int* eligible) {
+    return open_gpu_progressive(j, scans, cap, nscan, rows_needed, eligible, true);
 }
 int lep_jpeg_finish_gpu_progressive(lep_jpeg* j, const lep_huffprogdec_scan* scans, int nscan, const lep_huffdec_row* rows) {
     if (nscan <= 0 || !scans || !rows) return LEP_ASSERTION_FAILURE;   // (public entry: v[0] is read below)
@@ -137,24 +143,36 @@ int lep_jpeg_finish_gpu_progressive(lep_jpeg* j, const lep_huffprogdec_scan* sca
     for (auto& sc : v) { sc.result_off -= rows0; sc.t.rows_off -= rows0; }
     return lep::parse_jpeg_finish_gpu_progressive(&j->jf, v, reinterpret_cast<const lep::ScanDecodeRow*>(rows) + rows0) ? LEP_UNSUPPORTED_JPEG : 0;
 }
-int lep_jpeg_plan_progressive_check(lep_jpeg* j, size_t jpeg_len, lep_huffprog_image* image, lep_huffprog_scan* scans, uint32_t* file_first,
-                                    uint32_t* file_len, int cap, int* nscan, int* eligible) {
+static int plan_progressive_check(lep_jpeg* j, size_t jpeg_len, lep_huffprog_image* image, lep_huffprog_scan* scans, uint32_t* file_first,
+                                  uint32_t* file_len, int cap, int* nscan, int* eligible, bool allow_cut) {
     *eligible = 0; *nscan = 0;
     lep::ProgPlan plan;
     // (rst_cnt as the parser counted it: a scan that holds fewer restart markers than its length asks for is not planned)
-    if (lep::progressive_plan(&j->jf, jpeg_len, true, &plan) || !plan.gpu_ok) return 0;
+    if (lep::progressive_plan(&j->jf, jpeg_len, true, &plan, allow_cut) || !plan.gpu_ok) return 0;
     const size_t n = plan.scans.size();
     if ((int)n > cap || n != j->jf.scan_file_range.size()) return 0;
     for (size_t q = 0; q < n; ++q) {
         const auto& r = j->jf.scan_file_range[q];
-        if (r.second <= r.first || r.second > jpeg_len) return 0;
-        file_first[q] = r.first; file_len[q] = r.second - r.first;
+        size_t end = r.second;
+        // (the scan a file ENDS in: written whole from the frame it is longer than what the file kept of it, and the check holds it against
+        // the file's bytes up to the cut -- less the file's last two, which the container keeps as they are, lep_container.cc's garbage)
+        if (j->jf.early_eof && q + 1 == n) end = jpeg_len > j->jf.garbage.size() ? jpeg_len - j->jf.garbage.size() : 0;
+        if (end <= r.first || end > jpeg_len) return 0;
+        file_first[q] = r.first; file_len[q] = (uint32_t)(end - r.first);
     }
     memcpy(image, &plan.image, sizeof *image);
     memcpy(scans, plan.scans.data(), sizeof(lep_huffprog_scan) * n);
     *nscan = (int)n;
     *eligible = 1;
     return 0;
+}
+int lep_jpeg_plan_progressive_check(lep_jpeg* j, size_t jpeg_len, lep_huffprog_image* image, lep_huffprog_scan* scans, uint32_t* file_first,
+                                    uint32_t* file_len, int cap, int* nscan, int* eligible) {
+    return plan_progressive_check(j, jpeg_len, image, scans, file_first, file_len, cap, nscan, eligible, false);
+}
+int lep_jpeg_plan_progressive_check_cut(lep_jpeg* j, size_t jpeg_len, lep_huffprog_image* image, lep_huffprog_scan* scans, uint32_t* file_first,
+                                        uint32_t* file_len, int cap, int* nscan, int* eligible) {
+    return plan_progressive_check(j, jpeg_len, image, scans, file_first, file_len, cap, nscan, eligible, true);
 }
 int lep_jpeg_scan_bytes(const lep_jpeg* j, const uint8_t** data, size_t* len) {
     *data = j->jf.scan.data(); *len = j->jf.scan.size();
@@ -202,6 +220,7 @@ int lep_jpeg_set_container_version(lep_jpeg* j, int version) {
 int lep_container_can_write_version(int version) { return version == 1 || (version == 2 && lep::brotli_encoder_available()) ? 1 : 0; }
 
 int lep_jpeg_is_progressive(const lep_jpeg* j) { return j->jf.progressive_needed ? 1 : 0; }
+int lep_jpeg_cut_block_irregular(const lep_jpeg* j) { return j && j->jf.cut_block_irregular ? 1 : 0; }
 
 int lep_jpeg_plan(const lep_jpeg* j, int max_threads, lep_segment* segs, int image_index) {
     lep::EncodeOptions o = j->opt;
@@ -498,9 +517,9 @@ int lep_file_recode_head(const lep_file* f, const uint8_t** data, size_t* len) {
     return 0;
 }
 
-int lep_file_recode_plan_progressive(lep_file* f, lep_huffprog_image* image, lep_huffprog_scan* scans, int cap, int* nscan, int* gpu_ok) {
+static int recode_plan_progressive(lep_file* f, lep_huffprog_image* image, lep_huffprog_scan* scans, int cap, int* nscan, int* gpu_ok, bool allow_cut) {
     *gpu_ok = 0; *nscan = 0;
-    int rc = lep::recode_progressive_prepare(&f->lf, &f->prog);
+    int rc = lep::recode_progressive_prepare(&f->lf, &f->prog, allow_cut);
     if (rc) return rc;
     f->prog_planned = true;
     if (!f->prog.gpu_ok || (int)f->prog.scans.size() > cap) { f->prog.gpu_ok = false; return 0; }
@@ -510,6 +529,13 @@ int lep_file_recode_plan_progressive(lep_file* f, lep_huffprog_image* image, lep
     *nscan = (int)f->prog.scans.size();
     *gpu_ok = 1;
     return 0;
+}
+
+int lep_file_recode_plan_progressive(lep_file* f, lep_huffprog_image* image, lep_huffprog_scan* scans, int cap, int* nscan, int* gpu_ok) {
+    return recode_plan_progressive(f, image, scans, cap, nscan, gpu_ok, false);
+}
+int lep_file_recode_plan_progressive_cut(lep_file* f, lep_huffprog_image* image, lep_huffprog_scan* scans, int cap, int* nscan, int* gpu_ok) {
+    return recode_plan_progressive(f, image, scans, cap, nscan, gpu_ok, true);
 }
 
 int lep_file_recode_finish_progressive(lep_file* f, const lep_bytes* scan_bytes, int nscan, lep_bytes* out) {

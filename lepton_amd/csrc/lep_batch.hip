@@ -92,10 +92,13 @@ __global__ void lep_compare_kernel(const uint4* __restrict__ a, const uint4* __r
 // with the file's own bytes of that scan (uploaded beside the un-stuffed copy the decoder read); any difference -- the
 // length, a byte, an encoder that gave up (bit 31 of its length) -- sets bit 1 of the image's flag word.
 struct ScanCheck { uint64_t out_off, ref_off; uint32_t ref_len, image; };
+constexpr uint32_t kScanCheckPrefix = 0x80000000u;   // ScanCheck::image: the scan a file ends in -- written whole, its first ref_len bytes are the file's
 __global__ void lep_scan_check_kernel(const uint8_t* __restrict__ out, const uint32_t* __restrict__ out_len, const uint8_t* __restrict__ ref,
                                       const ScanCheck* __restrict__ items, uint32_t* flags) {
-    const ScanCheck it = items[blockIdx.x];
-    bool diff = out_len[blockIdx.x] != it.ref_len;
+    ScanCheck it = items[blockIdx.x];
+    // (a prefix: what was written may well have outgrown a slot sized for the part the file kept; the bytes in front of that hold)
+    bool diff = (it.image & kScanCheckPrefix) ? (out_len[blockIdx.x] & 0x7fffffffu) < it.ref_len : out_len[blockIdx.x] != it.ref_len;
+    it.image &= ~kScanCheckPrefix;
     if (!diff) {
         const uint4* a = reinterpret_cast<const uint4*>(out + it.out_off);   // both 16-byte aligned
         const uint4* b = reinterpret_cast<const uint4*>(ref + it.ref_off);
@@ -322,6 +325,7 @@ struct BatchCall {
     int32_t* status = nullptr;
     int threads = 1;
     bool gpu_huffman = true;
+    bool cut_progressive = false;      // lep_gpu_cut_progressive: progressive files that end inside a scan take the scan kernels
     const bool trace = getenv("LEP_BATCH_TRACE") != nullptr;   // read once per call
     lep_batch_stats st;
     double t_pipe0 = 0;
@@ -402,13 +406,13 @@ int route_chunk(CompressCall& x, Chunk* c, Slot* s, std::vector<LiveImage>& imgs
             if (ok) { im.route = lepbatch::kSequential; return; }
             im.pscans.resize(64);
             int ns = 0, okp = 0;
-            if (!lep_jpeg_open_gpu_progressive(x.parsed[i], im.pscans.data(), 64, &ns, &im.prow_need, &okp) && okp) {
+            if (!(x.cut_progressive ? lep_jpeg_open_gpu_progressive_cut : lep_jpeg_open_gpu_progressive)(x.parsed[i], im.pscans.data(), 64, &ns, &im.prow_need, &okp) && okp) {
                 im.pscans.resize((size_t)ns);
                 if (!x.verify) { im.route = lepbatch::kProgressive; return; }
                 auto& pc = im.pchk;
                 pc.scans.resize((size_t)ns); pc.first.resize((size_t)ns); pc.len.resize((size_t)ns);
                 int nc = 0, okc = 0;
-                if (!lep_jpeg_plan_progressive_check(x.parsed[i], x.jpgs[i].len, &pc.img, pc.scans.data(), pc.first.data(), pc.len.data(), ns, &nc, &okc) &&
+                if (!(x.cut_progressive ? lep_jpeg_plan_progressive_check_cut : lep_jpeg_plan_progressive_check)(x.parsed[i], x.jpgs[i].len, &pc.img, pc.scans.data(), pc.first.data(), pc.len.data(), ns, &nc, &okc) &&
                     okc && nc == ns) { im.route = lepbatch::kProgressive; return; }
             }
             im.pscans.clear();
@@ -650,11 +654,13 @@ void plan_progressive_check(CompressCall& x, Chunk* c, Slot* s, const std::vecto
         for (size_t q = 0; q < im.pchk.scans.size(); ++q) {
             lep_huffprog_scan sc = im.pchk.scans[q];
             sc.image = (int32_t)c->pimg.size();
-            sc.out_cap = lepbatch::verify_out_cap(sc.out_cap, im.pchk.len[q]);
+            // (the scan a file ends in keeps the cap of its geometry: its writer's buffers are sized from it, and it is written whole)
+            const bool ends_here = q < im.pscans.size() && (im.pscans[q].t.flags & LEP_HUFFDEC_EARLY_EOF);
+            if (!ends_here) sc.out_cap = lepbatch::verify_out_cap(sc.out_cap, im.pchk.len[q]);
             sc.out_off = arena.place(sc.out_cap);
             sc.corr_off = (uint32_t)arena.place_corr(sc.corr_cap);
             c->pscan.push_back(sc);
-            c->pcheck.push_back(ScanCheck{sc.out_off, (uint64_t)im.scans[q].ref_off, im.pchk.len[q], (uint32_t)k});
+            c->pcheck.push_back(ScanCheck{sc.out_off, (uint64_t)im.scans[q].ref_off, im.pchk.len[q], (uint32_t)k | (ends_here ? kScanCheckPrefix : 0u)});
             c->pchecked[k] = 1;
         }
         c->pimg.push_back(pi);
@@ -996,6 +1002,7 @@ int lep_compress_batch_slices(lep_gpu* g, const lep_bytes* files, const lep_slic
     // WHILE the split-phase encoder's kernels of chunk k run.  The chunking itself is lep_batch_plan (lep_api.cc).
     x.verify = o && o->verify;
     x.gpu_huffman = !(o && o->host_huffman);
+    x.cut_progressive = lep_gpu_cut_progressive(g, -1) != 0;
     HIPOK(hipSetDevice(lep_gpu_device(g)));
     tune_malloc_for_pool();
     const double t_begin = now_s();
@@ -1179,7 +1186,7 @@ void plan_progressive_recode(DecompressCall& x, Chunk* c, Slot* s) {
         if (c->hfirst[k] >= 0) continue;
         lep_huffprog_image pi;
         int ns = 0, ok = 0;
-        if (lep_file_recode_plan_progressive(x.files[c->live[k]], &pi, tmp.data(), (int)tmp.size(), &ns, &ok) || !ok) continue;
+        if ((x.cut_progressive ? lep_file_recode_plan_progressive_cut : lep_file_recode_plan_progressive)(x.files[c->live[k]], &pi, tmp.data(), (int)tmp.size(), &ns, &ok) || !ok) continue;
         point_into_frame(pi.blocks, c->host_desc[k], s->d_frames + c->frame_off[k]);
         c->pfirst[k] = (int)c->pscan.size(); c->pcount[k] = ns;
         for (int q = 0; q < ns; ++q) {
@@ -1264,6 +1271,17 @@ int launch_decompress_chunk(DecompressCall& x, Chunk* c, Slot* s) {
     (void)lep_gpu_expect_company(x.g, 0);
     (void)lep_gpu_use_arena(x.g, 0);
     if (rc) return rc;
+    // A progressive file that ends inside a scan and was coded as ONE thread segment: the reference's re-coder reads zeros for every block at
+    // or behind trunc_bc -- even where the stream codes the first block of a later row (recode_progressive's lazy_tail).  The scan writers
+    // get the same view: those blocks are cleared behind the decode, in front of the scan launch.  Several segments: the frame as it is.
+    for (size_t k = 0; k < c->live.size(); ++k) {
+        if (c->pfirst[k] < 0 || c->seg_first[k + 1] - c->seg_first[k] != 1) continue;
+        const lep_image_desc& d = c->host_desc[k];
+        for (int cc = 0; cc < d.ncomp; ++cc) {
+            const int64_t all = (int64_t)d.width_blocks[cc] * d.height_blocks[cc], coded = d.coded_blocks[cc];
+            if (coded >= 0 && coded < all) HIPOK(hipMemsetAsync(c->dev_desc[k].blocks[cc] + coded * 64, 0, (size_t)(all - coded) * 128, s_compute));
+        }
+    }
     // NOT redundant: the scan encoders' descriptors live in ONE device buffer of the codec, whichever workspace set the decoder used (the
     // encoders always take set 0's).  A launch beside the previous one is on the other stream, so nothing else orders this chunk's
     // descriptor upload behind the previous chunk's encoders, which still read that buffer: this wait on the previous slot's `done` is
@@ -1414,6 +1432,7 @@ extern "C" int lep_decompress_batch(lep_gpu* g, const lep_bytes* leps, int n, le
     x.chunk_budget = o && o->chunk_frame_bytes ? o->chunk_frame_bytes : ((size_t)32 << 30);
     x.chunk_images = o && o->chunk_images > 0 ? (size_t)o->chunk_images : 1024;
     x.gpu_huffman = !(o && o->host_huffman);
+    x.cut_progressive = lep_gpu_cut_progressive(g, -1) != 0;
     HIPOK(hipSetDevice(lep_gpu_device(g)));
     tune_malloc_for_pool();
     const double t_begin = now_s();

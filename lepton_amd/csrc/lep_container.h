@@ -116,8 +116,9 @@ struct ProgPlan {
     std::vector<size_t> scan_hdr_end;     // header position behind each SOS
     std::vector<uint32_t> markers;        // restart markers each scan writes itself
 };
-int recode_progressive_prepare(LepFile* lf, ProgPlan* plan);
-int progressive_plan(JpegFile* jf, size_t jpeg_size, bool rst_cnt_set, ProgPlan* plan);
+// allow_cut: progressive files that end inside a scan are planned too (the caller knows what that asks of it: jpeg_progressive.cc)
+int recode_progressive_prepare(LepFile* lf, ProgPlan* plan, bool allow_cut = false);
+int progressive_plan(JpegFile* jf, size_t jpeg_size, bool rst_cnt_set, ProgPlan* plan, bool allow_cut = false);
 int recode_progressive_finish(LepFile* lf, const ProgPlan& plan, const std::vector<std::pair<const uint8_t*, size_t>>& scan_bytes,
                               std::vector<uint8_t>* out);
 int recode_finish(LepFile* lf, const RecodePlan& plan, const std::vector<std::pair<const uint8_t*, size_t>>& seg_bytes, const lep_huff_end* ends,

@@ -551,6 +551,7 @@ struct lep_gpu {
     int huffprog_simt = 1;              // LEP_HUFFPROG_SIMT=0: every progressive scan's bytes from the wavefront-per-scan kernel (lep_huffprog.h)
     int huffprog_simt_rst = 1;          // LEP_HUFFPROG_SIMT_RST=0: scans with a restart interval from the wavefront-per-scan kernel
     uint32_t huffprog_forms[4] = {0, 0, 0, 0};   // the last progressive write's scans by form: lane, lane with intervals, wavefront, sequential
+    int cut_progressive = 0;            // lep_gpu_cut_progressive / LEP_CUT_PROGRESSIVE=1: the batch calls take progressive files that end inside a scan on the scan kernels
     int stream_pack = 1;                // LEP_STREAM_PACK=0: lep_decompress_batch_stream fetches a band's bytes with one copy per segment, not packed (lep_pack.h)
     int huffenc_simt = 1;               // LEP_HUFFENC_SIMT=0: every segment's scan bytes from the wavefront-per-segment kernel (lep_huff.h)
     int simt_sub_bits = 0;              // LEP_HUFFDEC_SIMT_BITS: bits per subsequence of the lane-per-subsequence scan decoder (0 = from the launch's size)
@@ -1135,6 +1136,7 @@ int lep_gpu_create(int device, lep_gpu** out) {
     if (const char* e = getenv("LEP_HUFFDEC_SIMT_BITS")) g->simt_sub_bits = std::max(0, atoi(e));
     if (const char* e = getenv("LEP_HUFFENC_SIMT")) g->huffenc_simt = atoi(e) != 0;
     if (const char* e = getenv("LEP_STREAM_PACK")) g->stream_pack = atoi(e) != 0;
+    if (const char* e = getenv("LEP_CUT_PROGRESSIVE")) g->cut_progressive = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROG_SIMT")) g->huffprog_simt = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROG_SIMT_RST")) g->huffprog_simt_rst = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_WIN")) g->huffprogdec_win = atoi(e) != 0;
@@ -1380,6 +1382,7 @@ int lep_gpu_huffman_progressive_decode_device(lep_gpu* g, const lep_huffprogdec_
     lephuff::ProgDecPlan plan;
     if (lephuff::prog_dec_plan(reinterpret_cast<const lephuff::ProgDecScan*>(scans), nscan, o, &plan)) return LEP_ASSERTION_FAILURE;
     static_assert(sizeof(lep_huffdec_image) == sizeof(lephuff::HuffDecImage), "C ABI mirrors");
+    for (uint64_t at : plan.declined) HIPCHK(g, hipMemsetAsync(d_rows + at, lephuff::kProgDecDeclinedFill, sizeof(lep_huffdec_row), st));
     const auto &many = plan.seq_lanes, &one = plan.seq_single;
     if (!many.empty()) { if (int rc = lep_gpu_huffman_decode_simt_device(g, reinterpret_cast<const lep_huffdec_image*>(many.data()), (int)many.size(), d_rows, st)) return rc; }
     if (!one.empty()) { if (int rc = lep_gpu_huffman_decode_device(g, reinterpret_cast<const lep_huffdec_image*>(one.data()), (int)one.size(), d_rows, st)) return rc; }
@@ -1669,6 +1672,11 @@ int lep_gpu_huffman_progressive_encode_forms(lep_gpu* g, uint32_t counts[4]) {
 }
 int lep_gpu_device(lep_gpu* g) { return g ? g->device : -1; }
 int lep_gpu_stream_pack(lep_gpu* g) { return g ? g->stream_pack : 0; }
+int lep_gpu_cut_progressive(lep_gpu* g, int on) {
+    if (!g) return 0;
+    if (on >= 0) g->cut_progressive = on != 0;
+    return g->cut_progressive;
+}
 // "0000:c1:00.0" of the device the object was created on (hipDeviceGetPCIBusId): which physical GPU a rank of a multi-GPU run drives
 int lep_gpu_pci_bus_id(lep_gpu* g, char* out, int cap) {
     if (!g || !out || cap < 16) return LEP_ASSERTION_FAILURE;

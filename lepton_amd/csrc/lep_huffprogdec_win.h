@@ -54,6 +54,7 @@ struct WinScan {                        // the scan's constants, in registers
     int16_t* blocks;                    // ... and its frame
     const uint8_t* scan;
     uint32_t scan_len, limit;
+    bool cut;                           // kHuffDecEarlyEof: the file ends inside this scan (run_scan_win)
 };
 
 struct ProgWinWave : ProgDecWave {
@@ -85,13 +86,20 @@ struct ProgWinWave : ProgDecWave {
             L(wpf0) = lepwave::gld(p); L(wpf1) = lepwave::gld(p + 1); L(wpf2) = lepwave::gld(p + 2); L(wpf3) = lepwave::gld(p + 3);
         }
     }
+    // dword d of the scan as the ring holds it: every bit at or behind scan_len * 8 is zero BY POSITION, whatever lies behind the scan in
+    // its slot (BitReader::read shifts zeros in behind the data's last bit, and a file cut inside this scan is decoded into them)
+    WDEV uint32_t clip(uint32_t v, uint32_t d) const {
+        const uint32_t o = d * 4u;
+        if (o + 4u <= k.scan_len) return v;
+        return o >= k.scan_len ? 0u : v & (0xffffffffu << (8u * (o + 4u - k.scan_len)));
+    }
     WDEV void commit() {   // the chunk that was requested a refill ago goes into the ring, the next one is requested
         const uint32_t last = k.scan_len & ~15u;
         LANES(l) {
             const uint32_t d = pf_dword + 4u * (uint32_t)l, s = d & (kWinRing - 1);
             const bool in = d * 4u <= last;
-            ws->ring[s] = in ? __builtin_bswap32(L(wpf0)) : 0u; ws->ring[s + 1] = in ? __builtin_bswap32(L(wpf1)) : 0u;
-            ws->ring[s + 2] = in ? __builtin_bswap32(L(wpf2)) : 0u; ws->ring[s + 3] = in ? __builtin_bswap32(L(wpf3)) : 0u;
+            ws->ring[s] = in ? clip(__builtin_bswap32(L(wpf0)), d) : 0u; ws->ring[s + 1] = in ? clip(__builtin_bswap32(L(wpf1)), d + 1u) : 0u;
+            ws->ring[s + 2] = in ? clip(__builtin_bswap32(L(wpf2)), d + 2u) : 0u; ws->ring[s + 3] = in ? clip(__builtin_bswap32(L(wpf3)), d + 3u) : 0u;
         }
         ring_hi = pf_dword + kWinChunk;
         request(ring_hi);
@@ -172,14 +180,20 @@ struct ProgWinWave : ProgDecWave {
     // the bit at absolute position p of the scan, from the ring (inside LANES; p within the ring)
     WDEV uint32_t ring_bit(uint32_t p) const { return (ws->ring[(p >> 5) & (kWinRing - 1)] >> (31u - (p & 31u))) & 1u; }
 
-    // ---- AC first stage, one block (decode_ac_prg_fs): 0 ok, -1 irregular ------------------------------------------------------------
+    // What the block decoders answer: 0 ok; -1 the block does not decode (bits that are no code, a run that leaves its band) or the host parser
+    // warns (non-optimal end-of-band runs in a refinement scan); kNotCanonical: it decodes, but into something a canonical encoder does not
+    // write -- coded zeros in front of an end of band or at the end of the band, runs the encoder would have merged -- which the reference
+    // accepts without a word.  In a whole scan both send the file to the host parser; in the block that meets the end of a cut file the
+    // second kind is what the zeros behind the data make of a code that was cut in two, and the block is kept as the reference keeps it.
+    static constexpr int kNotCanonical = -2;
+    // ---- AC first stage, one block (decode_ac_prg_fs) ------------------------------------------------------------------------------
     WDEV int ac_first_win(int dpos) {
         const uint32_t from = (uint32_t)k.from, to = (uint32_t)k.to;
         const int sal = k.sal;
         if (eobrun > 0) { --eobrun; return 0; }   // inside a run: the band of this block is zero (the frame starts zeroed)
         uint32_t bpos = from, last_s = 1;
         int rc = 0;
-        bool run_read = false;
+        bool run_read = false, odd = false;
         LV(uint32_t, nv);
         LANES(l) L(nv) = 0;
 #pragma nounroll
@@ -213,18 +227,19 @@ struct ProgWinWave : ProgDecWave {
                 // end of band, and of 2^r + extra - 1 further blocks (a run behind a run the encoder had not filled up: host)
                 const uint32_t extra = r ? f16 >> (16u - r) : 0u;
                 off += len + r;
-                if (last_s == 0u) { rc = -1; break; }
+                if (last_s == 0u) odd = true;
                 eobrun = extra + (1u << r) - 1u;
-                if (bpos == from && peobrun > 0 && peobrun < k.max_eobrun) { rc = -1; break; }
+                if (bpos == from && peobrun > 0 && peobrun < k.max_eobrun) odd = true;   // (the reference's first stage never complains about these)
                 peobrun = (int)eobrun + 1;
                 run_read = true;
                 break;
             }
         }
         if (!run_read) {
-            if (!rc && last_s == 0u) rc = -1;         // the band ends in a coded zero
+            if (last_s == 0u) odd = true;             // the band ends in a coded zero
             peobrun = 0;
         }
+        if (!rc && odd) rc = kNotCanonical;
         // (a value whose 16 bits come out zero is not stored: the frame starts zeroed)
         LV(int, chg);
         LANES(l) L(chg) = L(nv) != 0;
@@ -289,6 +304,7 @@ struct ProgWinWave : ProgDecWave {
         int p = from - 1;
         uint64_t ahead = ~0ull;
         int rc = 0;
+        bool odd = false;
         if (eobrun == 0) {
 #pragma nounroll
             for (;;) {
@@ -337,13 +353,15 @@ struct ProgWinWave : ProgDecWave {
                 } else {
                     const uint32_t extra = r ? f16 >> (16u - r) : 0u;
                     off += len + r; acc += len + r;
-                    if ((last >> 16) == 0u) { rc = -1; break; }                  // ZRL in front of the end of band: not canonical
+                    if ((last >> 16) == 0u) odd = true;                          // ZRL in front of the end of band: not canonical
                     eobrun = extra + (1u << r);
-                    if (p == from - 1 && peobrun > 0 && peobrun < k.max_eobrun - 1) { rc = -1; break; }   // jpgcoder.cc:3229-3236
+                    // jpgcoder.cc:3229-3236: the reference warns where the run goes on behind this block (and refuses the file), and says
+                    // nothing about a run of this block alone
+                    if (p == from - 1 && peobrun > 0 && peobrun < k.max_eobrun - 1) { if (eobrun > 1u) { rc = -1; break; } odd = true; }
                     break;
                 }
             }
-            if (!rc && eobrun == 0 && (last >> 16) == 0u) rc = -1;               // the band ends in a ZRL
+            if (eobrun == 0 && (last >> 16) == 0u) odd = true;                   // the band ends in a ZRL
         }
         if (!rc && eobrun > 0) {
             if (p < to) {                                                        // the rest of the band: correction bits only
@@ -368,7 +386,7 @@ struct ProgWinWave : ProgDecWave {
         held_mask = lepwave::wave_ballot(chg);
         held_dpos = dpos;
         peobrun = (int)eobrun;
-        return rc;
+        return rc ? rc : (odd ? kNotCanonical : 0);
     }
 
     // BitReader::unpad (bitops.hh) at the chain's position
@@ -416,6 +434,7 @@ struct ProgWinWave : ProgDecWave {
             k.cmp = c; k.bch = img->bch[c]; k.nch = scan->nch[c]; k.ncv = scan->ncv[c]; k.vs = img->vs[c];
             k.blocks = img->blocks[c];
             k.scan = img->scan; k.scan_len = img->scan_len; k.limit = img->scan_len * 8u;
+            k.cut = (img->flags & kHuffDecEarlyEof) != 0;
         }
         LANES(l) {
             for (int i = l; i < 512; i += 64) { ws->lut[0][i] = img->lut[0][i]; ws->lut[1][i] = img->lut[1][i]; ws->lut[2][i] = img->lut[2][i]; }
@@ -447,12 +466,19 @@ struct ProgWinWave : ProgDecWave {
         const int mcuh = img->mcuh, sal = scan->sal;
         const uint32_t limit = k.limit;
         eobrun = 0; peobrun = 0;
+        // A file that ends inside this scan (k.cut; only a file's last scan can be one): the reference decodes block after block until the read
+        // that takes the data's last bit -- zeros behind it -- keeps that block and stops (decode_progressive_scan: `if (br.eof) { sta = 2;
+        // break; }`).  Here: the first block after which pos() >= limit ends the scan, sta = 3, cut_blocks = blocks of the scan's order up to
+        // and including it (one-component scans: the block position it started at + 1).  Anything that fails in that block is a status as
+        // anywhere else: which of the reference's half-decoded states to keep is the host parser's to know.
+        uint32_t cut_blocks = 0;
         int sta = 0;
         if (dc && scan->sah != 0) {
             // DC refinement: one bit per block and nothing else -- block i of the scan's order is bit i: 64 blocks per step, lane = block
             uint32_t P = 0;
             for (int i = 0; i < scan->cmpc; ++i) P += (uint32_t)scan->mbs[scan->cmp[i]];
-            const uint32_t total = scan->cmpc == 1 ? (uint32_t)k.nch * (uint32_t)k.ncv : (uint32_t)img->mcuc * P;
+            uint32_t total = scan->cmpc == 1 ? (uint32_t)k.nch * (uint32_t)k.ncv : (uint32_t)img->mcuc * P;
+            if (k.cut && limit <= total) { total = limit; cut_blocks = limit; }      // (block i is bit i: the block that reads the last bit is block limit - 1)
             const uint32_t per_row = scan->cmpc == 1 ? (uint32_t)k.nch * (uint32_t)k.vs : (uint32_t)mcuh * P;   // blocks of the scan per MCU row
             for (uint32_t i0 = 0; i0 < total && !status; i0 += 64) {
                 const uint32_t n = total - i0 < 64u ? total - i0 : 64u;
@@ -469,7 +495,7 @@ struct ProgWinWave : ProgDecWave {
                 off = n;
                 if (PIPE) { LSYNC(); publish((i0 + n) / per_row); }
             }
-            sta = status ? -1 : 2;
+            sta = status ? -1 : (cut_blocks ? 3 : 2);
             if (pos() > limit) sta = -1;
         } else if (dc && scan->cmpc > 1) {
             // DC first stage over MCUs: one code per block.  Lane q of `where` / `what` describes block q of an MCU: its place relative
@@ -515,13 +541,16 @@ struct ProgWinWave : ProgDecWave {
                         int16_t* fr = c == 0 ? frame[0] : (c == 1 ? frame[1] : (c == 2 ? frame[2] : frame[3]));
                         int16_t* dst = fr + (int64_t)(rb + mx * (int)(wt >> 8) + (int)wh) * 64 + 49;
                         LANES(l) if (l == 0) lepwave::gst(dst, (int16_t)((uint16_t)v << sal));
-                        if (pos() > limit) { bad = true; break; }
+                        if (pos() >= limit) {
+                            if (k.cut) cut_blocks = ((uint32_t)(my * mcuh + mx)) * P + q + 1u;
+                            if (k.cut || pos() > limit) { bad = true; break; }
+                        }
                     }
                 }
                 for (int c = 0; c < 4; ++c) rowbase[c] += stride[c];
                 if (PIPE && !bad) { LSYNC(); publish((uint32_t)(my + 1)); }
             }
-            sta = bad ? -1 : 2;
+            sta = cut_blocks ? 3 : (bad ? -1 : 2);
         } else {
             // one component: DC first stage or an AC scan, the component's nch x ncv blocks row by row (next_mcuposn, jpgcoder.cc:5432-5456)
             int col = 0, row = 0, dpos = 0, cur_row = -1, rstw = 0;
@@ -551,7 +580,7 @@ struct ProgWinWave : ProgDecWave {
                     LANES(l) if (l == 0) lepwave::gst(dst, (int16_t)((uint16_t)v << sal));
                 } else {
                     const int rc = k.sah == 0 ? ac_first_win(dpos) : ac_refine_win(dpos, col + 1 < k.nch);
-                    if (rc < 0) { sta = -1; break; }
+                    if (rc < 0 && !(rc == kNotCanonical && k.cut && pos() >= limit)) { sta = -1; break; }
                     if (k.sah == 0 && eobrun) {          // a run: its blocks are passed as a whole
                         if (!stray && col + (int)eobrun < k.nch) { col += (int)eobrun; dpos += (int)eobrun; eobrun = 0; }   // (inside the block row: skip_run comes to the same)
                         else {                           // skip_eobrun's own arithmetic (jpgcoder.cc:5462-5500), divisions and all
@@ -561,6 +590,10 @@ struct ProgWinWave : ProgDecWave {
                         }
                     }
                 }
+                if (pos() >= limit) {
+                    if (k.cut) { if (sta >= 0) { cut_blocks = (uint32_t)dpos + 1u; sta = 3; } break; }
+                    if (pos() > limit) { sta = -1; break; }
+                }
                 if (sta == 0) {
                     if (stray) { sta = next_noninterleaved(k.cmp, &dpos, &rstw); row = dpos / k.bch; col = dpos - row * k.bch; }
                     else {
@@ -569,25 +602,25 @@ struct ProgWinWave : ProgDecWave {
                         if (row >= k.ncv) sta = 2;
                     }
                 }
-                if (pos() > limit) { sta = -1; break; }
             }
             flush_store();
-            if (sta > 0 && eobrun > 0) sta = -1;
+            if (sta == 2 && eobrun > 0) sta = -1;
             if (dc) { const int v = lastdc[0]; lastdc[0] = 0; lastdc[k.cmp & 3] = v; }
         }
         if (sta == -1) { if (!PIPE || !status) status = 1; }
-        else {
+        else if (sta != 3) {
             const int got = unpad_win(255);
             padbit = (int8_t)got;
-        }
-        if (!status && pos() != limit) status = 2;   // bytes left over, or missing
+        }                                            // (a cut scan: the reader stands at the end of the data, unpad leaves the fill bit as it is)
+        if (!status && sta != 3 && pos() != limit) status = 2;   // bytes left over, or missing
         if (PIPE) publish(0x7fffffffu);
-        const uint32_t bp = pos();
+        const bool cut_end = sta == 3 && !status;
+        const uint32_t bp = cut_end ? cut_blocks : pos();
         HuffDecRow* fin = rows_arena + scan->result_off;
         LANES(l) if (l == 0) {
             fin->bitpos = bp;
             for (int c = 0; c < 4; ++c) fin->last_dc[c] = (int16_t)lastdc[c];
-            fin->aux = (padbit & 255) | (status << 8);
+            fin->aux = (padbit & 255) | (status << 8) | (cut_end ? kHuffDecRowTruncated : 0);
         }
     }
 };

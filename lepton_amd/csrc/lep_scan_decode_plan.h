@@ -43,7 +43,13 @@ struct ProgDecPlan {
         bool any_win = false;
         uint32_t piece_cut(int lv) const { return rcut[(size_t)lv] < (int)plans.size() ? plans[(size_t)rcut[(size_t)lv]].piece0 : pieces; }
     } c;
+    // d. Scans of files that END INSIDE them (kHuffDecEarlyEof in t.flags; a file's last scan) which the window form does not take -- a
+    // restart interval, a slot that is not aligned, the form switched off: only lep_huffprogdec_win.h knows the cut, so such a scan goes
+    // to NO kernel.  Their result_off: the launch code marks the final record there as not written, and the file goes to the host parser.
+    std::vector<uint64_t> declined;
 };
+// what the launch code (and the emulation) fills a declined scan's final record with, byte for byte: aux < 0, a status
+constexpr int kProgDecDeclinedFill = 0x80;
 
 // Non-zero: a sequential scan of no or more than four components, a dependency level outside 0 .. 63, more pieces than an int32 counts.
 inline int prog_dec_plan(const ProgDecScan* scans, int nscan, const ProgDecOptions& o, ProgDecPlan* out) {
@@ -51,7 +57,12 @@ inline int prog_dec_plan(const ProgDecScan* scans, int nscan, const ProgDecOptio
     std::vector<int> prog;          // the progressive scans, by their index in the caller's array
     for (int i = 0; i < nscan; ++i) {
         const ProgDecScan& sc = scans[i];
-        if (!progdec_is_sequential(sc)) { if (sc.level < 0 || sc.level > 63) return 1; prog.push_back(i); continue; }
+        if (!progdec_is_sequential(sc)) {
+            if (sc.level < 0 || sc.level > 63) return 1;
+            if ((sc.t.flags & kHuffDecEarlyEof) && !(o.win && prog_win_takes(sc))) { out->declined.push_back(sc.result_off); continue; }
+            prog.push_back(i);
+            continue;
+        }
         if (sc.cmpc < 1 || sc.cmpc > 4) return 1;
         const HuffDecImage im = sequential_scan_image(sc);
         ((o.lanes && sequential_scan_for_lanes(im)) ? out->seq_lanes : out->seq_single).push_back(im);

@@ -10,7 +10,11 @@ device, from lep_gpu_last_kernel_ms.  One JSON line per corpus.
 --write-only leaves the compress leg out.
 
 The baseline is ANOTHER BUILD of the library (LEP_LIB_PATH=<the parent commit's liblepton_mi355x.so>), alternated with this one in the
-same visit; LEP_HUFFPROGDEC_RST=0 on this build is a convenience, not the baseline.  --cache DIR keeps the corpus between processes."""
+same visit; LEP_HUFFPROGDEC_RST=0 on this build is a convenience, not the baseline.  --cache DIR keeps the corpus between processes.
+
+--corpus plain: 256 x 4K progressive files WITHOUT restart intervals from bench.py's own generator (lepton_amd.corpus.make_corpus, the
+seed of its `progressive` corpus, 8 distinct) -- what the window decoder's whole-file path is measured on when that kernel changes;
+--decode-only leaves the timed compress_batch runs out (one warm call still checks that every file takes the scan kernels)."""
 import argparse
 import ctypes as C
 import io
@@ -29,7 +33,8 @@ sys.path.insert(0, ROOT)
 
 CORPORA = {"rows_1": dict(restart_marker_rows=1), "blocks_516": dict(restart_marker_blocks=516),
            "blocks_5": dict(restart_marker_blocks=5),    # (blocks_5: a marker per five blocks, about 26,000 units per luma scan; not part of "both")
-           "none": dict()}                               # (none: the same pictures without an interval, for --write-only; not part of "both")
+           "none": dict(),                               # (none: the same pictures without an interval, for --write-only; not part of "both")
+           "plain": None}                                # (plain: bench.py's progressive corpus, no interval; not part of "both")
 BOTH = ["blocks_516", "rows_1"]
 
 
@@ -47,6 +52,17 @@ def picture(args):
 
 
 def corpus(name, w, h, distinct, cache):
+    if CORPORA[name] is None:                            # bench.py's generator and seed (its `progressive` extra: 30001 + 1000 * 2)
+        from lepton_amd import corpus as bench_corpus
+
+        files = [os.path.join(cache, "%s_%dx%d_%02d.jpg" % (name, w, h, i)) for i in range(distinct)] if cache else []
+        if files and all(os.path.exists(p) for p in files):
+            return [open(p, "rb").read() for p in files]
+        made = bench_corpus.make_corpus(distinct, w, h, 32001, progressive=True)
+        for p, j in zip(files, made):
+            os.makedirs(cache, exist_ok=True)
+            open(p, "wb").write(j)
+        return made
     out = []
     missing = []
     for i in range(distinct):
@@ -209,6 +225,7 @@ def main():
     ap.add_argument("--cache", default=None)
     ap.add_argument("--write", action="store_true", help="add the write leg: decompress_batch and the scan write alone")
     ap.add_argument("--write-only", action="store_true", help="the write leg without the compress leg")
+    ap.add_argument("--decode-only", action="store_true", help="the scan decode alone: no timed compress_batch runs")
     ap.add_argument("--label", default=os.environ.get("LEP_LIB_PATH") and "LEP_LIB_PATH" or "this build")
     a = ap.parse_args()
     assert a.repeats >= 5, "at least 5 repeats"
@@ -229,7 +246,7 @@ def main():
         assert st == [0] * len(jpgs), "a file of the corpus was refused"
         assert stats["gpu_huffman_files"] == len(jpgs), "a file of the corpus went to the host parser"
         secs = []
-        for _ in range(a.repeats):
+        for _ in range(0 if a.decode_only else a.repeats):
             t0 = time.perf_counter()
             _, st, _ = codec.compress_batch(jpgs)
             secs.append(time.perf_counter() - t0)
@@ -252,9 +269,10 @@ def main():
         written = write_leg(L, codec, distinct, jpgs, a.repeats) if a.write else {}
         print(json.dumps({"corpus": name, "label": a.label, "library": abi.LIB_PATH, "files": a.files, "distinct": a.distinct, "size": [a.width, a.height], "jpeg_bytes": nbytes,
                           "knob_LEP_HUFFPROGDEC_RST": os.environ.get("LEP_HUFFPROGDEC_RST"), "repeats": a.repeats, **written,
-                          "compress_batch_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4)},
-                          "compress_MB_s": {"median": round(nbytes / statistics.median(secs) / 1e6, 1), "best": round(nbytes / min(secs) / 1e6, 1)},
-                          "scan_decode_ms": {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3)}, "scan_decode_kernel": kernel,
+                          **({} if a.decode_only else {
+                              "compress_batch_s": {"median": round(statistics.median(secs), 4), "min": round(min(secs), 4)},
+                              "compress_MB_s": {"median": round(nbytes / statistics.median(secs) / 1e6, 1), "best": round(nbytes / min(secs) / 1e6, 1)}}),
+                          "scan_decode_ms": {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}, "scan_decode_kernel": kernel,
                           "scans": n, "scans_with_a_status": refused}), flush=True)
     codec.close()
 

@@ -5,6 +5,7 @@ sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
 from conftest import golden, golden_cases, ref_cases, ref_golden
 from lepton_amd.codec import GpuCodec
 c = GpuCodec(0)
+c.cut_progressive(True)   # (progressive files that end inside a scan: on the scan kernels, lep_gpu_cut_progressive)
 files = [(n, golden(n)) for n in golden_cases()] + [("ref:" + n, ref_golden(n)) for n in ref_cases()]
 host_c, host_d = [], []
 for name, (jpg, lep) in files:
