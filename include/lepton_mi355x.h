@@ -501,11 +501,15 @@ int lep_compress(lep_gpu *g, const uint8_t *jpg, size_t len, lep_bytes *out);
  * One file per call, on the host parser; lep_compress_batch_slices takes many slices through the batch pipeline and gives the same bytes. */
 int lep_compress_slice(lep_gpu *g, const uint8_t *jpg, size_t len, size_t start_byte, size_t trunc, lep_bytes *out);
 int lep_decompress(lep_gpu *g, const uint8_t *lepdata, size_t len, lep_bytes *out);
-/* lep_decompress with the JPEG's bytes handed to `sink` as they become final, in file order.  A whole baseline file with one interleaved
- * scan is decoded in a session (lep_gpu_decode_rows_*), band_mcu_rows MCU rows per advance (<= 0: one advance): the header goes out before
+/* lep_decompress with the JPEG's bytes handed to `sink` as they become final, in file order.  Every single file the split re-coder plans
+ * (lep_file_recode_plan says gpu_ok: a baseline file or a -startbyte / -trunc slice of one, 'Z' or 'Y', one scan of one, two or three
+ * components, cut inside that scan or not, with or without restart intervals; lep_file_streams_in_session answers for a file)
+ * is decoded in a session (lep_gpu_decode_rows_*), band_mcu_rows MCU rows per advance (<= 0: one advance): the header (a slice's prefix
+ * bytes) goes out before
  * the first advance, then after every advance the MCU rows that have become complete are Huffman-coded on the host, segment by segment
  * from each segment's hand-off; segment 0's rows go out as they come, a later segment's bytes once the segments in front of it are done.
- * Every other file (progressive, truncated, several files back to back, ...) is lep_decompress and one sink call: stats->advances = 0.
+ * Every other file (progressive, sequential in several scans, cut with restart intervals, several files back to back, ...) is
+ * lep_decompress and one sink call: stats->advances = 0.
  * The bytes sunk, concatenated, are lep_decompress's and the return value is the same; when a segment fails, what has been sunk by
  * then are bytes of rows in front of the failing block.  A sink that returns non-zero ends the call with LEP_OS_ERROR.  stats may be NULL. */
 typedef int (*lep_sink)(void *user, const uint8_t *data, size_t len);
@@ -515,6 +519,9 @@ typedef struct lep_stream_stats {
     uint64_t bytes_before_last_advance;        /* bytes the sink had when the last advance was launched */
 } lep_stream_stats;
 int lep_decompress_stream(lep_gpu *g, const uint8_t *lepdata, size_t len, int band_mcu_rows, lep_sink sink, void *user, lep_stream_stats *stats);
+/* Host only: does lep_decompress_stream / lep_decompress_batch_stream decode this .lep in a session?  1 / 0, or the exit code (> 1) of a
+ * file that does not parse.  (A parse that ends in LEP_ASSERTION_FAILURE, which is 1, answers 0: the file is not streamed.) */
+int lep_file_streams_in_session(const uint8_t *lepdata, size_t len);
 
 /* Whole batches of files as a pipeline (what `lepton -socket` workers / src/lepton/socket_serve.cc:312-390 would hand to
  * the GPU): JPEG parsing + Huffman scan decode on a host thread pool, coefficient frames over PCIe on a copy stream while
@@ -558,8 +565,8 @@ int lep_compress_batch_slices(lep_gpu *g, const lep_bytes *jpgs, const lep_slice
                               const lep_batch_options *opt, lep_batch_stats *stats);
 int lep_decompress_batch(lep_gpu *g, const lep_bytes *leps, int n, lep_bytes *outs, int32_t *status,
                          const lep_batch_options *opt, lep_batch_stats *stats);
-/* lep_decompress_batch with every file's bytes handed to `sink` as they become final.  The files lep_decompress_stream streams (one whole
- * baseline file, one interleaved scan of two or three components, not truncated, not chained, taken by the split re-coder) are decoded in
+/* lep_decompress_batch with every file's bytes handed to `sink` as they become final.  The files lep_decompress_stream streams (every
+ * single file the split re-coder plans: whole files and slices, one to three components, cut inside the scan or not; not chained) are decoded in
  * sessions (lep_gpu_decode_rows_*) of at most LEP_STREAM_SESSION_FILES files (environment, default 64) and 16384 thread segments, one session
  * after another: `begin` takes all files of a session as one launch, each file's header bytes go out before the first advance, and after
  * every advance of band_mcu_rows MCU rows (<= 0: one advance) ONE lep_gpu_huffman_encode_device launch writes the rows every segment
@@ -567,7 +574,10 @@ int lep_decompress_batch(lep_gpu *g, const lep_bytes *leps, int n, lep_bytes *ou
  * back, and two copies bring them down (LEP_STREAM_PACK=0: one copy per segment).  Only scan bytes cross PCIe: frames and streams are device
  * memory of the call.  A file's front segment goes out as it comes, a later segment's bytes once the segments in front of it are complete.
  * At the end lep_file_recode_finish's checks run over the segments' bytes and end states and supply the tail; what went out must be the
- * front of that result (else LEP_ASSERTION_FAILURE).  A file whose writer outgrew its byte bound, or whose finish does not succeed (declined, or a
+ * front of that result (else LEP_ASSERTION_FAILURE).  A band of a one-component file is band_mcu_rows x (block rows per MCU row) block rows:
+ * the writer's rows of such a file are block rows.  A band whose writer stops at the cut of a file cut inside its scan ends the file's last
+ * segment when that segment's bytes have reached its byte bound by then (lep_file_recode_finish's condition, per band): such a file finishes
+ * on the writer like any other and moves no frame.  A file whose writer outgrew its byte bound, or whose finish does not succeed (declined, or a
  * hand-off check that fails: any non-zero answer, as in lep_decompress_stream, so that exit codes stay lep_decompress's -- a check that failed on
  * good data would show only as frame_bytes_down > 0), has its frame
  * downloaded (stats->frame_bytes_down) and is finished by the host re-coder under the same check.  Every other file of the call goes through

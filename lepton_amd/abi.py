@@ -215,6 +215,8 @@ def lib():
             L.lep_gpu_stream_pack.argtypes = [vp]
             L.lep_file_recode_head.argtypes = [vp, P(vp), P(C.c_size_t)]
             L.lep_decompress_batch_stream.argtypes = [vp, P(Bytes), C.c_int, C.c_int, BATCH_SINK_FN, vp, P(C.c_int32), P(BatchOptions), P(BatchStreamStats)]
+        if hasattr(L, "lep_file_streams_in_session"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_file_streams_in_session.argtypes = [vp, C.c_size_t]
         L.lep_gpu_use_arena.argtypes = [vp, C.c_int]
         L.lep_gpu_sync.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
@@ -305,4 +307,5 @@ EXPORTS = [
     "lep_gpu_decode_rows_begin", "lep_gpu_decode_rows_advance", "lep_gpu_decode_rows_end", "lep_decompress_stream",
     "lep_gpu_pack_device", "lep_gpu_stream_pack", "lep_file_recode_head", "lep_decompress_batch_stream",
     "lep_jpeg_cut_block_irregular", "lep_file_recode_plan_progressive_cut", "lep_jpeg_plan_progressive_check_cut", "lep_jpeg_open_gpu_progressive_cut", "lep_gpu_cut_progressive",
+    "lep_file_streams_in_session",
 ]

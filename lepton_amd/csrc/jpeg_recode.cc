@@ -317,7 +317,7 @@ struct SegmentRowCoder::Impl {
     BitWriter w;
     BoundedOut o;
     int16_t lastdc[4];
-    int next, end, mcuh;
+    int next, end, mcuh, unit;   // unit: planned rows per MCU row of the row coder
     Impl(LepFile* lf) : rc(*lf) {}
 };
 SegmentRowCoder::SegmentRowCoder(LepFile* lf, const RecodePlan& plan, size_t s) : p(new Impl(lf)) {
@@ -329,13 +329,18 @@ SegmentRowCoder::SegmentRowCoder(LepFile* lf, const RecodePlan& plan, size_t s) 
     p->o.shut = g.out_cap == 0;
     memcpy(p->lastdc, g.last_dc, sizeof p->lastdc);
     p->next = g.mcu_row0; p->end = g.mcu_row1; p->mcuh = lf->jpeg.mcuh;
+    // A one-component file's planned rows are block rows (recode_prepare), the row coder's step is the MCU row of hs x vs blocks: bcv / mcuv
+    // planned rows -- fewer in the last one, whose padding rows the plan leaves out.  1 for every other file, and for a plain one-component one.
+    const JpegFile& jf = lf->jpeg;
+    p->unit = jf.ncomp == 1 ? std::max(jf.comp[0].bcv / std::max(jf.mcuv, 1), 1) : 1;
 }
 SegmentRowCoder::~SegmentRowCoder() { delete p; }
 int SegmentRowCoder::next_row() const { return p->next; }
 int SegmentRowCoder::end_row() const { return p->end; }
 void SegmentRowCoder::code_rows(int upto) {
-    for (; p->next < upto && p->next < p->end; ++p->next) {
-        p->rc.mcu_row(p->w, p->next * p->mcuh, p->o, p->lastdc);
+    // (whole MCU rows only: a planned row that is part of one waits for the rest of it)
+    for (int row_end; p->next < p->end && (row_end = std::min(p->next + p->unit, p->end)) <= upto; p->next = row_end) {
+        p->rc.mcu_row(p->w, p->next / p->unit * p->mcuh, p->o, p->lastdc);
         drain(p->w, p->o);
         p->w.row_flush();
     }

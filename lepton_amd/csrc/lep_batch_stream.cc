@@ -2,8 +2,15 @@
 // decoded in one session of the resumable decoder (lep_gpu_decode_rows_*); after every advance the MCU rows that every thread segment
 // completed are written by the lane scan writer on the device (lep_gpu_huffman_encode_device: one launch per band, every segment from the
 // end state of its band before), the band's new bytes are moved back to back (lep_gpu_pack_device) and come down in two copies; only scan
-// bytes cross PCIe.  The band bookkeeping is lep_stream_bands.h's (stepped on the CPU by tests/emu/stream_bands_emu.cc); here are the
-// device memory, the launches and the copies.  Files that are not streamed take one lep_decompress_batch call.
+// bytes cross PCIe.  The band bookkeeping is lep_stream_bands.h's (stepped on the CPU by tests/emu/stream_bands_emu.cc and stream_layouts_emu.cc); here are the
+// device memory, the launches and the copies.  Streamed: every single file the split re-coder plans (lep::streams_in_session) -- whole files
+// and -startbyte / -trunc slices, one to three components, cut inside the scan or not.  Files that are not streamed take one
+// lep_decompress_batch call.
+// A file cut inside its scan needs nothing done to its frame in front of a band's writer launch, as it needs nothing in front of
+// lep_decompress_batch's one scan launch (launch_decompress_chunk clears behind the cut for PROGRESSIVE files of one segment only, and
+// those are not streamed): the session's frames start zero-filled, the decoder stores nothing behind the cut, and the lane writer
+// itself stops at the first block at or behind trunc_bc (a row's first block apart, the reference's decode_row rule: lep_huff_simt.h
+// code_mcus) and says so in its end state -- which band_written (lep_stream_bands.h) weighs band by band.
 #include "../../include/lepton_mi355x.h"
 
 #include <algorithm>
@@ -137,7 +144,7 @@ int run_session(Call& C, std::vector<Streamed>& files, size_t first, size_t last
             memcpy(&planned, &F.plan.segs[(size_t)q], sizeof planned);
             planned.out_cap = slots[q].slot;
             bsegs.emplace_back();
-            lepbands::start_segment(&bsegs.back(), i, planned, slots[q].off);
+            lepbands::start_segment(&bsegs.back(), i, planned, slots[q].off, q + 1 == F.nseg, slots[q].bound);
         }
     }
     const int nseg = (int)dsegs.size();
@@ -192,8 +199,7 @@ int run_session(Call& C, std::vector<Streamed>& files, size_t first, size_t last
         for (int i = 0; i < nf; ++i) {
             lepbands::File& bf = bfiles[(size_t)i];
             const lep_image_desc& d = dev[(size_t)i];
-            int vs[LEP_MAX_COMPONENTS];
-            lepbands::block_rows_per_mcu_row(d, vs);
+            const lepbands::RowUnits units = lepbands::row_units(d, himgs[(size_t)i]);
             for (int q = 0; q < bf.nseg; ++q) {
                 const int k = bf.seg0 + q;
                 if (prog[(size_t)k].status > 0 && !bsegs[(size_t)k].stopped) {
@@ -205,7 +211,7 @@ int run_session(Call& C, std::vector<Streamed>& files, size_t first, size_t last
             for (int q = 0; q < bf.nseg; ++q) {
                 const int k = bf.seg0 + q;
                 lep_huff_segment hs;
-                if (!lepbands::band_segment(bsegs[(size_t)k], lepbands::complete_row(bsegs[(size_t)k], prog[(size_t)k], vs, d.ncomp), i, &hs)) continue;
+                if (!lepbands::band_segment(bsegs[(size_t)k], lepbands::complete_row(bsegs[(size_t)k], prog[(size_t)k], units.vs, d.ncomp), i, &hs)) continue;
                 launch.push_back(hs); which.push_back(k); src_off.push_back(hs.out_off);
             }
         }

@@ -14,9 +14,25 @@
 
 extern "C" {
 
+// Is this .lep one that lep_decompress_stream / lep_decompress_batch_stream decode in a session (1) or hand to lep_decompress whole (0)?
+// Host only.  A file that does not parse answers its exit code -- bar LEP_ASSERTION_FAILURE, which is 1: such a file is not streamed, 0.
+int lep_file_streams_in_session(const uint8_t* lepdata, size_t len) {
+    lep_file* f = nullptr;
+    if (int rc = lep_file_open(lepdata, len, &f)) return rc == LEP_ASSERTION_FAILURE ? 0 : rc;
+    std::unique_ptr<lep_file> hold(f);
+    lep::RecodePlan plan;
+    lep_segment segs[LEP_MAX_SEGMENTS];
+    lep_bytes streams[LEP_MAX_SEGMENTS];
+    int n = 0;
+    return lep::streams_in_session(f, lepdata, len, &plan, segs, streams, &n) ? 1 : 0;
+}
+
 // lep_decompress with the bytes handed on as they become final (include/lepton_mi355x.h).  The decode is a session
 // (lep_gpu_decode_rows_*): after every advance the block rows the segments completed are fetched into the host frame and the MCU rows
 // they complete are coded by a SegmentRowCoder per segment; recode_finish, over the same bytes, supplies the checks and the tail.
+// Streamed: every single file the split re-coder plans (lep::streams_in_session) -- whole files and -startbyte / -trunc slices, one to
+// three components, cut inside the scan or not.  A cut file's coders read what the re-coder reads behind the cut (RowCoder::mcu_row) and
+// are bound by the segments' byte bounds, so nothing goes out that the finished file does not start with; the front check below stays.
 using lep::DeviceMem;
 using lep::SessionEnd;
 
@@ -89,7 +105,8 @@ int lep_decompress_stream(lep_gpu* g, const uint8_t* lepdata, size_t len, int ba
     int fetched[LEP_MAX_SEGMENTS][LEP_MAX_COMPONENTS] = {{0}};   // rows_done as of the last fetch
     lep_decode_progress prog[LEP_MAX_SEGMENTS];
     int vs[LEP_MAX_COMPONENTS];
-    lepbands::block_rows_per_mcu_row(d, vs);
+    lepbands::block_rows_per_mcu_row(d, vs);                                   // where a segment's rows start in every component (the fetch)
+    const lepbands::RowUnits units = lepbands::row_units(d, plan.image);      // the plan's rows, which the coders count in
     bool failed = false, scan_byte_out = false;
     for (int running = 1; running > 0;) {
         stats->bytes_before_last_advance = sunk;
@@ -107,7 +124,7 @@ int lep_decompress_stream(lep_gpu* g, const uint8_t* lepdata, size_t len, int ba
                     if (int rc = lep_gpu_memcpy_d2h(g, (char*)d.blocks[c] + (size_t)r0 * row_bytes, (const char*)dev.blocks[c] + (size_t)r0 * row_bytes, (size_t)(r1 - r0) * row_bytes)) return rc;
                     fetched[s][c] = r1;
                 }
-                if (prog[s].status != 0) complete = std::min(complete, prog[s].rows_done[c] / vs[c]);
+                if (prog[s].status != 0) complete = std::min(complete, prog[s].rows_done[c] / units.vs[c]);
             }
             coders[(size_t)s]->code_rows(complete);
         }
@@ -159,10 +176,12 @@ int lep_decompress_stream(lep_gpu* g, const uint8_t* lepdata, size_t len, int ba
 
 bool lep::streams_in_session(lep_file* f, const uint8_t* lepdata, size_t len, RecodePlan* plan, lep_segment* segs, lep_bytes* streams, int* nseg) {
     LepFile& lf = f->lf;
-    JpegFile& jf = lf.jpeg;
     *nseg = 0;
+    // Every single file the split re-coder plans: 'Z' and 'Y' (a -startbyte / -trunc slice), one to three components, cut inside the scan
+    // or not, with or without restart intervals.  What recode_prepare does not plan or declines stays out by itself: progressive files,
+    // sequential frames in several scans, cut files with restart intervals or one component, the layouts it sends to the host re-coder.
     const bool chained = lep_chained_file_follows(lepdata, len, lep_file_consumed(f)) != 0;
-    if (chained || lf.flag != 'Z' || jf.early_eof || jf.ncomp < 2 || recode_prepare(&lf, plan) != 0 || !plan->gpu_ok) return false;
+    if (chained || recode_prepare(&lf, plan) != 0 || !plan->gpu_ok) return false;
     const int n = lep_file_segments(f, segs, streams, 0);
     if (n <= 0 || (size_t)n != plan->segs.size()) return false;
     *nseg = n;

@@ -1,8 +1,12 @@
 // lep_stream_bands.h -- host only: the bookkeeping of a decode session whose completed MCU rows are written by the scan writer band after
-// band (lep_decompress_batch_stream, lep_batch_stream.cc; stepped on the CPU by tests/emu/stream_bands_emu.cc).  Per thread segment:
+// band (lep_decompress_batch_stream, lep_batch_stream.cc; stepped on the CPU by tests/emu/stream_bands_emu.cc and stream_layouts_emu.cc).  Per thread segment:
 // which rows a band added, the state the band's writer starts from (the end state of the band before, the file's hand-off for the first),
 // where in the segment's slot its bytes go; per file: which bytes may go out (a segment's only when every segment in front of it is
 // complete), and whether what went out is the front of the finished file.  Nothing here touches a device or a socket.
+// Rows are the PLAN's rows throughout (lep_huff_segment.mcu_row0 / mcu_row1): MCU rows of an interleaved file, block rows of a one-component
+// file (lep_huff_image.interleaved, recode_prepare) -- RowUnits converts the decoder's block-row counts and the band height into them.
+// A -startbyte / -trunc slice ('Y') has no rule of its own here: its head is the prefix garbage, its first segment is seeded with the
+// overhang of the row it starts in, its bounds are the slice's -- all of it the plan's (recode_prepare), so it is stepped like a whole file.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -21,7 +25,9 @@ struct Segment {
     uint32_t overhang = 0;         // what the next band's writer starts from
     int16_t last_dc[4] = {0, 0, 0, 0};
     uint64_t slot_off = 0;         // the segment's slot in the scan arena
-    uint32_t slot_cap = 0;         // ... its size: the segment's byte bound (out_cap of the plan)
+    uint32_t slot_cap = 0;         // ... its size
+    uint32_t bound = 0;            // the segment's byte bound itself (a front segment's slot may be smaller: place_recode_segments)
+    bool last = false;             // the file's last segment: the one a cut inside the scan may end (band_written)
     uint32_t written = 0;          // bytes of the slot that are written
     bool stopped = false;          // its decode failed: nothing more is written
     std::vector<uint8_t> bytes;    // host copy of the written bytes (what recode_finish is given)
@@ -43,8 +49,10 @@ struct File {
     bool writes() const { return !failed && !declined && !gone; }
 };
 
-inline void start_segment(Segment* s, int file, const lep_huff_segment& planned, uint64_t slot_off) {
+// planned.out_cap is the slot's size; bound: the plan's byte bound where the slot was given another size (0: the slot's)
+inline void start_segment(Segment* s, int file, const lep_huff_segment& planned, uint64_t slot_off, bool last_of_file = false, uint32_t bound = 0) {
     s->file = file;
+    s->last = last_of_file; s->bound = bound ? bound : planned.out_cap;
     s->row0 = planned.mcu_row0; s->row1 = std::max(planned.mcu_row0, planned.mcu_row1); s->coded = s->row0;
     s->overhang = planned.overhang;
     memcpy(s->last_dc, planned.last_dc, sizeof s->last_dc);
@@ -58,8 +66,22 @@ inline void block_rows_per_mcu_row(const lep_image_desc& d, int* vs) {
     for (int c = 0; c < d.ncomp && c < LEP_MAX_COMPONENTS; ++c) vs[c] = std::max(d.height_blocks[c] / std::max(d.mcu_rows, 1), 1);
 }
 
-// The MCU row up to which segment s is in the frame after an advance: every component's block rows below rows_done[c] are there, a
-// finished segment is there to its end.  vs[c] = block rows of component c per MCU row.
+// The plan's row unit against the decoder's: vs[c] = block rows of component c per planned row, per_mcu_row = planned rows per MCU row
+// (what one band_mcu_rows of an advance adds).  Interleaved: planned rows ARE MCU rows -- the geometry's ratio, 1.  One component: the
+// writer's plan is nch x ncv MCUs of one block and its segments are in block rows (clipped to ncv: rows that only pad the frame to whole
+// MCUs are never written, so the last MCU row may hold fewer), while rows_done[0] counts frame block rows -- 1, and the frame's block
+// rows per MCU row (the hand-offs' luma_mul).
+struct RowUnits { int vs[LEP_MAX_COMPONENTS] = {1, 1, 1}; int per_mcu_row = 1; };
+template <class PlanImage>   // lep_huff_image, or recode_prepare's RecodeImage of the same layout
+inline RowUnits row_units(const lep_image_desc& d, const PlanImage& plan) {
+    RowUnits u;
+    if (plan.ncomp == 1) u.per_mcu_row = std::max(d.height_blocks[0] / std::max(d.mcu_rows, 1), 1);
+    else block_rows_per_mcu_row(d, u.vs);
+    return u;
+}
+
+// The planned row up to which segment s is in the frame after an advance: every component's block rows below rows_done[c] are there, a
+// finished segment is there to its end.  vs[c] = block rows of component c per planned row (RowUnits::vs).
 inline int complete_row(const Segment& s, const lep_decode_progress& p, const int* vs, int ncomp) {
     if (p.status == 0) return s.row1;
     int complete = s.row1;
@@ -82,6 +104,11 @@ inline bool band_segment(const Segment& s, int complete, int image, lep_huff_seg
 
 // What the band's writer answered: len bytes at `data` (the host copy of slot_off + written ...), its end state.  false = the band did
 // not fit what was left of the slot, or the writer stopped of its own accord: the file is the host re-coder's.
+// A band that stopped at the cut of a file cut inside its scan (pad & 1, kHuffEndCut) is the file's under recode_finish's own condition,
+// stated per band: it is the file's LAST segment and what the segment attempted, all bands together, has reached its byte bound -- then
+// nothing behind the cut can show, the segment is complete whatever rows remain, and its bytes, clipped to the bound, may go out.  (The
+// slot must be the bound's size for that: clipped to anything else the bytes are not the bound's.)  A cut end state in another segment or
+// with the bound not reached, and a refusal (pad & 2, kHuffEndRefused), decline the file.  recode_finish keeps the last word at the end.
 inline bool band_written(Segment* s, const lep_huff_segment& launched, const uint8_t* data, uint32_t len, const lep_huff_end& end) {
     if (len > launched.out_cap) len = launched.out_cap;
     s->bytes.insert(s->bytes.end(), data, data + len);
@@ -92,7 +119,13 @@ inline bool band_written(Segment* s, const lep_huff_segment& launched, const uin
     const uint32_t before = s->end.attempted;
     s->end = end;
     s->end.attempted = before + end.attempted;   // recode_finish reads the segment's count, not the band's
-    return end.attempted <= launched.out_cap && !(end.pad & 3);
+    if (end.pad & 2) return false;
+    if (end.pad & 1) {
+        if (!s->last || s->slot_cap != s->bound || s->end.attempted < s->bound) return false;
+        s->coded = s->row1;
+        return true;
+    }
+    return end.attempted <= launched.out_cap;
 }
 
 // Hand on what may go out of file f: the front segment's new bytes, and on to the next segment when the front one is complete.

@@ -8,9 +8,12 @@
 
 namespace lep {
 
-// Is this parsed file one that is streamed -- one whole baseline file with one interleaved scan of two or three components, several thread
-// segments or one: the files the split re-coder plans (recode_prepare says gpu_ok), bar truncated ones (what the re-coder reads behind the
-// cut is not rows of this decode) and chains of files?  true: *plan is its plan, segs / streams (LEP_MAX_SEGMENTS each) its *nseg segments.
+// Is this parsed file one that is streamed -- any single file the split re-coder plans (recode_prepare says gpu_ok): a whole baseline file
+// ('Z') or a -startbyte / -trunc slice ('Y'), one scan of one, two or three components, several thread segments or one, cut inside the scan
+// or not, with or without restart intervals?  Not streamed: chains of files, and whatever recode_prepare does not plan or declines
+// (progressive files, sequential frames in several scans, cut files with restart intervals or one component, the layouts it sends to the
+// host re-coder).  true: *plan is its plan, segs / streams (LEP_MAX_SEGMENTS each) its *nseg segments.  lep_file_streams_in_session is
+// this rule for a caller without a device.
 bool streams_in_session(lep_file* f, const uint8_t* lepdata, size_t len, RecodePlan* plan, lep_segment* segs, lep_bytes* streams, int* nseg);
 
 struct DeviceMem {   // device allocations of one call, freed when it returns
