@@ -401,6 +401,35 @@ struct BoolDec4S {
 #ifndef LEP_DEC4_WORD_PER_LANE
 #define LEP_DEC4_WORD_PER_LANE 1
 #endif
+// Exec-mask bookkeeping of the lane-parallel phases, taken out in the source (the structurizer mode that removes some of it miscompiles
+// another kernel: __graft_entry__.py).  Both default to 1; 0 = the form before (A/B builds, scripts/build_variant.sh).
+//   LEP_DEC4_UNIFORM_TESTS: what is the same for the whole wavefront -- a block's has_left / has_above, "first block of the row", the
+//     neighbours' non-zero counts -- is held as a scalar (uflag / unii) and tested by a scalar branch AROUND whole lane-parallel bodies or
+//     by a select on it, never by an `if` inside a LANES body (which compiles to s_and_saveexec / s_cbranch_execz / s_or exec per test).
+//   LEP_DEC4_LANE_SELECTS: a lane-range test (l < 49, l < 56, p < zz ..) whose body only reads LDS at addresses that are in range for
+//     every lane and computes is written branch-free -- every lane computes on a clamped index, lanes outside the range select 0 -- and an
+//     exec region is kept only around a store or a global load that must not happen.
+#ifndef LEP_DEC4_UNIFORM_TESTS
+#define LEP_DEC4_UNIFORM_TESTS 1
+#endif
+#ifndef LEP_DEC4_LANE_SELECTS
+#define LEP_DEC4_LANE_SELECTS 1
+#endif
+// The update's second regrouped pass: the words adapt_group still took a pass per slot for -- the edges' residual words 0..3 (regrouped
+// onto lanes 4 * (e * 7 + j) + slot like their exponent words 0..3) and exponent words 4..7 of the interior and the edges (nobody holds
+// those: the adapting lane takes the group's address from the lane the position was coded under and loads, adapts and stores its own
+// dword).  Written on the branch-free lane maps, so it needs LEP_DEC4_LANE_SELECTS and LEP_DEC4_WORD_PER_LANE; 0 = the owners' form.
+#ifndef LEP_DEC4_WORD_PER_LANE_2
+#define LEP_DEC4_WORD_PER_LANE_2 1
+#endif
+#define LEP_DEC4_WPL2 (LEP_DEC4_WORD_PER_LANE_2 && LEP_DEC4_WORD_PER_LANE && LEP_DEC4_LANE_SELECTS)
+#if LEP_DEC4_UNIFORM_TESTS
+#define LEP_UFLAG(c) uflag(c)
+#define LEP_UINT(v) unii(v)
+#else
+#define LEP_UFLAG(c) (c)
+#define LEP_UINT(v) (v)
+#endif
 
 // A segment's resume record (Dec4WaveT::run_rows): all that a segment carries from one band's launch to the next beside its model, its
 // summary rings, the frame and the two LDS-resident Branch tables.  Written by lane 0 at a band's end; all zero = fresh.
@@ -727,6 +756,19 @@ struct Dec4WaveT {
         adapt_words(Wd, use, obs);
         LANES(l) if (L(use)) model[L(ad) + (uint32_t)L(slot)] = L(Wd);
     }
+    // the same for words no lane holds (exponent words 4..7, read on demand by the serial code): the adapting lane takes the group's address
+    // from lane src, loads its own dword at + off + slot, adapts and stores it
+    WDEV void adapt_reloaded(const uint32_t* adr, const int* src, const int* slot, const int* use, const int* obs, uint32_t off) {
+        LV(uint32_t, Wd); LV(uint32_t, ad);
+        lepwave::wave_gather(adr, src, ad);
+        LANES(l) {
+            L(ad) += off + (uint32_t)L(slot);
+            L(Wd) = 0;
+            if (L(use)) L(Wd) = model[L(ad)];
+        }
+        adapt_words(Wd, use, obs);
+        LANES(l) if (L(use)) model[L(ad)] = L(Wd);
+    }
 
     // ---- round 1: the 6-bit count of interior non-zeros (model.hh:463-485) --------------------------------------------
     WDEV int round_nz(int nzbin_ctx) {
@@ -872,7 +914,14 @@ struct Dec4WaveT {
         // ---- owners adapt ---------------------------------------------------------------------------------------------------
         LEP_MARK("77_update"); LEP_PRIO_PARALLEL();
         LV(int, nzw);
+#if LEP_DEC4_LANE_SELECTS
+        {   // (& 63: in range for every lane); the window's visited part is a scalar bound
+            const int seen = imin(16, zz - zz0);
+            LANES(l) L(nzw) = (l < seen) & (S.here[(zz0 + l) & 63] != 0);
+        }
+#else
         LANES(l) L(nzw) = l < 16 && zz0 + l < zz && S.here[zz0 + l] != 0;
+#endif
         const uint32_t nzmask = (uint32_t)lepwave::wave_ballot(nzw);
         LV(int, u0); LV(int, b0); LV(int, u1); LV(int, b1); LV(int, u2); LV(int, b2);
 #if LEP_DEC4_WORD_PER_LANE
@@ -881,6 +930,28 @@ struct Dec4WaveT {
         // (No test of the source lane's `valid`: the candidate in force at a visited position is nzbin(left_at) with left0 - pi <= left_at
         // <= nzhi(that bin), which is the prefetch condition, and the serial loop ends before a candidate >= LEP_DEC4_CANDS is coded.)
         LV(int, src); LV(int, slot);
+#if LEP_DEC4_LANE_SELECTS
+        // branch-free: every lane works its position out (p <= 63, left_at clamped into nzbin's 64 entries) and the lanes of positions that
+        // were not visited, or not under a candidate, select "not used" at the end.  Observations of unused words are not read.
+        LANES(l) {
+            const int pi = l & 15, k = l >> 4, p = zz0 + pi;
+            const int left_at = left0 - __builtin_popcount(nzmask & ((1u << pi) - 1));
+            const int c = nb0 - (int)S.nzbin[left_at > 0 ? left_at : 0];
+            const int cf = S.here[p];
+            const int v = cf < 0 ? -cf : cf, len = bitlen((uint32_t)v);
+            const int on = (p < zz) & (left_at > 0) & (c < LEP_DEC4_CANDS);
+            L(src) = on ? pi + 16 * c : l; L(slot) = k;
+            L(u0) = on & (k <= len); L(b0) = len != k;
+            L(u1) = on & (k <= len - 2); L(b1) = (v >> k) & 1;
+#if LEP_DEC4_WPL2
+            L(u2) = on & (4 + k <= imin(len, 10)); L(b2) = len != 4 + k;   // exponent word 4 + k, one per lane (words 8..10 are coded straight from HBM)
+#else
+            int uc, bcc;
+            mask_exp(4, len, uc, bcc);
+            L(u2) = (on & (c == k)) ? uc : 0; L(b2) = bcc;
+#endif
+        }
+#else
         LANES(l) {
             int s = l, ua = 0, oa = 0, ub = 0, ob = 0, uc = 0, bcc = 0;
             const int pi = l & 15, k = l >> 4, p = zz0 + pi;
@@ -898,6 +969,7 @@ struct Dec4WaveT {
             }
             L(src) = s; L(slot) = k; L(u0) = ua; L(b0) = oa; L(u1) = ub; L(b1) = ob; L(u2) = uc; L(b2) = bcc;
         }
+#endif
         adapt_regrouped(W0, a0, src, slot, u0, b0);
         if (lepwave::wave_ballot(u1)) adapt_regrouped(W1, a1, src, slot, u1, b1);
 #else
@@ -923,12 +995,16 @@ struct Dec4WaveT {
             if (L(u1)) st4(model + L(a1), L(W1));
         }
 #endif
+#if LEP_DEC4_WPL2
+        if (lepwave::wave_ballot(u2)) adapt_reloaded(a0, src, slot, u2, b2, kGS);   // exponent words 4..7 (rare in the interior)
+#else
         if (lepwave::wave_ballot(u2)) {   // exponent words 4..7: re-read by the owner (rare in the interior)
             LV(U4, W2);
             LANES(l) if (L(u2)) L(W2) = ld4(model + L(a0) + kGS);
             adapt_group<0>(W2, u2, b2);
             LANES(l) if (L(u2)) st4(model + L(a0) + kGS, L(W2));
         }
+#endif
         LSYNC();
         zz_io = zz; left_io = left;
     }
@@ -1089,6 +1165,24 @@ struct Dec4WaveT {
 #if !LEP_DEC4_WORD_PER_LANE
         LV(int, u0); LV(int, b0);
 #endif
+#if LEP_DEC4_WPL2
+        // (no owners: u1 / b1 and u2 / b2 are per-word masks on the lanes of the word-per-lane map below)
+#elif LEP_DEC4_LANE_SELECTS && LEP_DEC4_WORD_PER_LANE
+        // branch-free: lanes 56..63 compute as combo 0 (cj / cn / here / thr read in range) and select "not used"
+        LANES(l) {
+            const int lc = l < 56 ? l : 0;
+            const int e = lc >= 28 ? 1 : 0, c = lc - e * 28, j = S.cj[c], n = S.cn[c];
+            const uint32_t mk = e ? mv : mh;
+            const int left_at = (e ? nev : neh) - __builtin_popcount(mk & ((1u << j) - 1));
+            const int cf = S.here[(e ? 57 : 50) + j];
+            const int v = cf < 0 ? -cf : cf, len = bitlen((uint32_t)v);
+            int ub, bb, uc, bcc;
+            mask_exp(4, len, ub, bb);
+            mask_res(imin(len - 2, (int)S.thr[e ? (j + 1) * 8 : j + 1] - 1), v, uc, bcc);
+            const int on = (l < 56) & (left_at == n);   // n >= 1: the position was visited with n non-zeros left
+            L(u1) = on ? ub : 0; L(b1) = bb; L(u2) = on ? uc : 0; L(b2) = bcc;
+        }
+#else
         LANES(l) {
             int ua = 0, ba = 0, ub = 0, bb = 0, uc = 0, bcc = 0;
             if (l < 56) {
@@ -1116,11 +1210,36 @@ struct Dec4WaveT {
 #endif
             L(u1) = ub; L(b1) = bb; L(u2) = uc; L(b2) = bcc;
         }
+#endif
 #if LEP_DEC4_WORD_PER_LANE
         {   // exponent words 0..3 of the 14 positions on lanes 4 * (e * 7 + j) + slot, from the one combo lane the position was coded under;
             // lanes 56..61: the word of its tree level that the count's prefix selects.  (Exponent words 4..7 and the residual words keep
             // their owners' form below: u1 / u2.)
             LV(int, src); LV(int, slot); LV(int, use); LV(int, ob);
+#if LEP_DEC4_LANE_SELECTS
+            // branch-free: both kinds of lane compute both answers on clamped indices (position 13 for lanes 56.., level 0 of the horizontal
+            // tree for lanes outside 56..61) and select
+            LANES(l) {
+                const int q = imin(l >> 2, 13), e = q >= 7 ? 1 : 0, j = q - 7 * e;
+                const int left_at = (e ? nev : neh) - __builtin_popcount((e ? mv : mh) & ((1u << j) - 1));
+                const int cf = S.here[(e ? 57 : 50) + j];
+                const int v = cf < 0 ? -cf : cf, len = bitlen((uint32_t)v);
+                const int kp = l & 3;
+                const int vis = (l < 56) & ((uint32_t)(left_at - 1) < (uint32_t)(7 - j));   // visited, and not on the path that codes straight from HBM
+                const int tr = (l >= 56) & (l < 62), t = tr ? l - 56 : 0;
+                const int te = t >= 3 ? 1 : 0, i = 2 - (t - 3 * te), value = te ? nev : neh;
+                L(src) = vis ? e * 28 + ((j * (15 - j)) >> 1) + left_at - 1 : l;   // combo_base(j) = j * (15 - j) / 2
+                L(slot) = tr ? (value >> (i + 1)) & 3 : kp;
+                L(use) = tr | (vis & (kp <= len));
+                L(ob) = tr ? (value >> i) & 1 : len != kp;
+#if LEP_DEC4_WPL2
+                // the position's exponent word 4 + kp (words 8..10 are coded straight from HBM) and residual word kp (bits 0 .. min(len - 2,
+                // threshold - 1, 3) of |v| go through the residual group) on the same lanes, from the same combo lane
+                L(u1) = vis & (4 + kp <= imin(len, 10)); L(b1) = len != 4 + kp;
+                L(u2) = vis & (kp <= imin(len - 2, (int)S.thr[e ? (j + 1) * 8 : j + 1] - 1)); L(b2) = (v >> kp) & 1;
+#endif
+            }
+#else
             LANES(l) {
                 int s = l, k = l & 3, u = 0, o = 0;
                 if (l < 56) {
@@ -1138,12 +1257,18 @@ struct Dec4WaveT {
                 }
                 L(src) = s; L(slot) = k; L(use) = u; L(ob) = o;
             }
+#endif
             adapt_regrouped(W0, a0, src, slot, use, ob);
+#if LEP_DEC4_WPL2
+            if (lepwave::wave_ballot(u1)) adapt_reloaded(a0, src, slot, u1, b1, kGS);
+            if (lepwave::wave_ballot(u2)) adapt_regrouped(W2, a2, src, slot, u2, b2);
+#endif
         }
 #else
         adapt_group<3>(W0, u0, b0);
         LANES(l) if (L(u0)) st4(model + L(a0), L(W0));
 #endif
+#if !LEP_DEC4_WPL2
         if (lepwave::wave_ballot(u1)) {
             LANES(l) if (L(u1)) L(W1) = ld4(model + L(a0) + kGS);   // read on demand by the serial code: the owner re-reads it
             adapt_group<0>(W1, u1, b1);
@@ -1153,6 +1278,7 @@ struct Dec4WaveT {
             adapt_group<0>(W2, u2, b2);
             LANES(l) if (L(u2)) st4(model + L(a2), L(W2));
         }
+#endif
         LSYNC();
         return 0;
     }
@@ -1165,7 +1291,14 @@ struct Dec4WaveT {
         LANES(l) {
             uint32_t adr = 0, pk = 0, rw = 0;
             if (l < 3) { adr = ctx_expdc(a, b17) + (uint32_t)l * 4; L(W0) = ld4(model + adr); pk = pack_probs(L(W0)); }
+#if LEP_DEC4_LANE_SELECTS
+            {   // residual Branch of bit l-3 on lanes 3..12: an LDS read at a clamped index for every lane, selected
+                const uint32_t r = S.resdc[a * 12 + imin(l < 3 ? 0 : l - 3, 9)];
+                rw = ((l >= 3) & (l < 13)) ? r : 0u;
+            }
+#else
             else if (l < 13) rw = S.resdc[a * 12 + (l - 3)];   // residual Branch of bit l-3
+#endif
             L(a0) = adr; L(PK0) = pk; L(RW) = rw;
         }
         LEP_MARK("dc_serial"); LEP_PRIO_SERIAL((SCMASK & 8) != 0);
@@ -1240,10 +1373,33 @@ struct Dec4WaveT {
     }
 
     // Decodes one block into sh->here (aligned order). left / above / aleft / ns_* are staged by the caller.
-    WDEV int decode_block(bool has_left, bool has_above) {
+    static WDEV uint8_t bsr_of(int prior) { return (uint8_t)bitlen((uint32_t)imin(iabs(prior), 1023)); }
+    WDEV int decode_block(bool has_left_, bool has_above_) {
         Dec4Shared& S = *sh;
+        const bool has_left = LEP_UFLAG(has_left_), has_above = LEP_UFLAG(has_above_);
         // ---- contexts that do not depend on this block's bits ---------------------------------------------
         LEP_MARK("prologue");
+#if LEP_DEC4_UNIFORM_TESTS
+        // the neighbour case is the wavefront's: one scalar branch around each case's whole body.  (LEP_DEC4_LANE_SELECTS: bsr has 64 slots
+        // and left / above / aleft 64 entries; slots 49..63 are never read, so all lanes store theirs.)
+        int nzctx;
+        {
+            const int nz_above = unii(S.ns_above.nz), nz_left = unii(S.ns_left.nz);   // 0..49
+            if (has_left && has_above) {
+                LANES(l) { S.here[l] = 0; if (LEP_DEC4_LANE_SELECTS || l < 49) S.bsr[l] = bsr_of((uint16_t)((iabs(S.left[l]) + iabs(S.above[l])) * 13 + 6 * iabs(S.aleft[l])) >> 5); }
+                nzctx = (int)((uint32_t)(nz_above + nz_left + 2) >> 2);
+            } else if (has_left) {
+                LANES(l) { S.here[l] = 0; if (LEP_DEC4_LANE_SELECTS || l < 49) S.bsr[l] = bsr_of((int16_t)iabs(S.left[l])); }
+                nzctx = (int)((uint32_t)(nz_left + 1) >> 1);
+            } else if (has_above) {
+                LANES(l) { S.here[l] = 0; if (LEP_DEC4_LANE_SELECTS || l < 49) S.bsr[l] = bsr_of((int16_t)iabs(S.above[l])); }
+                nzctx = (int)((uint32_t)(nz_above + 1) >> 1);
+            } else {
+                LANES(l) { S.here[l] = 0; if (LEP_DEC4_LANE_SELECTS || l < 49) S.bsr[l] = 0; }
+                nzctx = 0;
+            }
+        }
+#else
         LANES(l) {
             S.here[l] = 0;
             if (l < 49) {
@@ -1259,6 +1415,7 @@ struct Dec4WaveT {
         if (has_left && has_above) nzctx = (S.ns_above.nz + S.ns_left.nz + 2) / 4;
         else if (has_above) nzctx = (S.ns_above.nz + 1) / 2;
         else if (has_left) nzctx = (S.ns_left.nz + 1) / 2;
+#endif
         const int nzbin_ctx = (int)uni((uint32_t)nzbin_of(nzctx));
         LSYNC();
 
@@ -1277,7 +1434,15 @@ struct Dec4WaveT {
             LV(int, tx); LV(int, ty); LV(int, badf);
             LANES(l) {
                 int ex = 0, ey = 0, bad = 0;
+#if LEP_DEC4_LANE_SELECTS
+                {   // here and a2r have 64 entries: every lane reads its own, the interior's non-zero lanes keep the coordinates
+                    const int coord = S.a2r[l];
+                    const int in = (l < 49) & (S.here[l] != 0);
+                    ex = in ? coord & 7 : 0; ey = in ? coord >> 3 : 0;
+                }
+#else
                 if (l < 49 && S.here[l] != 0) { const int coord = S.a2r[l]; ex = coord & 7; ey = coord >> 3; }
+#endif
                 if (l < 14) {
                     const bool hz = l < 7;
                     const int j = hz ? l : l - 7;
@@ -1318,8 +1483,21 @@ struct Dec4WaveT {
             LV(int, emin); LV(int, emax); LV(int, s0); LV(int, s1); LV(int, tmp);
             LANES(l) {
                 int ev = 0, have = 0;
+#if LEP_DEC4_LANE_SELECTS
+                {   // lanes 0..7: the left neighbour's column against pixel columns 0 / 1 of row i; lanes 8..15: the one above, rows 0 / 1 of column i.
+                    // One form for both (the indices are selected, not the values); every lane computes on i = l & 7, lanes 16.. select 0
+                    const int i = l & 7;
+                    const bool lf = (l & 8) == 0;
+                    const int p0 = S.pix[lf ? i : i * 8], p1 = S.pix[lf ? 8 + i : i * 8 + 1];   // LEP_PIX(S, i, 0), (S, i, 1) : LEP_PIX(S, 0, i), (S, 1, i)
+                    const int16_t* nsp = lf ? S.ns_left.vert : S.ns_above.horiz;
+                    const int nsv = nsp[i];
+                    have = (l < 16) & (lf ? (int)has_left : (int)has_above);
+                    ev = have ? (int)(int16_t)(nsv - half16(p0 - p1) - (p0 + 1024)) : 0;
+                }
+#else
                 if (l < 8 && has_left) { have = 1; ev = (int16_t)(S.ns_left.vert[l] - half16(LEP_PIX(S, l, 0) - LEP_PIX(S, l, 1)) - (LEP_PIX(S, l, 0) + 1024)); }
                 if (l >= 8 && l < 16 && has_above) { const int i = l - 8; have = 1; ev = (int16_t)(S.ns_above.horiz[i] - half16(LEP_PIX(S, 0, i) - LEP_PIX(S, 1, i)) - (LEP_PIX(S, 0, i) + 1024)); }
+#endif
                 L(emax) = have ? ev : -0x7fffffff;
                 L(emin) = have ? -ev : -0x7fffffff;
                 L(s0) = l < 8 ? ev : 0;
@@ -1345,6 +1523,20 @@ struct Dec4WaveT {
         // ---- neighbour summary (block_context.hh:44-78) -------------------------------------------------------------
         LEP_MARK("publish");
         pad_block((uint32_t)pred, sh);
+#if LEP_DEC4_LANE_SELECTS
+        // the summary as 18 half words (vert[8], horiz[8], nz): lanes 0..7 horiz[i] from pixel rows 7 / 6, lanes 8..15 vert[i] from pixel columns 7 / 6
+        // (indices selected), lanes 16 / 17 the two halves of nz -- one store, one lane range
+        static_assert(__builtin_offsetof(NSum, vert) == 0 && __builtin_offsetof(NSum, horiz) == 16 && __builtin_offsetof(NSum, nz) == 32, "publish writes NSum as half words");
+        LANES(l) {
+            const int i = l & 7;
+            const bool hz = (l & 8) == 0;
+            const int pa = S.pix[hz ? i * 8 + 7 : 56 + i], pb = S.pix[hz ? i * 8 + 6 : 48 + i];   // LEP_PIX(S, 7, i), (S, 6, i) : LEP_PIX(S, i, 7), (S, i, 6)
+            const int dcq = S.here[49] * (int)S.q[0];
+            const int edge = dcq + pa + 1024 + half16(pa - pb);
+            const int val = l < 16 ? edge : (l == 16 ? nz : nz >> 16);
+            if (l < 18) ((int16_t*)&S.ns_here)[l < 16 ? l ^ 8 : l] = (int16_t)val;
+        }
+#else
         LANES(l) {
             if (l < 16) {
                 const int i = l & 7;
@@ -1354,6 +1546,7 @@ struct Dec4WaveT {
             }
             if (l == 16) S.ns_here.nz = nz;
         }
+#endif
         LSYNC();
         return 0;
     }
@@ -1382,7 +1575,7 @@ struct Dec4WaveT {
             stage_component(r.component);
             const int w = img->width[comp], yb = r.curr_y;
             int16_t* row = img->blocks[comp] + (int64_t)yb * w * 64;
-            const bool has_above = !top[comp];
+            const bool has_above = LEP_UFLAG(!top[comp]);
             const int16_t* arow = has_above ? row - (int64_t)w * 64 : nullptr;
             NSum* nrow = ns + img->ns_offset[comp] + (yb & 1) * w;
             const NSum* narow = ns + img->ns_offset[comp] + ((yb & 1) ^ 1) * w;
@@ -1394,9 +1587,32 @@ struct Dec4WaveT {
             }
             // a truncated image's last row ends with the last coded block (at least one block of a row is always coded)
             const int coded_here = (int)img->coded_blocks[comp] - yb * w;
-            const int x_end = imin(w, coded_here < 1 ? 1 : coded_here);
+            const int x_end = LEP_UINT(imin(w, coded_here < 1 ? 1 : coded_here));
             for (int x = 0; x < x_end; ++x) {
                 LEP_MARK("staging");
+#if LEP_DEC4_UNIFORM_TESTS
+                // "not the row's first block" and "one more block to fetch for" as scalar branches around the bodies.  In a top row nxt_above /
+                // nxt_ns are zero and nobody reads above / ns_above, so those two are stored without a test; the two LDS stores of the
+                // nine summary words share one lane range (the first block copies ns_left onto itself: the source is a scalar select)
+                const bool first = uflag(x == 0), more = uflag(has_above && x + 1 < x_end);
+                if (!first) { LANES(l) { sh->left[l] = sh->here[l]; sh->aleft[l] = sh->above[l]; } }
+                {
+                    const uint32_t* ns_from = first ? (const uint32_t*)&sh->ns_left : (const uint32_t*)&sh->ns_here;
+                    LANES(l) {
+                        sh->above[l] = L(nxt_above);
+                        if (l < (int)(sizeof(NSum) / 4)) { ((uint32_t*)&sh->ns_left)[l] = ns_from[l]; ((uint32_t*)&sh->ns_above)[l] = L(nxt_ns); }
+                    }
+                }
+                LSYNC();
+                if (more) {
+                    LANES(l) {
+                        L(nxt_above) = arow[(int64_t)(x + 1) * 64 + l];
+                        if (l < (int)(sizeof(NSum) / 4)) L(nxt_ns) = ((const uint32_t*)&narow[x + 1])[l];
+                    }
+                }
+                LSYNC();
+                int rc = unii(decode_block(!first, has_above));
+#else
         LANES(l) {
                     if (x) { sh->left[l] = sh->here[l]; sh->aleft[l] = sh->above[l]; }
                     if (l < (int)(sizeof(NSum) / 4)) {
@@ -1414,6 +1630,7 @@ struct Dec4WaveT {
                 }
                 LSYNC();
                 int rc = decode_block(x > 0, has_above);
+#endif
                 if (ROWS) if (rc) { rw->state = kRowsFailed; rw->fail_component = comp; rw->fail_y = yb; rw->fail_x = x; }
                 if (rc) return rc;
                 LEP_MARK("store");

@@ -67,6 +67,11 @@ WDEV uint32_t uni(uint32_t v) {
     return v;
 #endif
 }
+// uni() for a flag and for a small signed value that are wave-uniform by construction but reach the code as a lane mask or in a
+// VGPR (loop state of the block walk, a count read from LDS): tests on them are then s_cmp + s_cbranch around whole lane-parallel
+// bodies, not s_and_saveexec regions inside them.  Outside LANES the lane-loop emulation runs uniform code once: identity there.
+WDEV bool uflag(bool c) { return uni(c ? 1u : 0u) != 0; }
+WDEV int unii(int v) { return (int)uni((uint32_t)v); }
 // the opposite of uni(): hides from the compiler that a value is wave-uniform, so that what is computed from it is
 // placed on the vector ALUs (used to move part of the serial work off the scalar unit)
 WDEV uint32_t vec(uint32_t v) {
