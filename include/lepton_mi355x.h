@@ -117,7 +117,7 @@ int lep_gpu_decode_device(lep_gpu *g, const lep_image_desc *images, int nimg, co
  * text; the other set stays usable after lep_gpu_use_arena.  advance / end act on the set that is current when they are called.
  * lep_gpu_decode_device / _host are unchanged and do not go through the banded kernel. */
 typedef struct lep_decode_progress {       /* one per segment, caller's order */
-    int32_t status;                        /* -1 running, 0 finished, otherwise the exit code */
+    int32_t status;                        /* -1 running, -2 retired by the caller, 0 finished, otherwise the exit code */
     int32_t rows_done[LEP_MAX_COMPONENTS]; /* every block row of component c that is this segment's and lies below rows_done[c] is in the frame */
     int32_t fail_component, fail_y, fail_x;/* the block at which status became non-zero (it is not stored, everything before it is); -1 otherwise */
     uint32_t bins;
@@ -126,6 +126,13 @@ int lep_gpu_decode_rows_begin(lep_gpu *g, const lep_image_desc *images, int nimg
                               const uint8_t *d_streams, const uint64_t *stream_offsets, const uint32_t *d_stream_len, void *hip_stream);
 int lep_gpu_decode_rows_advance(lep_gpu *g, int band_mcu_rows, lep_decode_progress *progress /* host, nseg */, int *running);
 int lep_gpu_decode_rows_end(lep_gpu *g);
+/* Between two advances (or before the first): the session's segments seg_index[0..n) -- the caller's order, as in progress[] -- are
+ * retired.  A retired segment is decoded no further: later advances leave at its record, touch nothing of it and do not count it in
+ * *running; its progress.status is -2 and its rows_done stays what the last band left.  Rows below rows_done are in the frame, nothing
+ * behind them was stored.  A segment that has finished or failed keeps its state.  The record's state word is written by a copy in
+ * the order of the session's stream.  LEP_ASSERTION_FAILURE with a lep_gpu_last_error text: no session on the current workspace set,
+ * or an index that is not one of the session's.  A caller that never retires sees no difference. */
+int lep_gpu_decode_rows_retire(lep_gpu *g, const int32_t *seg_index, int n);
 /* Workspace set (0 or 1) the next lep_gpu_*_device launches use.  Two launches that overlap in time (different hip streams) must
  * use different sets; a set may be reused once the launch that used it has finished (stream order does that when the same
  * stream always goes with the same set).  Default 0. */
@@ -193,6 +200,14 @@ int lep_gpu_huffman_encode_device(lep_gpu *g, const lep_huff_image *images, int 
  * session's: it may be called while a session is open on that set. */
 int lep_gpu_pack_device(lep_gpu *g, const uint8_t *d_src, const uint64_t *src_off, const uint32_t *d_len, int n,
                         uint8_t *d_dst, uint64_t d_dst_cap, uint64_t *d_dst_off, void *hip_stream);
+/* The same with a window per run: run i contributes its bytes [win_skip[i], min(d_len[i], win_skip[i] + win_take[i])) -- nothing when
+ * d_len[i] <= win_skip[i].  win_skip / win_take are host arrays that the call copies; the clipped lengths are made on the device from
+ * d_len, and d_dst_off[0..n] is their prefix sum.  The copy starts at d_src + src_off[i] + win_skip[i] at whatever alignment that leaves,
+ * loads no dword that holds no byte of the window and writes nothing behind d_dst + d_dst_off[n]; the cap, n <= 16384 and the use while a
+ * session is open are as above. */
+int lep_gpu_pack_window_device(lep_gpu *g, const uint8_t *d_src, const uint64_t *src_off, const uint32_t *d_len,
+                               const uint32_t *win_skip, const uint32_t *win_take, int n,
+                               uint8_t *d_dst, uint64_t d_dst_cap, uint64_t *d_dst_off, void *hip_stream);
 /* Progressive files that END INSIDE A SCAN (no EOI) in lep_compress_batch / lep_decompress_batch: on = 1 sends them to the scan kernels
  * (lep_jpeg_open_gpu_progressive_cut, lep_file_recode_plan_progressive_cut), on = 0 -- what a codec starts with, unless
  * LEP_CUT_PROGRESSIVE=1 was set when it was made -- keeps them with the host parser and re-coder, where every earlier release had them;
@@ -451,6 +466,14 @@ int lep_file_recode_plan(lep_file *f, lep_huff_image *image, lep_huff_segment *s
 int lep_file_recode_head(const lep_file *f, const uint8_t **data, size_t *len);
 /* ends: the kernel's per-segment end states (NULL: only the byte counts are held against the hand-offs) */
 int lep_file_recode_finish(lep_file *f, const lep_bytes *seg_bytes, const lep_huff_end *ends, int nseg, lep_bytes *out);
+/* The same checks and the same tail one by one, for a caller that kept a segment's end state and byte count but not its bytes (a range
+ * read).  _segment_end: segment q ran to its end in state *end with `bytes` bytes; last_given != 0: it is the last one of the file.
+ * 0, LEP_GPU_PATH_DECLINED (what the writer said about a cut: the host re-coder decides) or LEP_ASSERTION_FAILURE (partial byte, bit
+ * count, last DCs or byte count are not what hand-off q + 1 recorded).  _tail: what the finish writes behind the last segment's bytes
+ * (misplaced restart markers, the rest of the header, the garbage) when bytes_in_front bytes stand in front of it; *first (may be
+ * NULL) is where it starts: bytes_in_front, or the bound in front of the garbage where that is less.  Both need the plan. */
+int lep_file_recode_segment_end(lep_file *f, int q, const lep_huff_end *end, uint64_t bytes, int last_given);
+int lep_file_recode_tail(lep_file *f, uint64_t bytes_in_front, lep_bytes *out, uint64_t *first);
 /* progressive files: _plan fills the image and up to `cap` scan descriptors (out_cap / corr_cap = what each scan may need;
  * image index, out_off, corr_off and blocks[] are the caller's to set); *gpu_ok = 0: the file keeps the host re-coder
  * (truncated, withheld restart markers ...).  SEQUENTIAL frames coded in several scans are planned here too: their scans have
@@ -522,6 +545,34 @@ int lep_decompress_stream(lep_gpu *g, const uint8_t *lepdata, size_t len, int ba
 /* Host only: does lep_decompress_stream / lep_decompress_batch_stream decode this .lep in a session?  1 / 0, or the exit code (> 1) of a
  * file that does not parse.  (A parse that ends in LEP_ASSERTION_FAILURE, which is 1, answers 0: the file is not streamed.) */
 int lep_file_streams_in_session(const uint8_t *lepdata, size_t len);
+/* Host only: where the bytes [first, first + length) of the restored file lie.  A file that is decoded in a session is its head (what
+ * stands in front of the scan; of a -startbyte / -trunc file, which counts in its own bytes, the prefix garbage), one extent per thread
+ * segment and the tail (misplaced restart markers, the rest of the header, the garbage).  Every segment but the last writes exactly the
+ * segment_size its hand-off records -- the finish holds it to that --, so seg_first[] and every seg_len[] but the last are the header's
+ * (sizes_known = 0: a hand-off whose size the finish does not hold, or cannot be met; the extents are then a guess).  The last
+ * segment's seg_len is "to the tail": right when the file has jpeg_size bytes and no bound cuts its tail, which the header does not
+ * prove (last_len_known = 0, always); the segment's true end is found by decoding it.
+ * length == 0: to the end.  The range is clipped to jpeg_size (`first`, `length` say how); first >= jpeg_size is an empty answer:
+ * length 0, no segment, return value 0.  first_seg / last_seg: the segments the range touches (-1: none); win_skip / win_take: per
+ * touched segment the window, from the segment's first byte -- the last segment's window is open to where the garbage starts (scan_bound),
+ * its take may outlast the segment, and reaches_last says that the range reaches behind the last segment's start: that segment is then
+ * touched even by a range that lies in the tail (win_take 0) and must be decoded, to its end when the window outlasts it.  A file that is not decoded in a session (in_session = 0: progressive, several scans, chained, ...)
+ * has nseg = 0 and no extents; jpeg_size and the clipped range are filled.  Returns 0, or the exit code of a file that does not parse. */
+typedef struct lep_range_plan {
+    int32_t  in_session;                 /* what lep_file_streams_in_session answers */
+    int32_t  nseg;
+    uint64_t jpeg_size, head_len;
+    uint64_t seg_first[16], seg_len[16];
+    int32_t  sizes_known, last_len_known;
+    uint64_t tail_len;                   /* the tail where no bound cuts it */
+    uint64_t scan_bound;                 /* bytes the file may hold in front of its trailing garbage */
+    uint64_t first, length;              /* the range, clipped */
+    uint64_t head_bytes;                 /* bytes of the head it holds */
+    int32_t  first_seg, last_seg;
+    uint64_t win_skip[16], win_take[16];
+    int32_t  reaches_last, pad;
+} lep_range_plan;
+int lep_file_range_plan(const uint8_t *lepdata, size_t len, uint64_t first, uint64_t length, lep_range_plan *out);
 
 /* Whole batches of files as a pipeline (what `lepton -socket` workers / src/lepton/socket_serve.cc:312-390 would hand to
  * the GPU): JPEG parsing + Huffman scan decode on a host thread pool, coefficient frames over PCIe on a copy stream while
@@ -600,6 +651,39 @@ typedef struct lep_batch_stream_stats {
 int lep_decompress_batch_stream(lep_gpu *g, const lep_bytes *leps, int n, int band_mcu_rows,
                                 lep_batch_sink sink, void *user, int32_t *status,
                                 const lep_batch_options *opt, lep_batch_stream_stats *stats);
+/* Byte-range reads: outs[i] = the bytes [first, first + length) of what lep_decompress returns for leps[i] (length 0: to the end; clipped
+ * to the file; first at or behind its end: an empty answer, status 0), restored from the thread segments the range touches and no others.
+ * Thread segments are independent -- each resets its model, starts with no row above it, its scan writer starts from its own hand-off --
+ * and the header says where every segment but the last starts and ends (lep_file_range_plan).  Which file goes where:
+ *   - a file that is decoded in a session (lep_file_streams_in_session) whose range lies in its head is answered from the header: no
+ *     segment is begun, nothing is launched (files_no_decode);
+ *   - such a file whose range touches segments goes into a session with the touched segments ONLY (files_ranged; sessions of at most
+ *     LEP_STREAM_SESSION_FILES files and 16384 segments).  Frames start zero-filled; rows of other segments are never read.  After every
+ *     advance one scan-writer launch appends the rows every segment completed to its slot, the windowed pack brings down only the bytes
+ *     inside each segment's window, and a segment whose written count has reached the end of its window is retired (in practice a file's
+ *     last touched segment).  The MCU row at which a window ends is not in the file: bands find it.  band_mcu_rows > 0: bands of that
+ *     height; <= 0: 1, 2, 4, ... MCU rows, doubling -- at most ceil(log2 rows) + 1 advances, fewer than twice the rows needed;
+ *   - every other file (not decoded in a session; extents the header does not fix; a writer that declined or a cut the band rule does
+ *     not cover, found during a session) takes ONE lep_decompress_batch call with the others of its kind and is cut on the host
+ *     (files_whole): correct, not economical.
+ * A touched segment that ran to its end is held to the next hand-off as the finish holds it (partial byte, bit count, last DCs, byte
+ * count = segment_size: LEP_ASSERTION_FAILURE for that file); a decode that fails in a touched segment is that file's exit code; a range
+ * that reaches the tail has the last segment run to its end and the tail glued behind it.  DAMAGE IN A SEGMENT THE RANGE DOES NOT TOUCH IS
+ * NOT SEEN: such a range is answered with status 0 where lep_decompress fails.  Files fail alone; a file that does not parse gets
+ * lep_decompress's code.  outs[i].data is malloc'd when status[i] == 0 (lep_free).  The return value is non-zero only when the machinery
+ * failed.  stats may be NULL. */
+typedef struct lep_range { uint64_t first, length; } lep_range;
+typedef struct lep_range_stats {
+    int32_t  files_ranged, files_whole, files_no_decode;   /* in sessions / through lep_decompress_batch and cut on the host / answered from the header alone */
+    int32_t  sessions, advances, writer_launches;
+    int32_t  segments_total, segments_begun, segments_retired;   /* thread segments of the ranged files / of them given to a session / retired */
+    int64_t  mcu_rows_begun, mcu_rows_decoded;             /* planned rows of the begun segments / of them in the frame when their segment finished or was retired */
+    uint64_t scan_bytes_down, frame_bytes_down;            /* PCIe, device -> host: window bytes / frames (always 0: no path of this call moves one) */
+    double   wall_s;
+} lep_range_stats;
+int lep_decompress_batch_ranges(lep_gpu *g, const lep_bytes *leps, const lep_range *ranges, int n, int band_mcu_rows,
+                                lep_bytes *outs, int32_t *status, const lep_batch_options *opt, lep_range_stats *stats);
+int lep_decompress_range(lep_gpu *g, const uint8_t *lepdata, size_t len, uint64_t first, uint64_t length, lep_bytes *out);
 /* the chunking lep_compress_batch will apply: file_bytes[i] / frame_bytes[i] (lep_jpeg_peek_frame_bytes; 0 = not a usable file)
  * -> chunk k holds files [chunk_first[k], chunk_first[k + 1]); returns the number of chunks (cap = entries of chunk_first) */
 int lep_batch_plan(const size_t *file_bytes, const size_t *frame_bytes, int n, const lep_batch_options *opt, int *chunk_first, int cap);

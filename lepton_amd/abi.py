@@ -117,6 +117,25 @@ class BatchStreamStats(C.Structure):
 BATCH_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_size_t)
 
 
+class RangePlan(C.Structure):
+    _fields_ = [("in_session", C.c_int32), ("nseg", C.c_int32), ("jpeg_size", C.c_uint64), ("head_len", C.c_uint64),
+                ("seg_first", C.c_uint64 * 16), ("seg_len", C.c_uint64 * 16), ("sizes_known", C.c_int32), ("last_len_known", C.c_int32),
+                ("tail_len", C.c_uint64), ("scan_bound", C.c_uint64), ("first", C.c_uint64), ("length", C.c_uint64), ("head_bytes", C.c_uint64),
+                ("first_seg", C.c_int32), ("last_seg", C.c_int32), ("win_skip", C.c_uint64 * 16), ("win_take", C.c_uint64 * 16),
+                ("reaches_last", C.c_int32), ("pad", C.c_int32)]
+
+
+class Range(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("length", C.c_uint64)]
+
+
+class RangeStats(C.Structure):
+    _fields_ = [("files_ranged", C.c_int32), ("files_whole", C.c_int32), ("files_no_decode", C.c_int32), ("sessions", C.c_int32),
+                ("advances", C.c_int32), ("writer_launches", C.c_int32), ("segments_total", C.c_int32), ("segments_begun", C.c_int32),
+                ("segments_retired", C.c_int32), ("mcu_rows_begun", C.c_int64), ("mcu_rows_decoded", C.c_int64),
+                ("scan_bytes_down", C.c_uint64), ("frame_bytes_down", C.c_uint64), ("wall_s", C.c_double)]
+
+
 class BatchOptions(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("verify", C.c_int32), ("chunk_frame_bytes", C.c_size_t), ("host_huffman", C.c_int32), ("chunk_images", C.c_int32), ("overlap_launches", C.c_int32)]
 
@@ -217,6 +236,14 @@ def lib():
             L.lep_decompress_batch_stream.argtypes = [vp, P(Bytes), C.c_int, C.c_int, BATCH_SINK_FN, vp, P(C.c_int32), P(BatchOptions), P(BatchStreamStats)]
         if hasattr(L, "lep_file_streams_in_session"):   # (absent from an older build named by LEP_LIB_PATH)
             L.lep_file_streams_in_session.argtypes = [vp, C.c_size_t]
+        if hasattr(L, "lep_decompress_batch_ranges"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_gpu_decode_rows_retire.argtypes = [vp, P(C.c_int32), C.c_int]
+            L.lep_gpu_pack_window_device.argtypes = [vp, vp, P(C.c_uint64), vp, P(C.c_uint32), P(C.c_uint32), C.c_int, vp, C.c_uint64, vp, vp]
+            L.lep_file_range_plan.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_uint64, P(RangePlan)]
+            L.lep_file_recode_segment_end.argtypes = [vp, C.c_int, P(HuffEnd), C.c_uint64, C.c_int]
+            L.lep_file_recode_tail.argtypes = [vp, C.c_uint64, P(Bytes), P(C.c_uint64)]
+            L.lep_decompress_batch_ranges.argtypes = [vp, P(Bytes), P(Range), C.c_int, C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(RangeStats)]
+            L.lep_decompress_range.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint64, P(Bytes)]
         L.lep_gpu_use_arena.argtypes = [vp, C.c_int]
         L.lep_gpu_sync.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
@@ -308,4 +335,6 @@ EXPORTS = [
     "lep_gpu_pack_device", "lep_gpu_stream_pack", "lep_file_recode_head", "lep_decompress_batch_stream",
     "lep_jpeg_cut_block_irregular", "lep_file_recode_plan_progressive_cut", "lep_jpeg_plan_progressive_check_cut", "lep_jpeg_open_gpu_progressive_cut", "lep_gpu_cut_progressive",
     "lep_file_streams_in_session",
+    "lep_gpu_decode_rows_retire", "lep_gpu_pack_window_device", "lep_file_range_plan", "lep_file_recode_segment_end", "lep_file_recode_tail",
+    "lep_decompress_batch_ranges", "lep_decompress_range",
 ]

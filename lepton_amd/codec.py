@@ -200,7 +200,9 @@ class GpuCodec:
         """files: [LepFile].  A generator over a decode session (lep_gpu_decode_rows_*): after every advance of band_mcu_rows MCU rows
         (<= 0: to the end) the files' coefficient frames are fetched from the device and the list of progress records, one per
         segment in the files' order, is yielded; the frames are readable between yields.  The device frames start filled with the
-        byte `fill`.  The session is closed when the generator ends or is closed."""
+        byte `fill`.  The session is closed when the generator ends or is closed.  gen.send([indices]) in place of next(gen) retires
+        those segments (lep_gpu_decode_rows_retire) before the next advance, whose records it returns: a retired segment has status -2,
+        keeps its rows_done and is decoded no further."""
         L, h = self._L, self.handle
         nimg = len(files)
         flat, offs, blob = [], [0], b""
@@ -246,7 +248,12 @@ class GpuCodec:
                 for i, f in enumerate(files):
                     for c in range(f.desc.ncomp):
                         _check(L.lep_gpu_memcpy_d2h(h, f.desc.blocks[c], dev[i].blocks[c], f.desc.nblocks(c) * 128), "lep_gpu_memcpy_d2h")
-                yield [abi.DecodeProgress.from_buffer_copy(prog[k]) for k in range(nseg)]
+                retire = yield [abi.DecodeProgress.from_buffer_copy(prog[k]) for k in range(nseg)]
+                if retire:
+                    idx = (C.c_int32 * len(retire))(*retire)
+                    rc = L.lep_gpu_decode_rows_retire(h, idx, len(retire))
+                    if rc:
+                        raise LeptonError(rc, "lep_gpu_decode_rows_retire [%s]" % self.last_error())
         finally:
             if begun:
                 L.lep_gpu_decode_rows_end(h)
@@ -366,6 +373,46 @@ class GpuCodec:
         if rc:
             raise LeptonError(rc, "lep_decompress_batch_stream [%s]" % self.last_error())
         return pieces, list(status)[:n], {k: getattr(stats, k) for k, _ in abi.BatchStreamStats._fields_}
+
+    def decompress_range(self, lep, first, length=0):
+        """lep_decompress_range: the bytes [first, first + length) of decompress(lep) (length 0: to the end), restored from the thread
+        segments the range touches"""
+        out = abi.Bytes()
+        rc = self._L.lep_decompress_range(self.handle, bytes(lep), len(lep), first, length, C.byref(out))
+        if rc:
+            raise LeptonError(rc, "lep_decompress_range [%s]" % self.last_error())
+        data = out.tobytes()
+        self._L.lep_free(out.data)
+        return data
+
+    def decompress_batch_ranges(self, leps, ranges, band_mcu_rows=0, threads=0):
+        """lep_decompress_batch_ranges: ranges = one (first, length) per file (length 0: to the end) -> (outs, status, stats): per file
+        the range's bytes or None, the exit code per file, and the call's statistics as a dict.  band_mcu_rows <= 0: bands of
+        1, 2, 4, ... MCU rows"""
+        n = len(leps)
+        if len(ranges) != n:
+            raise ValueError("one (first, length) pair per file")
+        ins = (abi.Bytes * max(1, n))()
+        keep = []
+        for i, b in enumerate(leps):
+            buf = C.create_string_buffer(bytes(b), max(1, len(b)))
+            keep.append(buf)
+            ins[i].data = C.cast(buf, C.c_void_p).value
+            ins[i].len = ins[i].cap = len(b)
+        arr = (abi.Range * max(1, n))(*[abi.Range(int(a), int(b)) for a, b in ranges])
+        outs = (abi.Bytes * max(1, n))()
+        status = (C.c_int32 * max(1, n))()
+        opt = abi.BatchOptions(threads, 0, 0, 0, 0)
+        stats = abi.RangeStats()
+        rc = self._L.lep_decompress_batch_ranges(self.handle, ins, arr, n, band_mcu_rows, outs, status, C.byref(opt), C.byref(stats))
+        if rc:
+            raise LeptonError(rc, "lep_decompress_batch_ranges [%s]" % self.last_error())
+        res = []
+        for i in range(n):
+            res.append(outs[i].tobytes() if not status[i] else None)
+            if outs[i].data:
+                self._L.lep_free(outs[i].data)
+        return res, list(status)[:n], {k: getattr(stats, k) for k, _ in abi.RangeStats._fields_}
 
     def scan_second_chances(self):
         """sequential scans the batch compressor handed to the single-wave kernel since the process started, after the

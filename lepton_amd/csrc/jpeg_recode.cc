@@ -24,11 +24,12 @@ namespace {
 struct BoundedOut {   // bounded_iostream / BoundedMemWriter: bytes past the bound are dropped but counted
     std::vector<uint8_t> buf;
     size_t bound = 0, attempted = 0;
+    size_t base = 0;     // bytes that count as written in front of buf (recode_tail for a caller that kept none of them)
     bool shut = false;   // a bound of zero bytes (a worker's buffer resized to nothing); bound == 0 alone means "none"
-    void put(uint8_t b) { ++attempted; if (!shut && (!bound || buf.size() < bound)) buf.push_back(b); }
+    void put(uint8_t b) { ++attempted; if (!shut && (!bound || base + buf.size() < bound)) buf.push_back(b); }
     void write(const uint8_t* d, size_t n) { for (size_t i = 0; i < n; ++i) put(d[i]); }
     bool exceeded() const { return shut ? attempted > 0 : (bound && attempted > bound); }
-    bool reached() const { return shut || (bound && buf.size() >= bound); }
+    bool reached() const { return shut || (bound && base + buf.size() >= bound); }
 };
 
 static inline int blen16(unsigned v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
@@ -261,6 +262,22 @@ int recode_prepare(LepFile* lf, RecodePlan* plan) {
     return 0;
 }
 
+namespace {
+// what follows the last segment's bytes, written behind whatever `out` holds (or counts as held): recode_finish's end, and recode_tail
+void write_tail(LepFile* lf, const RecodePlan& plan, BoundedOut& out) {
+    JpegFile& jf = lf->jpeg;
+    if (!jf.rst_err.empty()) {
+        unsigned cum = jf.rsti ? (unsigned)((jf.mcuh * jf.mcuv - 1) / jf.rsti) : 0;
+        for (unsigned i = 0; i < jf.rst_err[0]; ++i) { out.put(0xFF); out.put((uint8_t)(0xD0 + ((cum + i) & 7))); }
+    }
+    const uint8_t* h = jf.hdr.data();
+    const size_t hdrs = jf.hdr.size();
+    if (!out.reached() && plan.hdr_pos < hdrs) out.write(h + plan.hdr_pos, hdrs - plan.hdr_pos);
+    out.bound = lf->jpeg_size;
+    out.write(jf.garbage.data(), jf.garbage.size());
+}
+}  // namespace
+
 // recode_finish: glue head + per-segment scan bytes + misplaced RST markers + the rest of the header + garbage together
 int recode_finish(LepFile* lf, const RecodePlan& plan, const std::vector<std::pair<const uint8_t*, size_t>>& seg_bytes, const lep_huff_end* ends,
                   std::vector<uint8_t>* result) {
@@ -279,34 +296,61 @@ int recode_finish(LepFile* lf, const RecodePlan& plan, const std::vector<std::pa
     // only if the thread's byte bound was reached by then (then nothing behind the cut can show) and only in the last thread; anything
     // else is the host re-coder's, which knows what the reference reads behind a cut: EX_GPU_PATH_DECLINED tells the caller so
     if (ends)
-        for (size_t q = 0; q < seg_bytes.size() && q < plan.segs.size(); ++q) {
-            if (ends[q].pad & 2) return EX_GPU_PATH_DECLINED;
-            if ((ends[q].pad & 1) && (q + 1 != seg_bytes.size() || ends[q].attempted < plan.segs[q].out_cap)) return EX_GPU_PATH_DECLINED;
-        }
+        for (size_t q = 0; q < seg_bytes.size() && q < plan.segs.size(); ++q)
+            if (int rc = recode_segment_end_declined(plan, q, q + 1 == seg_bytes.size(), ends[q])) return rc;
     if (seg_bytes.size() == lf->segs.size())
-        for (size_t q = 0; q + 1 < seg_bytes.size(); ++q) {
-            const Handoff& nx = lf->segs[q + 1];
-            if (nx.num_overhang_bits == 0xff) continue;
-            if (nx.luma_y_start != nx.luma_y_end || lf->version == 1) {
-                if (ends) {
-                    if (ends[q].num_overhang_bits != nx.num_overhang_bits || ends[q].overhang_byte != nx.overhang_byte) return EX_ASSERTION_FAILURE;
-                    if (memcmp(ends[q].last_dc, nx.last_dc, 3 * sizeof(int16_t))) return EX_ASSERTION_FAILURE;
-                }
-                if (seg_bytes[q].second != lf->segs[q].segment_size && !(q == 0 && out.buf.size() + seg_bytes[q].second >= out.bound)) return EX_ASSERTION_FAILURE;
-            }
-        }
+        for (size_t q = 0; q + 1 < seg_bytes.size(); ++q)
+            if (int rc = recode_segment_end_check(*lf, plan, q, ends ? &ends[q] : nullptr, seg_bytes[q].second)) return rc;
     for (const auto& sb : seg_bytes) out.write(sb.first, sb.second);
-    if (!jf.rst_err.empty()) {
-        unsigned cum = jf.rsti ? (unsigned)((jf.mcuh * jf.mcuv - 1) / jf.rsti) : 0;
-        for (unsigned i = 0; i < jf.rst_err[0]; ++i) { out.put(0xFF); out.put((uint8_t)(0xD0 + ((cum + i) & 7))); }
-    }
-    const uint8_t* h = jf.hdr.data();
-    const size_t hdrs = jf.hdr.size();
-    if (!out.reached() && plan.hdr_pos < hdrs) out.write(h + plan.hdr_pos, hdrs - plan.hdr_pos);
-    out.bound = max_file_size;
-    out.write(jf.garbage.data(), jf.garbage.size());
+    write_tail(lf, plan, out);
     result->swap(out.buf);
     return 0;
+}
+
+// What the scan encoder said about the cut of a truncated file, for segment q (last_given: the last one of the caller's list).
+int recode_segment_end_declined(const RecodePlan& plan, size_t q, bool last_given, const lep_huff_end& end) {
+    if (end.pad & 2) return EX_GPU_PATH_DECLINED;
+    if ((end.pad & 1) && (!last_given || end.attempted < plan.segs[q].out_cap)) return EX_GPU_PATH_DECLINED;
+    return 0;
+}
+
+// The end of segment q (not the file's last) held to hand-off q + 1: partial byte, bit count, last DCs (where the caller has an end
+// state) and the byte count -- made from counts and end states alone, so a caller that kept no bytes can make them too.
+int recode_segment_end_check(const LepFile& lf, const RecodePlan& plan, size_t q, const lep_huff_end* end, uint64_t bytes) {
+    if (q + 1 >= lf.segs.size()) return 0;
+    const Handoff& nx = lf.segs[q + 1];
+    if (nx.num_overhang_bits == 0xff) return 0;
+    if (nx.luma_y_start != nx.luma_y_end || lf.version == 1) {
+        if (end) {
+            if (end->num_overhang_bits != nx.num_overhang_bits || end->overhang_byte != nx.overhang_byte) return EX_ASSERTION_FAILURE;
+            if (memcmp(end->last_dc, nx.last_dc, 3 * sizeof(int16_t))) return EX_ASSERTION_FAILURE;
+        }
+        if (bytes != lf.segs[q].segment_size && !(q == 0 && plan.head.size() + bytes >= plan.scan_bound)) return EX_ASSERTION_FAILURE;
+    }
+    return 0;
+}
+
+// Is the byte count of segment q (not the last) one the header fixes -- does recode_segment_end_check hold it to segment_size, and can
+// the segment write that many (recode_prepare clamps out_cap to what the file and the segment's blocks may hold)?
+bool recode_segment_size_known(const LepFile& lf, const RecodePlan& plan, size_t q) {
+    if (q + 1 >= lf.segs.size() || q >= plan.segs.size()) return false;
+    const Handoff& nx = lf.segs[q + 1];
+    if (nx.num_overhang_bits == 0xff || !(nx.luma_y_start != nx.luma_y_end || lf.version == 1)) return false;
+    const uint64_t size = lf.segs[q].segment_size;
+    return size <= plan.segs[q].out_cap && (q != 0 || plan.head.size() + size < plan.scan_bound);
+}
+
+// What follows the last segment's bytes: misplaced restart markers, the rest of the header, the garbage.
+uint64_t recode_tail_bytes(const LepFile& lf, const RecodePlan& plan) {
+    const JpegFile& jf = lf.jpeg;
+    return (jf.rst_err.empty() ? 0 : (uint64_t)jf.rst_err[0] * 2) + (plan.hdr_pos < jf.hdr.size() ? jf.hdr.size() - plan.hdr_pos : 0) + jf.garbage.size();
+}
+void recode_tail(LepFile* lf, const RecodePlan& plan, uint64_t bytes_in_front, std::vector<uint8_t>* tail) {
+    BoundedOut out;
+    out.bound = plan.scan_bound;
+    out.base = (size_t)bytes_in_front;
+    write_tail(lf, plan, out);
+    tail->swap(out.buf);
 }
 
 // One thread segment of a planned file (recode_prepare said gpu_ok) coded MCU row by MCU row, as far as the caller says its rows are in

@@ -558,6 +558,23 @@ int lep_file_recode_finish(lep_file* f, const lep_bytes* seg_bytes, const lep_hu
     return to_bytes(jpg, out);
 }
 
+// lep_file_recode_finish's checks for one segment that ran to its end, from its end state and byte count alone, and its tail: what a
+// caller that kept no bytes of the segments (a range read) makes of them.
+int lep_file_recode_segment_end(lep_file* f, int q, const lep_huff_end* end, uint64_t bytes, int last_given) {
+    if (!f->planned || !f->plan.gpu_ok || q < 0 || (size_t)q >= f->plan.segs.size() || !end) return LEP_ASSERTION_FAILURE;
+    if (int rc = lep::recode_segment_end_declined(f->plan, (size_t)q, last_given != 0, *end)) return rc;
+    return lep::recode_segment_end_check(f->lf, f->plan, (size_t)q, end, bytes);
+}
+
+int lep_file_recode_tail(lep_file* f, uint64_t bytes_in_front, lep_bytes* out, uint64_t* first) {
+    if (!f->planned || !out) return LEP_ASSERTION_FAILURE;
+    const uint64_t at = std::min<uint64_t>(bytes_in_front, f->plan.scan_bound);
+    std::vector<uint8_t> tail;
+    lep::recode_tail(&f->lf, f->plan, at, &tail);
+    if (first) *first = at;
+    return to_bytes(tail, out);
+}
+
 }  // extern "C"
 
 // ---- layer 3: whole files (JPEG -> .lep -> JPEG) through the GPU hot path ---------------------------

@@ -123,6 +123,18 @@ int recode_progressive_finish(LepFile* lf, const ProgPlan& plan, const std::vect
                               std::vector<uint8_t>* out);
 int recode_finish(LepFile* lf, const RecodePlan& plan, const std::vector<std::pair<const uint8_t*, size_t>>& seg_bytes, const lep_huff_end* ends,
                   std::vector<uint8_t>* out);
+// recode_finish's checks and its tail one by one, for a caller that kept counts and end states but not the bytes (lep_batch_ranges.cc):
+//   _end_declined    what the scan encoder said about a cut: 0 or EX_GPU_PATH_DECLINED
+//   _end_check       the end of segment q held to hand-off q + 1 (partial byte, bit count, last DCs; `end` may be null) and its byte count
+//                    to segment_size: 0 or EX_ASSERTION_FAILURE
+//   _size_known      does _end_check hold segment q to segment_size, and can the segment write that many bytes?
+//   recode_tail      what recode_finish writes behind the last segment, with bytes_in_front bytes counted as written in front of it
+//   recode_tail_bytes   its length where no bound cuts it
+int recode_segment_end_declined(const RecodePlan& plan, size_t q, bool last_given, const lep_huff_end& end);
+int recode_segment_end_check(const LepFile& lf, const RecodePlan& plan, size_t q, const lep_huff_end* end, uint64_t bytes);
+bool recode_segment_size_known(const LepFile& lf, const RecodePlan& plan, size_t q);
+void recode_tail(LepFile* lf, const RecodePlan& plan, uint64_t bytes_in_front, std::vector<uint8_t>* tail);
+uint64_t recode_tail_bytes(const LepFile& lf, const RecodePlan& plan);
 // one thread segment of a planned file Huffman-coded on the host MCU row by MCU row (jpeg_recode.cc): rows [next_row, upto) per call
 class SegmentRowCoder {
 public:

@@ -433,7 +433,8 @@ struct BoolDec4S {
 
 // A segment's resume record (Dec4WaveT::run_rows): all that a segment carries from one band's launch to the next beside its model, its
 // summary rings, the frame and the two LDS-resident Branch tables.  Written by lane 0 at a band's end; all zero = fresh.
-enum : int32_t { kRowsFresh = 0, kRowsRunning = 1, kRowsFinished = 2, kRowsFailed = 3 };
+// kRowsRetired is the host's (lep_gpu_decode_rows_retire): written between two bands, it ends a segment the caller needs no more rows of.
+enum : int32_t { kRowsFresh = 0, kRowsRunning = 1, kRowsFinished = 2, kRowsFailed = 3, kRowsRetired = 4 };
 struct Dec4Resume {
     int32_t state, code;          // kRows*; the exit code when failed
     uint32_t idx, top;            // next schedule index (row_spec); bit c: component c has not had a row in this segment yet

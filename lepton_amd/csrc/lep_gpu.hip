@@ -339,13 +339,26 @@ __global__ __launch_bounds__(256) void lep_zero_kernel(uint4* p, size_t n16) {
 }
 // byte runs that lie apart moved back to back (lep_pack.h): offsets, then one wavefront per run
 __global__ __launch_bounds__(leppack::kScanLanes) void lep_pack_offsets_kernel(const uint32_t* __restrict__ len, int n, uint64_t* __restrict__ dst_off) {
-    leppack::offsets(len, n, dst_off);
+    leppack::offsets([len](int i) { return len[i]; }, n, dst_off);
 }
 __global__ __launch_bounds__(64) void lep_pack_copy_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ len,
                                                            int n, uint8_t* __restrict__ dst, uint64_t dst_cap, const uint64_t* __restrict__ dst_off) {
     if (dst_off[n] > dst_cap) return;
     const int i = (int)blockIdx.x;
     leppack::copy_run(src + src_off[i], dst + dst_off[i], len[i], threadIdx.x & 63u);
+}
+// ... with a window per run (lep_gpu_pack_window_device): the clipped lengths are made here, from the device's lengths, summed, and left in wlen
+__global__ __launch_bounds__(leppack::kScanLanes) void lep_pack_window_offsets_kernel(const uint32_t* __restrict__ len, const uint32_t* __restrict__ skip,
+                                                                                      const uint32_t* __restrict__ take, int n, uint32_t* __restrict__ wlen,
+                                                                                      uint64_t* __restrict__ dst_off) {
+    leppack::offsets([=](int i) { const uint32_t w = leppack::window_len(len[i], skip[i], take[i]); wlen[i] = w; return w; }, n, dst_off);
+}
+__global__ __launch_bounds__(64) void lep_pack_window_copy_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ skip,
+                                                                  const uint32_t* __restrict__ wlen, int n, uint8_t* __restrict__ dst, uint64_t dst_cap,
+                                                                  const uint64_t* __restrict__ dst_off) {
+    if (dst_off[n] > dst_cap) return;
+    const int i = (int)blockIdx.x;
+    leppack::copy_run(src + src_off[i] + skip[i], dst + dst_off[i], wlen[i], threadIdx.x & 63u);
 }
 // ... with one lane per run of MCUs (lep_huff_simt.h): count / place / code / stuff
 template <bool WRITE>
@@ -1264,15 +1277,40 @@ int lep_gpu_decode_rows_advance(lep_gpu* g, int band_mcu_rows, lep_decode_progre
     for (int s = 0; s < R.nseg; ++s) {
         const lep4::Dec4Resume& r = R.h_recs[(size_t)s];
         const bool failed = r.state == lep4::kRowsFailed;
-        if (r.state != lep4::kRowsFinished && !failed) ++still;
+        const bool retired = r.state == lep4::kRowsRetired;
+        if (r.state != lep4::kRowsFinished && !failed && !retired) ++still;
         if (!progress) continue;
         lep_decode_progress& p = progress[s];
-        p.status = r.state == lep4::kRowsFinished ? 0 : (failed ? r.code : -1);
+        p.status = r.state == lep4::kRowsFinished ? 0 : (failed ? r.code : (retired ? -2 : -1));
         for (int c = 0; c < LEP_MAX_COMPONENTS; ++c) p.rows_done[c] = c < 3 ? r.rows_done[c] : 0;
         p.fail_component = failed ? r.fail_component : -1; p.fail_y = failed ? r.fail_y : -1; p.fail_x = failed ? r.fail_x : -1;
         p.bins = r.nbins;
     }
     if (running) *running = still;
+    return 0;
+}
+
+// A segment the caller needs no more rows of: its record's state word becomes kRowsRetired, by a copy in stream order behind the band
+// before, and the rows kernel leaves at its entry from then on.  Finished and failed segments keep their state.
+int lep_gpu_decode_rows_retire(lep_gpu* g, const int32_t* seg_index, int n) {
+    if (!g) return LEP_GPU_ERROR;
+    lep_gpu::RowsSession& R = g->rows[g->cur];
+    if (!R.open) { g->err = "lep_gpu_decode_rows_retire: no decode session on arena set " + std::to_string(g->cur); return LEP_ASSERTION_FAILURE; }
+    if (n < 0 || (n > 0 && !seg_index)) { g->err = "lep_gpu_decode_rows_retire: a list of segment indices"; return LEP_ASSERTION_FAILURE; }
+    for (int k = 0; k < n; ++k)
+        if (seg_index[k] < 0 || seg_index[k] >= R.nseg) {
+            g->err = "lep_gpu_decode_rows_retire: segment index " + std::to_string(seg_index[k]) + " is not one of the session's " + std::to_string(R.nseg);
+            return LEP_ASSERTION_FAILURE;
+        }
+    HIPCHK(g, hipSetDevice(g->device));
+    lep4::Dec4Resume* d_recs = g->ws[lep_gpu::W_ROWS + g->cur].at<lep4::Dec4Resume>(0);
+    static const int32_t kRetired = lep4::kRowsRetired;
+    for (int k = 0; k < n; ++k) {
+        lep4::Dec4Resume& r = R.h_recs[(size_t)seg_index[k]];
+        if (r.state != lep4::kRowsFresh && r.state != lep4::kRowsRunning) continue;
+        HIPCHK(g, hipMemcpyAsync(&d_recs[seg_index[k]].state, &kRetired, sizeof kRetired, hipMemcpyHostToDevice, R.st));
+        r.state = lep4::kRowsRetired;
+    }
     return 0;
 }
 
@@ -1360,6 +1398,35 @@ int lep_gpu_pack_device(lep_gpu* g, const uint8_t* d_src, const uint64_t* src_of
     hipLaunchKernelGGL(lep_pack_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, ws.at<uint64_t>(0), d_len, n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
     HIPCHK(g, hipGetLastError());
     g->last_kernel = "lep_pack_{offsets,copy}_kernel";
+    return 0;
+}
+
+// ... with a window per run: run i gives its bytes [win_skip[i], min(d_len[i], win_skip[i] + win_take[i])).  W_PACK holds
+// src_off[n] | skip[n] | take[n] | the clipped lengths[n] (written by the offsets kernel).
+int lep_gpu_pack_window_device(lep_gpu* g, const uint8_t* d_src, const uint64_t* src_off, const uint32_t* d_len, const uint32_t* win_skip, const uint32_t* win_take,
+                               int n, uint8_t* d_dst, uint64_t d_dst_cap, uint64_t* d_dst_off, void* hip_stream) {
+    if (!g) return LEP_GPU_ERROR;
+    if (n < 0 || n > leppack::kMaxRuns || !d_dst_off || (n > 0 && (!src_off || !d_len || !win_skip || !win_take || !d_src || !d_dst))) {
+        g->err = "lep_gpu_pack_window_device: 0 <= n <= 16384 runs, with their arrays";
+        return LEP_ASSERTION_FAILURE;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
+    HIPCHK(g, hipSetDevice(g->device));
+    if (n == 0) { HIPCHK(g, hipMemsetAsync(d_dst_off, 0, sizeof(uint64_t), st)); return 0; }
+    Workspace& ws = g->ws[lep_gpu::W_PACK + (g->cur & 1)];
+    lepbuf::Layout L;
+    L.add<uint64_t>((size_t)n);
+    const size_t o_skip = L.add<uint32_t>((size_t)n), o_take = L.add<uint32_t>((size_t)n), o_wlen = L.add<uint32_t>((size_t)n);
+    if (int rc = ensure(g, ws, L.bytes())) return rc;
+    if (int rc = upload(g, ws.p, src_off, (size_t)n * sizeof(uint64_t), st)) return rc;
+    if (int rc = upload(g, ws.at<char>(o_skip), win_skip, (size_t)n * sizeof(uint32_t), st)) return rc;
+    if (int rc = upload(g, ws.at<char>(o_take), win_take, (size_t)n * sizeof(uint32_t), st)) return rc;
+    hipLaunchKernelGGL(lep_pack_window_offsets_kernel, dim3(1), dim3(leppack::kScanLanes), 0, st, d_len, (const uint32_t*)ws.at<uint32_t>(o_skip),
+                       (const uint32_t*)ws.at<uint32_t>(o_take), n, ws.at<uint32_t>(o_wlen), d_dst_off);
+    hipLaunchKernelGGL(lep_pack_window_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, (const uint64_t*)ws.at<uint64_t>(0), (const uint32_t*)ws.at<uint32_t>(o_skip),
+                       (const uint32_t*)ws.at<uint32_t>(o_wlen), n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
+    HIPCHK(g, hipGetLastError());
+    g->last_kernel = "lep_pack_window_{offsets,copy}_kernel";
     return 0;
 }
 

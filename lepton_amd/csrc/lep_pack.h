@@ -7,6 +7,9 @@
 //                             Every load is an aligned dword that holds at least one byte of the run (or a single byte of it):
 //                             nothing in front of or behind the run's first / last dword is touched.
 // A total beyond dst_cap copies nothing: every wavefront reads dst_off[n] and leaves.
+// lep_gpu_pack_window_device is the same pair with a window per run (skip, take: host values): the offsets kernel clips every
+// device-resident length to its window (window_len) -- that is what it sums and what it leaves for the copy kernel --, and the copy
+// starts skip bytes into the run, at whatever alignment that leaves: copy_run's contract, held for the window's bytes.
 #pragma once
 #include <stdint.h>
 
@@ -41,8 +44,17 @@ LEP_PACK_DEV void copy_run(const uint8_t* __restrict__ src, uint8_t* __restrict_
     if (lane < tail) dst[head + nd * 4 + lane] = s[nd * 4 + lane];
 }
 
+// What of a run of len bytes lies in its window: the bytes [skip, min(len, skip + take)), none when the run ends in front of it.
+LEP_PACK_DEV uint32_t window_len(uint32_t len, uint32_t skip, uint32_t take) {
+    if (len <= skip) return 0u;
+    const uint32_t rest = len - skip;
+    return rest < take ? rest : take;
+}
+
 #if defined(__HIPCC__)
-__device__ __forceinline__ void offsets(const uint32_t* __restrict__ len, int n, uint64_t* __restrict__ dst_off) {
+// len_of(i): the length run i contributes (a plain load, or the clipped length of a windowed run)
+template <class LenOf>
+__device__ __forceinline__ void offsets(LenOf len_of, int n, uint64_t* __restrict__ dst_off) {
     __shared__ uint64_t wave_total[kScanLanes / 64];
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int first = t * kPerLane;
@@ -50,7 +62,7 @@ __device__ __forceinline__ void offsets(const uint32_t* __restrict__ len, int n,
     uint64_t sum = 0;
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
-        mine[k] = first + k < n ? len[first + k] : 0u;
+        mine[k] = first + k < n ? len_of(first + k) : 0u;
         sum += mine[k];
     }
     uint64_t incl = sum;   // inclusive scan over the wave's lanes

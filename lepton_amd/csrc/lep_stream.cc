@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "lep_handles.h"
+#include "lep_range.h"
 #include "lep_stream_bands.h"
 #include "lep_stream_session.h"
 
@@ -25,6 +26,26 @@ int lep_file_streams_in_session(const uint8_t* lepdata, size_t len) {
     lep_bytes streams[LEP_MAX_SEGMENTS];
     int n = 0;
     return lep::streams_in_session(f, lepdata, len, &plan, segs, streams, &n) ? 1 : 0;
+}
+
+// Where a byte range of the restored file lies (lep_range.h).  Host only.  A file that is not decoded in a session has no extents.
+int lep_file_range_plan(const uint8_t* lepdata, size_t len, uint64_t first, uint64_t length, lep_range_plan* out) {
+    if (!out) return LEP_ASSERTION_FAILURE;
+    memset(out, 0, sizeof *out);
+    out->first_seg = out->last_seg = -1;
+    lep_file* f = nullptr;
+    if (int rc = lep_file_open(lepdata, len, &f)) return rc;
+    std::unique_ptr<lep_file> hold(f);
+    lep::RecodePlan plan;
+    lep_segment segs[LEP_MAX_SEGMENTS];
+    lep_bytes streams[LEP_MAX_SEGMENTS];
+    int n = 0;
+    const bool in_session = lep::streams_in_session(f, lepdata, len, &plan, segs, streams, &n);
+    if (!in_session) plan.gpu_ok = false;
+    lep::RangeParts parts;
+    const lep::RangeAnswer a = lep::range_plan(&f->lf, plan, first, length, &parts);
+    lep::fill_range_plan(parts, a, in_session, out);
+    return 0;
 }
 
 // lep_decompress with the bytes handed on as they become final (include/lepton_mi355x.h).  The decode is a session

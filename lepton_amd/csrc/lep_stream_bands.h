@@ -109,9 +109,16 @@ inline bool band_segment(const Segment& s, int complete, int image, lep_huff_seg
 // nothing behind the cut can show, the segment is complete whatever rows remain, and its bytes, clipped to the bound, may go out.  (The
 // slot must be the bound's size for that: clipped to anything else the bytes are not the bound's.)  A cut end state in another segment or
 // with the bound not reached, and a refusal (pad & 2, kHuffEndRefused), decline the file.  recode_finish keeps the last word at the end.
+// band_counted is the same rule for a caller that keeps counts and end states only (a range read, lep_range_bands.h: `bytes` holds no
+// byte of the band).
+inline bool band_counted(Segment* s, const lep_huff_segment& launched, uint32_t len, const lep_huff_end& end);
 inline bool band_written(Segment* s, const lep_huff_segment& launched, const uint8_t* data, uint32_t len, const lep_huff_end& end) {
     if (len > launched.out_cap) len = launched.out_cap;
     s->bytes.insert(s->bytes.end(), data, data + len);
+    return band_counted(s, launched, len, end);
+}
+inline bool band_counted(Segment* s, const lep_huff_segment& launched, uint32_t len, const lep_huff_end& end) {
+    if (len > launched.out_cap) len = launched.out_cap;
     s->written += len;
     s->coded = launched.mcu_row1;
     s->overhang = (uint32_t)end.overhang_byte | ((uint32_t)end.num_overhang_bits << 8);
