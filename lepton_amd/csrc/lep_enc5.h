@@ -711,6 +711,25 @@ WDEV void wchunk_stitch_lane(const SegPlan5& P, const SegDev& sd, uint8_t* strea
 //            from the same places and appends the block's bins.  count only adds the units up (LDS atomics: no order needed).
 enum { kCount = 0, kEmit = 1, kGather = 2 };
 
+// A/B switch of the gather pass (scripts/build_variant.sh <name> -DLEP_ENC5_GATHER_ROW_FLUSH=0 builds the form before):
+//   1: a lane stages 64 bins and the lanes write their complete sectors together at check points (Walk5::drain);
+//   0: 32 bins, every lane writes its sector the moment it is full -- inside the bin loops, one lane at a time
+// (Requesting the DC's sign byte behind the tile's scans, a switch of its own, measured nothing -- gather 154.0 ms without it against
+// 154.3 with it, profiles/r22_encoder_gather_row_flush_ab.txt -- and is not in the code.)
+#ifndef LEP_ENC5_GATHER_ROW_FLUSH
+#define LEP_ENC5_GATHER_ROW_FLUSH 1
+#endif
+// gather: what a lane knows about the bins it has staged (see Walk5::put_bin)
+#if LEP_ENC5_GATHER_ROW_FLUSH
+struct BinAcc {
+    uint32_t lw;         // lane | which wavefront's staging block << 16
+    uint32_t fu;         // the lane's first bin that has not been written to the list yet
+    uint32_t blo, bhi;   // the bit values of the last 64 bins, the newest in bit 0 of blo
+};
+#else
+typedef uint32_t BinAcc;
+#endif
+
 // (members in the order the passes need them: a launch takes the front of the block its pass uses -- gather 18 KB (its staging
 // block lies over the cursors the other two passes keep there), count 15 KB, emit all 26 KB -- and the resident workgroups per CU
 // follow from that)
@@ -723,7 +742,8 @@ struct Walk5Shared {
     uint16_t errx[2 * 64];                 // emit: the lanes' first refusal per half of the block (interior; edges and DC)
     uint32_t tcur[2 * 8];                  // emit / gather: threshold units already given out, per colour index / class lt
     union {
-        // ---- gather: per wavefront, the 32 bins (one 64-byte sector of the bin list) every lane is filling: dword d of lane l at [d * 64 + l]
+        // ---- gather: per wavefront, 64 bytes of staged bins per lane, dword d of lane l at [d * 64 + l]: a ring of the probability bytes
+        // of the lane's last 64 bins (LEP_ENC5_GATHER_ROW_FLUSH=0: the 32 half words of the sector the lane is filling)
         uint32_t stg[2][16 * 64];
         struct {
             // ---- count and emit
@@ -898,6 +918,9 @@ struct Walk5 {
     uint32_t* AT;              // emit / gather: the segment's [tile][64][64] array of places
     uint32_t sign_base[2], key_base, nz_base, en_base, dc_base;   // the plan's offsets (read once: a load per tile from the plan would sit on the critical path)
     uint32_t place_base, nzs_base, ens_base[2], dcs_base, plan_nblocks;
+#if !LEP_ON_GPU
+    int ring_over;             // gather, the CPU build only: a bin was put on a staged slot that had not been written yet (run: exit code 1008)
+#endif
 
     WDEV uint32_t* units() const { return reinterpret_cast<uint32_t*>(arena); }
 
@@ -1237,12 +1260,16 @@ struct Walk5 {
         uint8_t* signs = MODE != kCount ? arena + sign_base[ci] + sign_pos[ci] : nullptr;
         uint32_t* U = MODE != kCount ? units() : nullptr;
         LV(uint32_t, bp);   // gather: next bin of this lane
-        LV(uint32_t, bacc); // gather: where this lane stages its bins (see put_bin)
+        LV(BinAcc, bacc);   // gather: where this lane stages its bins (see put_bin)
         LV(int, sp);        // next sign byte of this lane
         LV(int, left);
         LANES(l) {   // a block's bins: [7x7 count: 6][interior] -- the interior half's run -- [edges, DC] -- the other half's
             L(bp) = nbins + (uint32_t)L(bbase) + (kInt || !L(act) ? 0u : 6u + (uint32_t)L(ibins));
+#if LEP_ENC5_GATHER_ROW_FLUSH
+            L(bacc).lw = (uint32_t)l | ((HALF == 2 ? 1u : 0u) << 16); L(bacc).fu = L(bp); L(bacc).blo = 0; L(bacc).bhi = 0;
+#else
             L(bacc) = (uint32_t)l | ((L(bp) & 31u) << 8) | ((HALF == 2 ? 1u : 0u) << 16);
+#endif
             L(sp) = L(sbase) + (kInt ? 0 : L(nz)); L(left) = L(nz);
         }
         // the number of non-zeros of the 7x7 interior (and the key word the sparse chains filter on)
@@ -1420,6 +1447,9 @@ struct Walk5 {
                     L(p_e) = c_e; L(p_te) = c_te; L(p_at) = c_at; L(p_tat) = c_tat; L(p_cf) = L(cfv); L(p_w0) = c_w0; L(p_w1) = c_w1; L(p_tw) = c_tw; L(p_sg) = c_sg;
                 }
             }
+#if LEP_ENC5_GATHER_ROW_FLUSH
+            if (MODE == kGather) drain(bp, bacc);   // a check point: at most 25 bins per lane since the one before (a coefficient's 22, an edge's count)
+#endif
         }
         if (MODE == kGather) {
             LANES(l) {
@@ -1433,6 +1463,9 @@ struct Walk5 {
         }
         // DC
         if (MODE != kCount && kEdge) {
+#if LEP_ENC5_GATHER_ROW_FLUSH
+            if (MODE == kGather) drain(bp, bacc);   // the last coefficient's bins are in; the DC adds at most 22
+#endif
             LANES(l) if (L(act)) {
                 uint32_t* rec = MODE == kEmit ? reinterpret_cast<uint32_t*>(arena + dc_base) + 6 * (ord0 + l)
                                               : reinterpret_cast<uint32_t*>(arena + dcs_base) + 6 * (size_t)L(rdcp);
@@ -1468,9 +1501,78 @@ struct Walk5 {
     // gather: append one bin (probability | bit << 8) of this lane.  A lane's bins are consecutive in the segment's list; stored as
     // they come -- four bytes at a time -- a 64-byte sector took sixteen stores spread over microseconds, and L2 wrote it back half
     // filled again and again (35 write requests per block where 3 sectors are filled: the pass was bound by them).  So a lane
-    // stages the sector it is filling in LDS (32 bins, Walk5Shared::stg) and writes it when it is full -- four 16-byte stores back
-    // to back -- or, where its run starts or ends inside a sector that a neighbour shares, the part that is its own.
-    // `acc`: lane | first own bin of the current sector << 8 | which wavefront's staging block << 16.
+    // stages its bins in LDS and writes them a sector (32 bins, 64 bytes) at a time -- four 16-byte stores back to back -- or, where
+    // its run starts or ends inside a sector that a neighbour shares, the part that is its own.
+    // When a sector leaves is the lanes' common decision, not the lane's own.  Written the moment it was full, a sector cost a
+    // lane-divergent branch in every bin loop: the 64 lanes stand at unrelated places in their sectors, so nearly every pass through a
+    // bin loop had some lane at a boundary, and the wavefront ran the whole flush -- LDS reads, waits, four stores -- for that one lane
+    // (13.6 store instructions per block where the tile's lanes together need 0.2).  Now put_bin is straight-line: the probability
+    // byte goes into the lane's ring of 64 (Walk5Shared::stg, slot = bin & 63), the bit value into a 64-bit shift register, and the
+    // complete sectors are written by drain() at the check points of half() -- once per row and in front of the DC -- where the
+    // lanes that have one go together; the half words are put together from ring and register there.  flush_bin writes what is
+    // left at the end of the run.  The ring holds the bins [fu & ~31, pos): see drain for why that is never more than 64.
+    // (LEP_ENC5_GATHER_ROW_FLUSH=0 -- the form before: `acc` = lane | first own bin of the current sector << 8 | which wavefront's
+    // staging block << 16, 32 half words staged per lane, the sector written by put_bin itself when it is full.)
+#if LEP_ENC5_GATHER_ROW_FLUSH
+    WDEV void put_bin(uint32_t& pos, BinAcc& acc, uint32_t v) {
+        Walk5Shared& S = LEP5_WSH(this);
+#if !LEP_ON_GPU
+        if (pos - acc.fu >= 64u) ring_over = 1;   // the slot still holds a bin that has not been written
+#endif
+        reinterpret_cast<uint8_t*>(S.stg[acc.lw >> 16])[((pos & 60u) << 6) + ((acc.lw & 63u) << 2) + (pos & 3u)] = (uint8_t)v;
+        acc.bhi = (acc.bhi << 1) | (acc.blo >> 31);
+        acc.blo = (acc.blo << 1) | ((v >> 8) & 1u);
+        ++pos;
+    }
+    // dword d (bins 2d, 2d + 1) of a sector: its probability bytes out of the ring (the sector's eight dwords start at dword rb of the
+    // lane's), its bit values out of x -- the sector's 32 bit values, the first bin's in bit 31
+    WDEV uint32_t staged_dword(const uint32_t* ring, uint32_t rb, uint32_t x, uint32_t d) {
+        const uint32_t four = ring[(rb + (d >> 1)) * 64];
+        const uint32_t bb = x >> (30u - 2u * d);   // bit 1: bin 2d, bit 0: bin 2d + 1
+#if LEP_ON_GPU
+        const uint32_t probs = __builtin_amdgcn_perm(0u, four, (d & 1u) ? 0x0c030c02u : 0x0c010c00u);
+#else
+        const uint32_t two = (d & 1u) ? four >> 16 : four;
+        const uint32_t probs = (two & 255u) | ((two & 0xff00u) << 8);
+#endif
+        return probs | ((bb & 2u) << 7) | ((bb & 1u) << 24);
+    }
+    // bins [a, b) of the sector that starts at bin `first` leave the staging block (pos: the lane's next bin; first + a >= acc.fu)
+    WDEV void write_staged(uint32_t first, uint32_t a, uint32_t b, const BinAcc& acc, uint32_t pos) {
+        Walk5Shared& S = LEP5_WSH(this);
+        const uint32_t* ring = S.stg[acc.lw >> 16] + (acc.lw & 63u);
+        const uint32_t rb = (first & 32u) >> 2;
+        const int t = (int)(first + 32u - pos);   // the sector's last bin is t bins ahead of the newest (t <= 0: -t bins behind it)
+        const uint32_t x = t > 0 ? acc.blo << (t & 31) : (uint32_t)(((((uint64_t)acc.bhi) << 32) | acc.blo) >> (uint32_t)(-t));
+        uint32_t* dst = reinterpret_cast<uint32_t*>(bins + first);
+        if (a == 0u && b == 32u) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                gst4(dst + 4 * q, staged_dword(ring, rb, x, 4 * q), staged_dword(ring, rb, x, 4 * q + 1), staged_dword(ring, rb, x, 4 * q + 2), staged_dword(ring, rb, x, 4 * q + 3));
+            return;
+        }
+        if (a & 1u) gst(bins + first + a, (uint16_t)(staged_dword(ring, rb, x, a >> 1) >> 16));
+        for (uint32_t d = (a + 1u) >> 1; d < (b >> 1); ++d) gst(dst + d, staged_dword(ring, rb, x, d));
+        if ((b & 1u) && b > a) gst(bins + first + b - 1u, (uint16_t)staged_dword(ring, rb, x, b >> 1));
+    }
+    // A check point (between LANES regions; bp / bacc: the lanes' variables).  With c = pos - (fu & ~31), the bins the ring holds, a lane
+    // is URGENT at c >= 40.  Nobody urgent: the pass is this compare and a ballot.  Otherwise every lane that has a complete sector
+    // (c >= 32) writes it in the same pass, a lane that has two writes both -- so the stores of a pass come from as many lanes as have
+    // anything to write, not from the one that happened to fill up.  Behind a check point every lane has c <= 39; up to the next one it
+    // puts at most 25 bins (half()), so c <= 64 always and put_bin never lands on a slot that has not been written (the CPU build checks).
+    WDEV void drain(const uint32_t* bp, BinAcc* bacc) {
+        LV(int, due);
+        LANES(l) L(due) = L(bp) - (L(bacc).fu & ~31u) >= 40u;
+        if (!lepwave::wave_ballot(due)) return;
+        do {
+            LANES(l) {
+                const uint32_t first = L(bacc).fu & ~31u;
+                if (L(bp) - first >= 32u) { write_staged(first, L(bacc).fu & 31u, 32u, L(bacc), L(bp)); L(bacc).fu = first + 32u; }
+                L(due) = L(bp) - L(bacc).fu >= 32u;   // (fu is a sector's start now, or the lane had nothing to write)
+            }
+        } while (lepwave::wave_ballot(due));
+    }
+#else
     WDEV void put_bin(uint32_t& pos, uint32_t& acc, uint32_t v) {
         Walk5Shared& S = LEP5_WSH(this);
         const uint32_t k = pos & 31u, l = acc & 63u;
@@ -1492,8 +1594,9 @@ struct Walk5 {
         for (uint32_t d = (a + 1u) >> 1; d < (b >> 1); ++d) gst(dst + d, src[d * 64]);
         if ((b & 1u) && b > a) gst(bins + first + b - 1u, (uint16_t)src[(b >> 1) * 64]);
     }
+#endif
     // the bins of one coefficient in stream order: exponent, sign, threshold bits, the residual bits below the threshold
-    WDEV void gather_coef(uint32_t& pos, uint32_t& acc, const uint32_t* U, uint32_t e, uint32_t t_e, uint32_t at, uint32_t tat, int cf, uint32_t w0,
+    WDEV void gather_coef(uint32_t& pos, BinAcc& acc, const uint32_t* U, uint32_t e, uint32_t t_e, uint32_t at, uint32_t tat, int cf, uint32_t w0,
                           uint32_t w1, uint32_t tw, uint32_t sg) {
         const int len = (int)(e >> 14) & 15, nres = (int)(e >> 10) & 15, nexp = len < 11 ? len + 1 : 11, m = nexp + nres;
         const int tn = t_e ? (int)(t_e >> 10) & 15 : 0;
@@ -1512,11 +1615,21 @@ struct Walk5 {
             put_bin(pos, acc, ((w >> (8 * (q & 3))) & 255u) | (((e >> (nres - 1 - (q - nexp))) & 1u) << 8));
         }
     }
-    // the lane's run ends here: what it has staged of the sector it stands in
+    // the lane's run ends here: what it has staged and not written -- with the ring of 64, up to two sectors, the last one in part
+#if LEP_ENC5_GATHER_ROW_FLUSH
+    WDEV void flush_bin(uint32_t pos, BinAcc& acc) {
+        while (acc.fu < pos) {
+            const uint32_t first = acc.fu & ~31u, b = pos - first < 32u ? pos - first : 32u;
+            write_staged(first, acc.fu & 31u, b, acc, pos);
+            acc.fu = first + b;
+        }
+    }
+#else
     WDEV void flush_bin(uint32_t pos, uint32_t acc) {
         const uint32_t k = pos & 31u, a = (acc >> 8) & 63u;
         if (k > a) write_staged(pos - k, a, k, acc);
     }
+#endif
 
     // whole segment (lepton_codec.hh:41-100 row schedule, vp8_encoder.cc:239-445); ns: the segment's two-row NSum rings (zeroed)
     // emit: the state at the first tile of every part (the wavefront that holds the exact bin count writes it)
@@ -1535,6 +1648,9 @@ struct Walk5 {
     WDEV int run(const ImageDev* image, const SegDev& seg, NSum* ns, Walk5Shared* shared, const SegPlan5* pl, uint8_t* arena_base, uint16_t* bins_base,
                  int wave_no = 0, int part = 0, int nparts = 1) {
         img = image; sh = shared; plan = pl; status = 0; wave = wave_no;
+#if !LEP_ON_GPU
+        ring_over = 0;
+#endif
         arena = (MODE != kCount) ? arena_base + pl->arena_off : nullptr;
         bins = (MODE == kGather) ? bins_base + pl->bins_off : nullptr;
         ord0 = 0; sign_pos[0] = sign_pos[1] = 0; nbins = 0; tile_no = 0;
@@ -1570,6 +1686,9 @@ struct Walk5 {
             if (more) fetch_tile(nxt_t, regs);   // in flight while this tile is worked on
             const int rc = tile(cur_t.x0, cur_t.nb, cur_t.has_above, cur_t.nrow, cur_t.narow);
             if (rc) return rc;
+#if !LEP_ON_GPU
+            if (MODE == kGather && ring_over) return 1008;   // (the staging ring's invariant, see drain: the GPU build carries no check)
+#endif
             if (MODE == kEmit) { LEP5_XSYNC(); checkpoints(ntiles, nparts); }
             cur_t = nxt_t;
             have = more;
