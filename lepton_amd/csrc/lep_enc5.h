@@ -569,6 +569,9 @@ WDEV void write_wave(const SegPlan5* plans, const uint16_t* bins, const SegDev* 
 //   stitch  lane = segment: adds every chunk's kept bits into the bytes behind it and the carries in front, ripples, applies the
 //           stream's end rule (boolwriter.cc:17-35).
 // The wavefront scan north_star names is here a scan over chunks: range states and bit offsets first, carries last.
+// Where the chunks are cut is a ChunkCut5: K equal stretches of the whole list (chunk_cut: the writer behind gather), or c equal
+// stretches of every part of gather (part_chunk_cut: a part's range / link / code run while the next part is gathered, link going on
+// from the part before; one stitch over all parts x c chunks at the end).  stitch asks for the records alone, not for the cuts.
 constexpr uint32_t kWarm5 = 16384;
 struct WChunk5 { uint32_t q_guess, q_end, shifts, q_start, t_start, keep, keep_bits, carry, pos_end, pad[7]; };   // 64 bytes
 static_assert(sizeof(WChunk5) == 64, "one record per (segment, chunk)");
@@ -621,53 +624,76 @@ WDEV void range_run(const uint16_t* list, uint32_t b0, uint32_t b1, bool first, 
     if (last) for (int i = 0; i < 32; ++i) t += (uint32_t)range_step(q, 0, 128);
     shifts = t; q24 = q;
 }
-WDEV void wchunk_range_lane(const SegPlan5& P, const uint16_t* bins, WChunk5* rec, int k, int K, uint32_t warm = kWarm5) {
+// what a chunk covers: bins [b0, b1) of the list; the start marker goes in front of the stream's first chunk, the 32 stop bins behind its last
+struct ChunkCut5 { uint32_t b0, b1; bool first, last; };
+WDEV ChunkCut5 chunk_cut(uint32_t nbins, int k, int K) { return ChunkCut5{chunk_first_bin(nbins, k, K), chunk_first_bin(nbins, k + 1, K), k == 0, k + 1 == K}; }
+// ... with the chunks cut at the boundaries of gather's PARTS: chunk p * c + s is the s-th of c equal stretches of part p's bins
+// [B(p), B(p + 1)), B from emit's checkpoints as write_wave reads them (B(0) = 0, B(nparts) = P.nbins -- which gather's last part
+// writes, so part p's cut asks for nothing that gather has not left by the time part p is gathered).  A part's chunks can therefore
+// be ranged, linked and coded while the next part is gathered; a part of fewer than c bins has empty chunks.
+WDEV ChunkCut5 part_chunk_cut(const SegPlan5& P, const Ckpt5* ck, int p, int s, int nparts, int c) {
+    const uint32_t B0 = p > 0 ? ck[p].nbins : 0u, B1 = p + 1 < nparts ? ck[p + 1].nbins : P.nbins, d = B1 - B0;
+    return ChunkCut5{B0 + chunk_first_bin(d, s, c), B0 + chunk_first_bin(d, s + 1, c), p == 0 && s == 0, p + 1 == nparts && s + 1 == c};
+}
+WDEV void wchunk_range_cut(const SegPlan5& P, const uint16_t* bins, WChunk5* rec, const ChunkCut5& c, uint32_t warm = kWarm5) {
     if (P.status) return;
     const uint16_t* list = bins + P.bins_off;
-    const uint32_t b0 = chunk_first_bin(P.nbins, k, K), b1 = chunk_first_bin(P.nbins, k + 1, K);
     uint32_t q24 = 254u << 24, sh = 0;
-    if (k > 0) {   // warm up: from kWarm5 bins before the chunk (or from the stream's true start, marker included, if that is nearer)
-        const bool from_start = b0 <= warm;
-        range_run(list, from_start ? 0u : b0 - warm, b0, from_start, false, q24, sh);
+    if (!c.first) {   // warm up: from `warm` bins before the chunk (or from the stream's true start, marker included, if that is nearer)
+        const bool from_start = c.b0 <= warm;
+        range_run(list, from_start ? 0u : c.b0 - warm, c.b0, from_start, false, q24, sh);
     }
     rec->q_guess = q24;
-    range_run(list, b0, b1, k == 0, k + 1 == K, q24, sh);
+    range_run(list, c.b0, c.b1, c.first, c.last, q24, sh);
     rec->q_end = q24; rec->shifts = sh;
+}
+WDEV void wchunk_range_lane(const SegPlan5& P, const uint16_t* bins, WChunk5* rec, int k, int K, uint32_t warm = kWarm5) {
+    wchunk_range_cut(P, bins, rec, chunk_cut(P.nbins, k, K), warm);
 }
 // bytes the serial writer has handed out after a total shift of T, and its `count` then (BoolEnc5::flush: count starts at -24)
 WDEV uint32_t bytes_at(uint32_t T) { return T >= 24 ? ((T - 24) >> 3) + 1 : 0u; }
 WDEV int count_at(uint32_t T) { return (int)T - 24 - 8 * (int)bytes_at(T); }
-WDEV void wchunk_link_lane(const SegPlan5& P, const uint16_t* bins, WChunk5* recs, int K) {
+// chunks [j0, j1) of a segment (recs: the segment's records, cut(j): chunk j's cut): (range, T) go on from where chunk j0 - 1 was
+// linked to -- the chunks in front of j0 have been linked by then
+template <class CUT>
+WDEV void wchunk_link_cuts(const SegPlan5& P, const uint16_t* bins, WChunk5* recs, int j0, int j1, CUT&& cut) {
     if (P.status) return;
     const uint16_t* list = bins + P.bins_off;
     uint32_t T = 0, q = 254u << 24;
-    for (int k = 0; k < K; ++k) {
-        WChunk5& r = recs[k];
-        if (k > 0 && r.q_guess != q) {   // the warm-up had not fallen into step: this chunk's range run again, from the range it really starts with
+    if (j0 > 0) { q = recs[j0 - 1].q_end; T = recs[j0 - 1].t_start + recs[j0 - 1].shifts; }
+    for (int j = j0; j < j1; ++j) {
+        WChunk5& r = recs[j];
+        if (j > 0 && r.q_guess != q) {   // the warm-up had not fallen into step: this chunk's range run again, from the range it really starts with
+            const ChunkCut5 c = cut(j);
             uint32_t q24 = q, sh = 0;
-            range_run(list, chunk_first_bin(P.nbins, k, K), chunk_first_bin(P.nbins, k + 1, K), false, k + 1 == K, q24, sh);
+            range_run(list, c.b0, c.b1, false, c.last, q24, sh);
             r.q_end = q24; r.shifts = sh;
         }
         r.q_start = q; r.t_start = T;
         q = r.q_end; T += r.shifts;
     }
 }
-WDEV void wchunk_code_lane(const SegPlan5& P, const uint16_t* bins, const SegDev& sd, uint8_t* streams, WChunk5* rec, int k, int K) {
+WDEV void wchunk_link_lane(const SegPlan5& P, const uint16_t* bins, WChunk5* recs, int K) {
+    wchunk_link_cuts(P, bins, recs, 0, K, [&](int k) { return chunk_cut(P.nbins, k, K); });
+}
+WDEV void wchunk_code_cut(const SegPlan5& P, const uint16_t* bins, const SegDev& sd, uint8_t* streams, WChunk5* rec, const ChunkCut5& c) {
     if (P.status) return;
     const uint16_t* list = bins + P.bins_off;
-    const uint32_t b0 = chunk_first_bin(P.nbins, k, K), b1 = chunk_first_bin(P.nbins, k + 1, K);
     BoolEnc5 bc;
     bc.init(streams + sd.stream_off, sd.stream_cap);
     bc.q24 = rec->q_start;
     bc.pos = bytes_at(rec->t_start); bc.count = count_at(rec->t_start); bc.floor_ = bc.pos;
-    if (k == 0) { bc.bin(0, 128); bc.flush(); }
-    for_bins(list, b0, b1, [&](uint32_t bit, uint32_t prob) { bc.bin(bit, prob); }, [&]() { bc.flush(); });
+    if (c.first) { bc.bin(0, 128); bc.flush(); }
+    for_bins(list, c.b0, c.b1, [&](uint32_t bit, uint32_t prob) { bc.bin(bit, prob); }, [&]() { bc.flush(); });
     bc.flush();
-    if (k + 1 == K) for (int i = 0; i < 32; ++i) { bc.bin(0, 128); if ((i & 3) == 3) bc.flush(); }
+    if (c.last) for (int i = 0; i < 32; ++i) { bc.bin(0, 128); if ((i & 3) == 3) bc.flush(); }
     bc.flush();
     for (; bc.nst; --bc.nst) { if (bc.pos < bc.cap) bc.out[bc.pos] = (uint8_t)(bc.stage >> (8 * (bc.nst - 1))); ++bc.pos; }
     // what the recurrence still holds: the 32 + count bits behind the last byte handed out (count is -8 .. -1 after a flush)
     rec->keep = (uint32_t)bc.low; rec->keep_bits = (uint32_t)(32 + bc.count); rec->carry = bc.carry_out; rec->pos_end = bc.pos;
+}
+WDEV void wchunk_code_lane(const SegPlan5& P, const uint16_t* bins, const SegDev& sd, uint8_t* streams, WChunk5* rec, int k, int K) {
+    wchunk_code_cut(P, bins, sd, streams, rec, chunk_cut(P.nbins, k, K));
 }
 // adds `v` (a carry) at byte x - 1 and below
 WDEV void add_back(uint8_t* out, uint32_t cap, uint32_t x, uint32_t v) {

@@ -234,6 +234,28 @@ __global__ __launch_bounds__(64) void lep_enc5_wchunk_kernel(const lep5::SegPlan
         else lep5::wchunk_stitch_lane(plans[id], segs[id], streams, stream_len, status, recs + (size_t)id * K, K);
     }
 }
+// ... with the chunks cut at the boundaries of gather's parts (lep5::part_chunk_cut): the three phases of ONE part's c chunks, launched
+// when that part is gathered and run beside the gather of the next -- PHASE 0 range and 2 code (lane = one of the part's chunks),
+// 1 link (lane = segment; goes on from the part before).  Stitch is the kernel above over all nparts * c chunks.
+template <int PHASE>
+__global__ __launch_bounds__(64) void lep_enc5_wchunk_part_kernel(const lep5::SegPlan5* __restrict__ plans, const uint16_t* __restrict__ bins, const SegDev* __restrict__ segs,
+                                                              int nseg, int nparts, int c, int part, lep5::WChunk5* recs, uint8_t* streams, const uint8_t* __restrict__ arena,
+                                                              int32_t* status, uint32_t* nbins_out) {
+    __builtin_amdgcn_s_setprio(3);   // (beside the next part's gather, like the lane-per-segment writer)
+    const int id = (int)(blockIdx.x * 64 + threadIdx.x);
+    const int seg = PHASE == 1 ? id : id / c, s = PHASE == 1 ? 0 : id - seg * c;
+    if (seg >= nseg) return;
+    const lep5::SegPlan5& P = plans[seg];
+    const lep5::Ckpt5* ck = reinterpret_cast<const lep5::Ckpt5*>(arena + P.arena_off + P.ckpt_base);
+    lep5::WChunk5* r = recs + (size_t)seg * (size_t)(nparts * c);
+    if (PHASE == 0) lep5::wchunk_range_cut(P, bins, r + part * c + s, lep5::part_chunk_cut(P, ck, part, s, nparts, c));
+    else if (PHASE == 2) lep5::wchunk_code_cut(P, bins, segs[seg], streams, r + part * c + s, lep5::part_chunk_cut(P, ck, part, s, nparts, c));
+    else {
+        if (part == 0) status[segs[seg].slot] = 0;
+        if (part + 1 == nparts) nbins_out[segs[seg].slot] = P.nbins;
+        lep5::wchunk_link_cuts(P, bins, r, part * c, (part + 1) * c, [&](int j) { return lep5::part_chunk_cut(P, ck, j / c, j % c, nparts, c); });
+    }
+}
 // counts -> per-segment layout (one thread per segment), then the prefix over the segments (one wavefront)
 __global__ void lep_enc5_plan_kernel(const uint32_t* __restrict__ counts, lep5::SegPlan5* plans, int nseg) {
     const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -575,9 +597,16 @@ struct lep_gpu {
                              // (MI355X, 1024 x 4K: 1 part 569 ms per launch, 4 parts 481, 8 parts 475)
     hipEvent_t ev_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     long enc5_wlanes = 131072;  // LEP_ENC5_WLANES: chunk lanes a launch of the stitched writer may have (segments x chunks per segment)
-    int enc5_wmaxseg = 4096;    // LEP_ENC5_WMAXSEG: launches of more segments keep the lane-per-segment writer beside gather
+    int enc5_wmaxseg = 4096;    // LEP_ENC5_WMAXSEG: launches of more segments take the writer enc5_wsched names (up to it: stitched behind gather)
     int enc5_wchunks = 64;   // LEP_ENC5_WCHUNKS: the stitched writer for launches that leave lanes free: up to this many chunks per segment (power of
                              // two; 0 = always the lane-per-segment writer beside gather)
+    bool enc5_parts_given = false;   // LEP_ENC5_PARTS was set: it holds for every launch (else: one part where the writer runs behind gather)
+    int enc5_wsched = 1;     // LEP_ENC5_WSCHED: the writer of launches of more than enc5_wmaxseg segments (LEP_ENC5_WMAXSEG=0: of every launch) --
+                             // 0 | lane: lane per segment beside gather; 1 | after: stitched behind the last gather part, chunks as below
+                             // that size; 2 | beside: stitched, every part's chunks ranged / linked / coded beside the next part's gather
+                             // (MI355X, 1024 x 4K, profiles/r23_*: lane 434 ms per launch; after 423, with gather in one part 403;
+                             // beside 420 at 8 parts x 4 chunks, 402 at 2 parts x 8 -- gather loses more to parts and to company than the writer's tail costs)
+    int enc5_wpartchunks = 4;   // LEP_ENC5_WPARTCHUNKS: chunks per part and segment of the `beside` schedule (a power of two, 1 .. 32)
     int enc5_gather_wgs = 0; // LEP_ENC5_GATHER_WGS: resident gather workgroups per CU held to this (through the LDS a launch asks for)
     int enc5_fold_apart = 0; // LEP_ENC5_FOLD_APART: the fold launches one after the other, a launch per kind of chain (for the profiler)
     size_t enc5_scratch_max = ~(size_t)0;   // LEP_ENC5_SCRATCH_MAX (bytes): a launch that needs more takes the single-kernel encoder (tests: the out-of-memory path)
@@ -829,8 +858,16 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     g->nstage = 0;
     HIPCHK(g, hipEventRecord(g->ev_stage[0], st));
     const bool two = g->enc5_waves == 2;
-    const int nparts = std::min(std::max(g->enc5_parts, 1), (int)lep5::kMaxParts);
-    auto walk = [&](int mode, uint8_t* entries, uint16_t* binlist, int part = 0) {
+    // The writer's schedule.  A launch that leaves the chip's lanes free takes the stitched writer behind gather: K chunks per segment (a
+    // power of two up to 64), as many as keep the launch under enc5_wlanes chunk lanes.  Round 4 capped the lanes at 4096 (K = 2 at 256
+    // images: two chains of 1.15 M bins per segment, 118 ms of writer on 64 wavefronts); round 6 measured the cap away (profiles/r6o_*:
+    // 256 images 253 -> 148 ms per launch with K = 32, 128 images 159 -> 107, 512 images -- which had kept the lane-per-segment writer
+    // -- 308 -> 260).  From 4097 segments on enc5_wsched says which (profiles/r23_*).
+    const int wsched = nseg <= g->enc5_wmaxseg ? 1 : g->enc5_wsched;
+    int K = 0;
+    if (g->enc5_wchunks >= 2 && wsched == 1) { K = 1; while (K * 2 <= g->enc5_wchunks && (long)nseg * K * 2 <= g->enc5_wlanes) K *= 2; }
+    int nparts = std::min(std::max(g->enc5_parts, 1), (int)lep5::kMaxParts);   // (emit and gather: settled below, once the records are there)
+    auto walk =[&](int mode, uint8_t* entries, uint16_t* binlist, int part = 0) {
         size_t lds = lep5::walk_lds_bytes(mode);
         if (mode == lep5::kGather && g->enc5_gather_wgs > 0) lds = std::max(lds, (size_t)(160 * 1024 / g->enc5_gather_wgs) & ~(size_t)255);   // (measurement aid: fewer resident workgroups)
 #define LEP_WALK(MODE, NW) hipLaunchKernelGGL((lep_enc5_walk_kernel<MODE, NW>), dim3(nseg), dim3(64 * NW), lds, st, d_img, d_seg, (NSum*)ns.p, d_nsoff, plans, entries, binlist, counts, part, nparts)
@@ -855,6 +892,18 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         if (!told) { told = true; fprintf(stderr, "lepton-mi355x: no room for the split-phase encoder's scratch (%.1f GB for %d segments): single-kernel encoder\n", ((double)tot[0] + 2.0 * (double)tot[1]) / 1e9, nseg); }
         return kEnc5NoMemory;
     }
+    if (K >= 2 && ensure(g, wchunks, (size_t)nseg * K * sizeof(lep5::WChunk5) + 256, false)) { (void)hipGetLastError(); g->err.clear(); K = 0; }
+    // Parts exist for a writer that runs beside gather.  Behind gather there is nothing to hide, and gather in parts is the slower one
+    // (1024 x 4K, nothing beside it: 8 parts 133 ms, one part 115 -- every part steps through the segment's tiles to its first and ends on
+    // its slowest segment; 512 images 231 against 220 ms per launch, 256 images 142 against 137): a launch that writes behind gather
+    // gathers in ONE part unless LEP_ENC5_PARTS names a number.
+    if (K >= 2 && !g->enc5_parts_given) nparts = 1;
+    // `beside`: c chunks per part, cut at the parts' boundaries -- part p's range / link / code go out on the second stream when part p
+    // is gathered and run beside the gather of part p + 1; behind the last part only that part's phases and the stitch are left
+    const int c = wsched == 2 ? g->enc5_wpartchunks : 0;
+    const bool beside = c >= 1 && !ensure(g, wchunks, (size_t)nseg * nparts * c * sizeof(lep5::WChunk5) + 256, false);
+    if (c >= 1 && !beside) { (void)hipGetLastError(); g->err.clear(); }   // (no room for the records: the lane-per-segment writer)
+    const bool wrote_beside = beside;
     // (Segment groups on streams of their own -- one group's writer and folds beside the next group's walks -- were measured
     // and dropped: MI355X, 1024 x 4K, profiles/r04l_*: 1 group 784 ms, 2: 875, 4: 1232; launches this large do not share the chip.)
     {
@@ -883,15 +932,26 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0));
         HIPCHK(g, hipStreamWaitEvent(st, g->ev_join3, 0));
         HIPCHK(g, hipEventRecord(g->ev_stage[3], st));
-        // A launch that leaves the chip's lanes free takes the stitched writer: K chunks per segment (a power of two up to 64), as many as
-        // keep the launch under enc5_wlanes chunk lanes.  Round 4 capped the lanes at 4096 (K = 2 at 256 images: two chains of 1.15 M bins
-        // per segment, 118 ms of writer on 64 wavefronts); round 6 measured the cap away (profiles/r6o_*: 256 images 253 -> 148 ms per
-        // launch with K = 32, 128 images 159 -> 107, 512 images -- which had kept the lane-per-segment writer -- 308 -> 260).  From 4097
-        // segments on the lane-per-segment writer beside gather stays: there the walks fill the chip and hide it.
-        int K = 0;
-        if (g->enc5_wchunks >= 2 && nseg <= g->enc5_wmaxseg) { K = 1; while (K * 2 <= g->enc5_wchunks && (long)nseg * K * 2 <= g->enc5_wlanes) K *= 2; }
-        if (K >= 2 && ensure(g, wchunks, (size_t)nseg * K * sizeof(lep5::WChunk5) + 256, false)) { (void)hipGetLastError(); g->err.clear(); K = 0; }
-        if (K >= 2) {
+        if (beside) {
+            lep5::WChunk5* recs = (lep5::WChunk5*)wchunks.p;
+            const int lane_groups = (int)(((long)nseg * c + 63) / 64);
+#define LEP_WPART(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_part_kernel<PHASE>), dim3(GRID), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, \
+                                                  nparts, c, part, recs, d_streams, (const uint8_t*)ws_entries.p, d_status, g->d_bins)
+            for (int part = 0; part < nparts; ++part) {
+                walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
+                HIPCHK(g, hipEventRecord(g->ev_part[part], st));
+                HIPCHK(g, hipStreamWaitEvent(g->stream2, g->ev_part[part], 0));
+                LEP_WPART(0, lane_groups); LEP_WPART(1, groups); LEP_WPART(2, lane_groups);
+            }
+#undef LEP_WPART
+            HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
+            hipLaunchKernelGGL((lep_enc5_wchunk_kernel<3>), dim3(groups), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, nparts * c, recs,
+                               d_streams, d_stream_len, d_status, g->d_bins);
+            HIPCHK(g, hipEventRecord(g->ev_join, g->stream2));
+            HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0));
+            HIPCHK(g, hipEventRecord(g->ev_stage[5], st));
+            g->nstage = 5;
+        } else if (K >= 2) {
             for (int part = 0; part < nparts; ++part) walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
             HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
             lep5::WChunk5* recs = (lep5::WChunk5*)wchunks.p;
@@ -920,7 +980,7 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     }
     HIPCHK(g, hipEventRecord(g->ev_enc5_done, st));
     HIPCHK(g, hipGetLastError());
-    g->last_kernel = "lep_enc5 (count | emit | fold | gather | write)";
+    g->last_kernel = wrote_beside ? "lep_enc5 (count | emit | fold | gather | write: part chunks beside gather)" : "lep_enc5 (count | emit | fold | gather | write)";
     return 0;
 }
 
@@ -1159,10 +1219,12 @@ int lep_gpu_create(int device, lep_gpu** out) {
     if (const char* e = getenv("LEP_ENC5_WAVES")) g->enc5_waves = atoi(e) == 1 ? 1 : 2;
     if (const char* e = getenv("LEP_ENC5_FOLD_APART")) g->enc5_fold_apart = atoi(e);
     if (const char* e = getenv("LEP_ENC5_GATHER_WGS")) g->enc5_gather_wgs = atoi(e);
-    if (const char* e = getenv("LEP_ENC5_PARTS")) g->enc5_parts = atoi(e);
+    if (const char* e = getenv("LEP_ENC5_PARTS")) { g->enc5_parts = atoi(e); g->enc5_parts_given = true; }
     if (const char* e = getenv("LEP_ENC5_WCHUNKS")) g->enc5_wchunks = atoi(e);
     if (const char* e = getenv("LEP_ENC5_WLANES")) g->enc5_wlanes = atol(e);
     if (const char* e = getenv("LEP_ENC5_WMAXSEG")) g->enc5_wmaxseg = atoi(e);
+    if (const char* e = getenv("LEP_ENC5_WSCHED")) g->enc5_wsched = !strcmp(e, "lane") ? 0 : !strcmp(e, "after") ? 1 : !strcmp(e, "beside") ? 2 : std::min(std::max(atoi(e), 0), 2);
+    if (const char* e = getenv("LEP_ENC5_WPARTCHUNKS")) { const int c = atoi(e); g->enc5_wpartchunks = 1; while (g->enc5_wpartchunks * 2 <= std::min(c, 32)) g->enc5_wpartchunks *= 2; }
     if (const char* e = getenv("LEP_ENC5_SCRATCH_MAX")) g->enc5_scratch_max = (size_t)strtoull(e, nullptr, 10);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= device) { delete g; return LEP_GPU_ERROR; }
