@@ -150,6 +150,28 @@ double lep_gpu_last_kernel_ms(lep_gpu *g);          /* HIP-event duration of the
  * launch was a single-kernel one). */
 int lep_gpu_last_stage_ms(lep_gpu *g, double *ms, int cap);
 const char *lep_gpu_last_kernel_name(lep_gpu *g);   /* which kernel generation / register-budget variant that launch used */
+/* Tests: the split-phase encoder's bool writer kernels on bin lists the caller gives -- one list per segment, `bins` holds them back to
+ * back (entries probability | bit << 8), nbins[s] their lengths -- launched in the encoder's order in one of its three forms:
+ *   LEP_DEBUG_WRITE_LANE         the lane-per-segment writer in `parts` parts (1..8; chunks is not read)
+ *   LEP_DEBUG_WRITE_STITCHED     range / link / code / stitch over `chunks` chunks per segment (1..256; parts = 1)
+ *   LEP_DEBUG_WRITE_PART_CHUNKS  range / link / code of `chunks` (1..32) chunks per part, part by part, then one stitch
+ * For the forms in parts with parts > 1, part_first[s * parts + p] is the first bin of segment s's part p: 0 for p = 0, ascending, at
+ * most nbins[s]; equal neighbours are empty parts.  A part's bins reach the device when the part's kernels are queued.
+ * Segment s writes into [stream_off[s], stream_off[s] + stream_cap[s]) of an output arena of arena_bytes that the call fills with the
+ * byte `guard` first; the reservations ascend and may leave gaps.  plan_status (may be NULL): a non-zero entry is a segment the walks
+ * refused -- the writer passes the code on and codes nothing.  The whole arena comes back in arena_out, with stream_len[nseg] and
+ * status[nseg] (both start as 0x7f7f7f7f) and, for the chunked forms, the writer's records in wchunks (may be NULL): per segment
+ * parts * chunks records of 16 uint32 -- q_guess, q_end, shifts, q_start, t_start, keep, keep_bits, carry, pos_end, 7 unused.
+ * Uses memory of its own and the object's stream; waits for the result.  LEP_ASSERTION_FAILURE: arguments out of range, or a decode
+ * session owns the current workspace set. */
+enum { LEP_DEBUG_WRITE_LANE = 0, LEP_DEBUG_WRITE_STITCHED = 1, LEP_DEBUG_WRITE_PART_CHUNKS = 2 };
+int lep_gpu_debug_write_bins(lep_gpu *g, int form, int parts, int chunks, int nseg, const uint16_t *bins, const uint32_t *nbins,
+                             const uint64_t *stream_off, const uint32_t *stream_cap, const int32_t *plan_status, const uint32_t *part_first,
+                             int guard, uint8_t *arena_out, size_t arena_bytes, uint32_t *stream_len, int32_t *status, void *wchunks);
+/* Tests: the stitched writer's records of the most recent encode launch, in the caller's segment order, parts * chunks per segment
+ * in the layout above; *nseg, *parts and *chunks (each may be NULL) say how that launch cut its segments -- parts = 1 for the writer
+ * behind gather.  Returns parts * chunks, 0 when that launch used another writer; the records are copied when cap_records holds them all. */
+int lep_gpu_debug_wchunks(lep_gpu *g, void *out, size_t cap_records, int *nseg, int *parts, int *chunks);
 /* JPEG Huffman re-encode of decoded coefficient frames on the GPU (replaces recode_one_mcu_row / encode_block_seq,
  * src/lepton/recoder.cc:316-412, 245-314, for whole, untruncated sequential scans): one wavefront per thread segment writes
  * that segment's scan bytes (FF00-stuffed, RST markers included) to d_out + segs[i].out_off, at most segs[i].out_cap of

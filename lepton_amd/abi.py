@@ -249,6 +249,9 @@ def lib():
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.restype = C.c_double
         L.lep_gpu_last_stage_ms.argtypes = [vp, P(C.c_double), C.c_int]
+        if hasattr(L, "lep_gpu_debug_write_bins"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_gpu_debug_write_bins.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
+            L.lep_gpu_debug_wchunks.argtypes = [vp, vp, C.c_size_t, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.lep_gpu_last_kernel_name.argtypes = [vp]
         L.lep_gpu_last_kernel_name.restype = C.c_char_p
         L.lep_gpu_selftest.argtypes = [vp]
@@ -337,4 +340,5 @@ EXPORTS = [
     "lep_file_streams_in_session",
     "lep_gpu_decode_rows_retire", "lep_gpu_pack_window_device", "lep_file_range_plan", "lep_file_recode_segment_end", "lep_file_recode_tail",
     "lep_decompress_batch_ranges", "lep_decompress_range",
+    "lep_gpu_debug_write_bins", "lep_gpu_debug_wchunks",
 ]

@@ -419,6 +419,44 @@ class GpuCodec:
         lane-per-subsequence scan decoder had answered with a status (process-wide, not per codec object)"""
         return int(self._L.lep_batch_scan_second_chances())
 
+    def debug_write_bins(self, form, parts, chunks, lists, offsets, caps, arena_bytes, guard=0xA5, plan_status=None, part_first=None):
+        """lep_gpu_debug_write_bins (tests): the bool writer kernels on `lists` (uint16 arrays, probability | bit << 8), list s into
+        [offsets[s], offsets[s] + caps[s]) of an arena of arena_bytes filled with `guard`; part_first: per list the first bins of its
+        `parts` parts.  -> (arena, stream_len, status, records): numpy arrays, the records (lists, parts * chunks, 16) uint32 -- None for
+        the lane-per-segment form"""
+        import numpy as np
+
+        n = len(lists)
+        bins = np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.uint16) for b in lists] + [np.zeros(1, dtype=np.uint16)]))
+        nbins = np.array([len(b) for b in lists], dtype=np.uint32)
+        off, cap = np.array(offsets, dtype=np.uint64), np.array(caps, dtype=np.uint32)
+        ps = None if plan_status is None else np.array(plan_status, dtype=np.int32)
+        pf = None if part_first is None else np.ascontiguousarray(np.array(part_first, dtype=np.uint32).reshape(n, parts))
+        K = 0 if form == 0 else (chunks if form == 1 else parts * chunks)
+        arena = np.zeros(max(arena_bytes, 1), dtype=np.uint8)
+        lens, status = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32)
+        recs = np.zeros((n, K, 16), dtype=np.uint32) if K else None
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        rc = self._L.lep_gpu_debug_write_bins(self.handle, form, parts, chunks, n, p(bins), p(nbins), p(off), p(cap), p(ps), p(pf), guard, p(arena), arena_bytes,
+                                              p(lens), p(status), p(recs))
+        if rc:
+            raise LeptonError(rc, "lep_gpu_debug_write_bins [%s]" % self.last_error())
+        return arena[:arena_bytes], lens, status, recs
+
+    def debug_wchunks(self):
+        """lep_gpu_debug_wchunks (tests): (parts, chunks, records) of the most recent encode launch -- records a numpy array (segments,
+        parts * chunks, 16) uint32 in the caller's segment order; (0, 0, None) when that launch did not use the stitched writer"""
+        import numpy as np
+
+        nseg, parts, chunks = C.c_int(), C.c_int(), C.c_int()
+        K = self._L.lep_gpu_debug_wchunks(self.handle, None, 0, C.byref(nseg), C.byref(parts), C.byref(chunks))
+        if not K:
+            return 0, 0, None
+        recs = np.zeros((nseg.value, K, 16), dtype=np.uint32)
+        if self._L.lep_gpu_debug_wchunks(self.handle, recs.ctypes.data_as(C.c_void_p), nseg.value * K, None, None, None) != K:
+            raise LeptonError(1, "lep_gpu_debug_wchunks [%s]" % self.last_error())
+        return parts.value, chunks.value, recs
+
     def close(self):
         if self.handle:
             self._L.lep_gpu_destroy(self.handle)

@@ -610,6 +610,8 @@ struct lep_gpu {
     int enc5_gather_wgs = 0; // LEP_ENC5_GATHER_WGS: resident gather workgroups per CU held to this (through the LDS a launch asks for)
     int enc5_fold_apart = 0; // LEP_ENC5_FOLD_APART: the fold launches one after the other, a launch per kind of chain (for the profiler)
     size_t enc5_scratch_max = ~(size_t)0;   // LEP_ENC5_SCRATCH_MAX (bytes): a launch that needs more takes the single-kernel encoder (tests: the out-of-memory path)
+    int wchunks_parts = 0, wchunks_per_part = 0;   // the stitched writer's cut in the most recent encode launch (0: it used none) and that launch's
+    std::vector<uint32_t> wchunks_slots;           // segments in launch order, as the caller counts them (lep_gpu_debug_wchunks)
     hipEvent_t ev_stage[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // stage boundaries of the last split-phase launch
     int nstage = 0;
     int enc_waves = 0;       // the same choice for the encoder (LEP_ENC_WAVES = 4 | 8; 2 = the two-wavefronts-per-segment kernel)
@@ -980,6 +982,7 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     }
     HIPCHK(g, hipEventRecord(g->ev_enc5_done, st));
     HIPCHK(g, hipGetLastError());
+    g->wchunks_parts = beside ? nparts : (K >= 2 ? 1 : 0); g->wchunks_per_part = beside ? c : (K >= 2 ? K : 0);
     g->last_kernel = wrote_beside ? "lep_enc5 (count | emit | fold | gather | write: part chunks beside gather)" : "lep_enc5 (count | emit | fold | gather | write)";
     return 0;
 }
@@ -1081,6 +1084,7 @@ static int launch_front(lep_gpu* g, bool dec, const lep_image_desc* images, int 
             std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cls[a] > cls[b]; });
         }
     }
+    if (!dec) g->wchunks_slots.assign((size_t)nseg, 0u);
     for (int i = 0; i < nseg; ++i) {
         const int s = order[i];
         hseg[i].image = segs[s].image; hseg[i].y0 = segs[s].luma_y_start; hseg[i].y1 = segs[s].luma_y_end;
@@ -1089,6 +1093,7 @@ static int launch_front(lep_gpu* g, bool dec, const lep_image_desc* images, int 
         uint64_t cap = stream_offsets[s + 1] - stream_offsets[s];
         hseg[i].stream_cap = (uint32_t)(cap > 0xffffffffu ? 0xffffffffu : cap);
         hseg[i].slot = (uint32_t)s;
+        if (!dec) g->wchunks_slots[(size_t)i] = (uint32_t)s;
         hns[i] = ns_total;
         ns_total += (uint64_t)himg[segs[s].image].ns_total;
     }
@@ -1149,6 +1154,7 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
         int waves = g->enc_waves;
         if (!waves) waves = nseg > 4608 ? 8 : (nseg <= g->enc_pair_max ? 2 : 4);
         bool done = false;
+        g->wchunks_parts = g->wchunks_per_part = 0;
         if (g->enc5_min > 0 && !g->enc_waves && nseg >= g->enc5_min) {   // (LEP_ENC_WAVES asks for one of the single-kernel forms)
             const int rc = launch_enc5(g, F.d_img, F.d_seg, F.d_nsoff, nseg, d_streams, d_stream_len, d_status, st);
             if (rc && rc != kEnc5NoMemory) return rc;
@@ -1857,6 +1863,156 @@ size_t lep_gpu_debug_huffenc(lep_gpu* g, void* out, size_t cap) {
     if (hipSetDevice(g->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
     const size_t n = std::min(cap, w.cap);
     return hipMemcpy(out, w.p, n, hipMemcpyDeviceToHost) == hipSuccess ? n : 0;
+}
+
+// tests: the split-phase encoder's bool writer kernels on bin lists the caller gives, one list per segment, launched in launch_enc5's
+// order in one of its three forms (include/lepton_mi355x.h).  The lists are laid out as gather leaves them (each 256-byte aligned with
+// room to the next multiple of 128 bins, 256 bytes behind the last); for the forms in parts a small arena holds every segment's Ckpt5
+// table and WriterState5, a part's bins reach the device when its turn comes (what lies behind them is still 0xA5) and SegPlan5::nbins is
+// set before the last part, as gather's last part sets it.  Everything is memory of the call's own, on the object's stream.
+namespace {
+struct DebugDev {   // device allocations of one debug call: freed on every way out
+    std::vector<void*> p;
+    ~DebugDev() { for (void* q : p) (void)hipFree(q); }
+    hipError_t get(void** out, size_t bytes) {
+        *out = nullptr;
+        const hipError_t e = hipMalloc(out, bytes ? bytes : 16);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+}  // namespace
+int lep_gpu_debug_write_bins(lep_gpu* g, int form, int parts, int chunks, int nseg, const uint16_t* bins, const uint32_t* nbins,
+                             const uint64_t* stream_off, const uint32_t* stream_cap, const int32_t* plan_status, const uint32_t* part_first,
+                             int guard, uint8_t* arena_out, size_t arena_bytes, uint32_t* stream_len, int32_t* status, void* wchunks) {
+    if (!g) return LEP_GPU_ERROR;
+    if (int rc = refuse_if_session(g, "lep_gpu_debug_write_bins")) return rc;
+    const bool in_parts = form == LEP_DEBUG_WRITE_LANE || form == LEP_DEBUG_WRITE_PART_CHUNKS;
+    bool ok = nseg >= 1 && nseg <= 65536 && bins && nbins && stream_off && stream_cap && arena_out && stream_len && status &&
+              (form == LEP_DEBUG_WRITE_LANE || form == LEP_DEBUG_WRITE_STITCHED || form == LEP_DEBUG_WRITE_PART_CHUNKS);
+    if (ok && in_parts) ok = parts >= 1 && parts <= (int)lep5::kMaxParts && (parts == 1 || part_first);
+    if (ok && form == LEP_DEBUG_WRITE_STITCHED) ok = parts == 1 && chunks >= 1 && chunks <= 256;
+    if (ok && form == LEP_DEBUG_WRITE_PART_CHUNKS) ok = chunks >= 1 && chunks <= 32;
+    uint64_t end = 0;
+    for (int s = 0; ok && s < nseg; ++s) {   // reservations: ascending, apart, inside the arena; part bounds: ascending from 0, inside the list
+        ok = stream_off[s] >= end && stream_off[s] + stream_cap[s] <= arena_bytes && nbins[s] < (1u << 28);
+        end = stream_off[s] + stream_cap[s];
+        for (int p = 0; ok && in_parts && parts > 1 && p < parts; ++p) {
+            const uint32_t b = part_first[(size_t)s * parts + p];
+            ok = p == 0 ? b == 0 : (b >= part_first[(size_t)s * parts + p - 1] && b <= nbins[s]);
+        }
+    }
+    if (!ok) { g->err = "lep_gpu_debug_write_bins: arguments out of range"; return LEP_ASSERTION_FAILURE; }
+    HIPCHK(g, hipSetDevice(g->device));
+    const int K = form == LEP_DEBUG_WRITE_STITCHED ? chunks : form == LEP_DEBUG_WRITE_PART_CHUNKS ? parts * chunks : 0;
+    constexpr uint32_t kSegArena = 1024;   // [kMaxParts] Ckpt5 | WriterState5
+    static_assert(lep5::kMaxParts * sizeof(lep5::Ckpt5) + sizeof(lep5::WriterState5) <= kSegArena, "a segment's checkpoints and writer state");
+    std::vector<lep5::SegPlan5> plans((size_t)nseg);
+    std::vector<SegDev> segs((size_t)nseg);
+    std::vector<uint8_t> h_arena((size_t)nseg * kSegArena, 0xEE);
+    std::vector<uint64_t> first((size_t)nseg + 1, 0);   // where the caller's lists start in `bins`
+    uint64_t total = 0;
+    for (int s = 0; s < nseg; ++s) {
+        lep5::SegPlan5& P = plans[(size_t)s];
+        memset(&P, 0, sizeof P);
+        P.arena_off = (uint64_t)s * kSegArena; P.ckpt_base = 0; P.wstate_base = (uint32_t)(lep5::kMaxParts * sizeof(lep5::Ckpt5)); P.arena_bytes = kSegArena;
+        P.bins_off = total; P.bins_cap = (nbins[s] + 127u) & ~127u;
+        P.nbins = in_parts && parts > 1 ? 0xEEEEEEEEu : nbins[s];   // (gather's last part writes it: nothing may ask for it before)
+        P.status = plan_status ? plan_status[s] : 0;
+        total += P.bins_cap;
+        first[(size_t)s + 1] = first[(size_t)s] + nbins[s];
+        lep5::Ckpt5* ck = reinterpret_cast<lep5::Ckpt5*>(h_arena.data() + P.arena_off);
+        for (int p = 1; in_parts && p < parts; ++p) ck[p].nbins = part_first[(size_t)s * parts + p];
+        SegDev& sd = segs[(size_t)s];
+        memset(&sd, 0, sizeof sd);
+        sd.stream_off = stream_off[s]; sd.stream_cap = stream_cap[s]; sd.slot = (uint32_t)s;
+    }
+    std::vector<lep5::SegPlan5> plans_last(plans);   // ... as they are once the last part is there
+    for (int s = 0; s < nseg; ++s) plans_last[(size_t)s].nbins = nbins[s];
+    std::vector<uint16_t> h_bins((size_t)total + 128, 0xA5A5);
+    for (int s = 0; s < nseg; ++s)
+        if (nbins[s]) memcpy(h_bins.data() + plans[(size_t)s].bins_off, bins + first[(size_t)s], (size_t)nbins[s] * 2);
+    DebugDev dev;
+    lep5::SegPlan5* d_plans; SegDev* d_segs; uint8_t *d_arena, *d_out; uint16_t* d_list; lep5::WChunk5* d_recs; uint32_t *d_len, *d_nb; int32_t* d_status;
+    const size_t list_bytes = (size_t)total * 2 + 256, rec_bytes = (size_t)nseg * (size_t)std::max(K, 1) * sizeof(lep5::WChunk5);
+    HIPCHK(g, dev.get((void**)&d_plans, plans.size() * sizeof(lep5::SegPlan5)));
+    HIPCHK(g, dev.get((void**)&d_segs, segs.size() * sizeof(SegDev)));
+    HIPCHK(g, dev.get((void**)&d_arena, h_arena.size()));
+    HIPCHK(g, dev.get((void**)&d_list, list_bytes));
+    HIPCHK(g, dev.get((void**)&d_recs, rec_bytes));
+    HIPCHK(g, dev.get((void**)&d_out, arena_bytes));
+    HIPCHK(g, dev.get((void**)&d_len, (size_t)nseg * 4));
+    HIPCHK(g, dev.get((void**)&d_nb, (size_t)nseg * 4));
+    HIPCHK(g, dev.get((void**)&d_status, (size_t)nseg * 4));
+    hipStream_t st = g->stream;
+    HIPCHK(g, hipMemcpyAsync(d_plans, plans.data(), plans.size() * sizeof(lep5::SegPlan5), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(SegDev), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemcpyAsync(d_arena, h_arena.data(), h_arena.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(g, hipMemsetAsync(d_list, 0xA5, list_bytes, st));
+    HIPCHK(g, hipMemsetAsync(d_recs, 0xEE, rec_bytes, st));
+    HIPCHK(g, hipMemsetAsync(d_out, guard & 255, arena_bytes ? arena_bytes : 16, st));
+    HIPCHK(g, hipMemsetAsync(d_len, 0x7f, (size_t)nseg * 4, st));
+    HIPCHK(g, hipMemsetAsync(d_status, 0x7f, (size_t)nseg * 4, st));
+    // part p's bins of every segment (all of them where the form has no parts)
+    auto send_part = [&](int p) -> int {
+        if (!in_parts || parts == 1) { HIPCHK(g, hipMemcpyAsync(d_list, h_bins.data(), (size_t)total * 2, hipMemcpyHostToDevice, st)); return 0; }
+        for (int s = 0; s < nseg; ++s) {
+            const uint32_t b0 = part_first[(size_t)s * parts + p], b1 = p + 1 < parts ? part_first[(size_t)s * parts + p + 1] : nbins[s];
+            const uint64_t at = plans[(size_t)s].bins_off + b0;
+            if (b1 > b0) HIPCHK(g, hipMemcpyAsync(d_list + at, h_bins.data() + at, (size_t)(b1 - b0) * 2, hipMemcpyHostToDevice, st));
+        }
+        if (p + 1 == parts) HIPCHK(g, hipMemcpyAsync(d_plans, plans_last.data(), plans_last.size() * sizeof(lep5::SegPlan5), hipMemcpyHostToDevice, st));
+        return 0;
+    };
+    const int groups = (nseg + 63) / 64;
+    if (form == LEP_DEBUG_WRITE_LANE) {
+        for (int part = 0; part < parts; ++part) {
+            if (int rc = send_part(part)) return rc;
+            hipLaunchKernelGGL(lep_enc5_write_kernel, dim3(groups), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, d_out,
+                               d_len, d_status, d_nb, d_arena, part, parts);
+        }
+    } else if (form == LEP_DEBUG_WRITE_STITCHED) {
+        if (int rc = send_part(0)) return rc;
+        const int lane_groups = (int)(((long)nseg * K + 63) / 64);
+#define LEP_WCHUNK(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, K, d_recs, d_out, d_len, d_status, d_nb)
+        LEP_WCHUNK(0, lane_groups); LEP_WCHUNK(1, groups); LEP_WCHUNK(2, lane_groups); LEP_WCHUNK(3, groups);
+#undef LEP_WCHUNK
+    } else {
+        const int c = chunks, lane_groups = (int)(((long)nseg * c + 63) / 64);
+#define LEP_WPART(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_part_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, \
+                                                  parts, c, part, d_recs, d_out, (const uint8_t*)d_arena, d_status, d_nb)
+        for (int part = 0; part < parts; ++part) {
+            if (int rc = send_part(part)) return rc;
+            LEP_WPART(0, lane_groups); LEP_WPART(1, groups); LEP_WPART(2, lane_groups);
+        }
+#undef LEP_WPART
+        hipLaunchKernelGGL((lep_enc5_wchunk_kernel<3>), dim3(groups), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, K, d_recs,
+                           d_out, d_len, d_status, d_nb);
+    }
+    HIPCHK(g, hipGetLastError());
+    HIPCHK(g, hipMemcpyAsync(arena_out, d_out, arena_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(g, hipMemcpyAsync(stream_len, d_len, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(g, hipMemcpyAsync(status, d_status, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
+    if (wchunks && K) HIPCHK(g, hipMemcpyAsync(wchunks, d_recs, rec_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(g, hipStreamSynchronize(st));
+    return 0;
+}
+
+// tests: the stitched writer's records of the most recent split-phase launch, a copy out of W_ENC5_WCHUNKS in the caller's segment order
+int lep_gpu_debug_wchunks(lep_gpu* g, void* out, size_t cap_records, int* nseg, int* parts, int* chunks) {
+    if (!g) return 0;
+    const int K = g->wchunks_parts * g->wchunks_per_part, n = (int)g->wchunks_slots.size();
+    if (nseg) *nseg = K ? n : 0;
+    if (parts) *parts = g->wchunks_parts;
+    if (chunks) *chunks = g->wchunks_per_part;
+    const Workspace& w = g->ws[lep_gpu::W_ENC5_WCHUNKS];
+    if (!K || !out || cap_records < (size_t)n * K || !w.p || w.cap < (size_t)n * K * sizeof(lep5::WChunk5)) return K;
+    if (hipSetDevice(g->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 0;
+    std::vector<lep5::WChunk5> recs((size_t)n * K);
+    if (hipMemcpy(recs.data(), w.p, recs.size() * sizeof(lep5::WChunk5), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    for (int i = 0; i < n; ++i)   // launch order -> the caller's
+        memcpy((char*)out + (size_t)g->wchunks_slots[(size_t)i] * K * sizeof(lep5::WChunk5), &recs[(size_t)i * K], (size_t)K * sizeof(lep5::WChunk5));
+    return K;
 }
 
 // profiling builds (-DLEP_PROF) only: per-phase shader-clock totals folded over the segments of the last decoder launch

@@ -526,3 +526,59 @@ extern "C" int emu_prog_scan_deps(const lep_huffprogdec_scan* scans, const int* 
     for (int i = 0; i < n; ++i) for (int d = 0; d < 4; ++d) deps_out[4 * i + d] = deps[(size_t)i].dep[d];
     return ok ? 1 : 0;
 }
+
+// one bin list (probability | bit << 8) through lepdev::BoolCoder<false> into `cap` bytes of room: start marker, bins, 32 stop bins, end
+// rule; the reference tests/bool_writer_ref.py is held against it
+extern "C" int emu_bool_writer_list(const uint16_t* bins, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* len, int* overflow) {
+    lepdev::BoolCoder<false> ref;
+    ref.init_stream(out, cap);
+    for (uint32_t i = 0; i < n; ++i) ref.put(bins[i] >> 8, bins[i] & 255);
+    *len = ref.finish();
+    *overflow = ref.overflow ? 1 : 0;
+    return 0;
+}
+
+// ... and through the split-phase encoder's writer as lep_gpu_debug_write_bins launches it on the GPU (form 0 write_wave in `parts` parts,
+// 1 the stitched writer over `chunks` chunks, 2 `chunks` chunks per part, part by part; part_first[parts] the parts' first bins, kWarm5):
+// bytes, length, status and, for the chunked forms, the records (parts * chunks of them).  The list has room to the next multiple of
+// 128 bins and 256 bytes behind, the later parts' bins are 0xA5A5 until their part comes, nbins is there from the last part on.
+extern "C" int emu_write_bins5(int form, int parts, int chunks, const uint16_t* bins, uint32_t n, const uint32_t* part_first, int plan_status,
+                               uint8_t* out, uint32_t cap, uint32_t* len, int32_t* status, lep5::WChunk5* recs) {
+    using namespace lep5;
+    if (parts < 1 || parts > kMaxParts || chunks < 1) return 1;
+    std::vector<uint16_t> work(((size_t)n + 127) / 128 * 128 + 128, 0xA5A5);
+    std::vector<uint8_t> arena(1024, 0xEE);
+    SegPlan5 plan;
+    memset(&plan, 0, sizeof plan);
+    plan.ckpt_base = 0; plan.wstate_base = (uint32_t)(kMaxParts * sizeof(Ckpt5)); plan.status = plan_status;
+    Ckpt5* ck = reinterpret_cast<Ckpt5*>(arena.data());
+    uint32_t B[kMaxParts + 1];
+    for (int p = 0; p < parts; ++p) B[p] = p == 0 ? 0u : part_first[p];
+    B[parts] = n;
+    for (int p = 1; p < parts; ++p) ck[p].nbins = B[p];
+    SegDev sd;
+    memset(&sd, 0, sizeof sd);
+    sd.stream_cap = cap;
+    *len = 0x7f7f7f7fu; *status = 0;   // (the kernels clear the status before the writer runs)
+    if (form == 1) {
+        memcpy(work.data(), bins, (size_t)n * 2);
+        plan.nbins = n;
+        for (int k = 0; k < chunks; ++k) wchunk_range_lane(plan, work.data(), recs + k, k, chunks);
+        wchunk_link_lane(plan, work.data(), recs, chunks);
+        for (int k = 0; k < chunks; ++k) wchunk_code_lane(plan, work.data(), sd, out, recs + k, k, chunks);
+        wchunk_stitch_lane(plan, sd, out, len, status, recs, chunks);
+        return 0;
+    }
+    plan.nbins = parts > 1 ? 0xEEEEEEEEu : n;
+    for (int p = 0; p < parts; ++p) {
+        for (uint32_t i = B[p]; i < B[p + 1]; ++i) work[i] = bins[i];
+        if (p + 1 == parts) plan.nbins = n;
+        if (form == 0) { write_wave(&plan, work.data(), &sd, 0, 1, out, len, status, arena.data(), p, parts); continue; }
+        const int c = chunks;
+        for (int s = 0; s < c; ++s) wchunk_range_cut(plan, work.data(), recs + p * c + s, part_chunk_cut(plan, ck, p, s, parts, c));
+        wchunk_link_cuts(plan, work.data(), recs, p * c, (p + 1) * c, [&](int j) { return part_chunk_cut(plan, ck, j / c, j % c, parts, c); });
+        for (int s = 0; s < c; ++s) wchunk_code_cut(plan, work.data(), sd, out, recs + p * c + s, part_chunk_cut(plan, ck, p, s, parts, c));
+    }
+    if (form == 2) wchunk_stitch_lane(plan, sd, out, len, status, recs, parts * chunks);
+    return 0;
+}
