@@ -144,7 +144,7 @@ int lep_gpu_expect_company(lep_gpu *g, int on);
  * ring holds events recorded on those streams; this waits for the copies and drops the events. */
 int lep_gpu_settle_uploads(lep_gpu *g);
 int lep_gpu_sync(lep_gpu *g);
-double lep_gpu_last_kernel_ms(lep_gpu *g);          /* HIP-event duration of the most recent encode / decode / scan launch (ms; -1: none timed) */
+double lep_gpu_last_kernel_ms(lep_gpu *g);          /* HIP-event duration of the most recent encode / decode / scan / sample launch (ms; -1: none timed) */
 /* The split-phase encoder (lep_enc5.h) is several kernels: stage times of the most recent encode launch that used it, in
  * order count + plan, emit, fold, gather, write (HIP events on the launch stream); returns how many were written (0: the
  * launch was a single-kernel one). */
@@ -230,6 +230,37 @@ int lep_gpu_pack_device(lep_gpu *g, const uint8_t *d_src, const uint64_t *src_of
 int lep_gpu_pack_window_device(lep_gpu *g, const uint8_t *d_src, const uint64_t *src_off, const uint32_t *d_len,
                                const uint32_t *win_skip, const uint32_t *win_take, int n,
                                uint8_t *d_dst, uint64_t d_dst_cap, uint64_t *d_dst_off, void *hip_stream);
+/* Coefficient frames in device memory -> 8-bit sample planes, one per component at the component's own resolution: no upsampling, no
+ * colour conversion, no cropping (lep_samples.h; nimg images in one launch; enqueues on hip_stream and returns; lep_gpu_last_kernel_ms
+ * times it).  images[].blocks are device pointers, 16-byte aligned, the frames exactly as the coders keep them.  Plane k = image * 3 +
+ * component is width_blocks * 8 / scale by height_blocks * 8 / scale samples at d_planes[k], pitch[k] bytes from row to row; entries of
+ * components an image does not have are not read.
+ * The arithmetic.  d[k] = c[k] * q[k], an 8x8 raster per block.
+ *   scale 1: the two-pass integer transform of libjpeg's jidctint ("islow") with 13-bit constants, columns first, then rows; with the
+ *   inputs i0..i7 of one column or row
+ *       z1 = (i2+i6)*4433;  t2 = z1 - i6*15137;  t3 = z1 + i2*6270
+ *       t0 = (i0+i4)<<13;   t1 = (i0-i4)<<13
+ *       t10 = t0+t3; t13 = t0-t3; t11 = t1+t2; t12 = t1-t2
+ *       a0 = i7; a1 = i5; a2 = i3; a3 = i1
+ *       z1 = a0+a3; z2 = a1+a2; z3 = a0+a2; z4 = a1+a3; z5 = (z3+z4)*9633
+ *       a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299
+ *       z1 *= -7373; z2 *= -20995; z3 = z3*-16069 + z5; z4 = z4*-3196 + z5
+ *       a0 += z1+z3; a1 += z2+z4; a2 += z2+z3; a3 += z1+z4
+ *       out[0..7] = t10+a3, t11+a2, t12+a1, t13+a0, t13-a0, t12-a1, t11-a2, t10-a3
+ *   each output descaled as (x + (1 << (s-1))) >> s, arithmetic shift, s = 11 behind the column pass and 18 behind the row pass; the
+ *   sample is clamp(result + 128, 0, 255).
+ *   scale 8: one sample per block, clamp(((d[0] + 4) >> 3) + 128, 0, 255).
+ *   Exact integer arithmetic -- equal to libjpeg's islow decoder sample for sample -- for frames in which every |d[k]| <= 32767 and every
+ *   value between the passes is <= 32767 in magnitude (real files: |d| up to 1020, 4188 between the passes); outside, what the formulas
+ *   give in wrapping 32-bit arithmetic, where libjpeg does not agree with itself either.
+ * row_first / row_end ([nimg * 3] block rows per plane, both NULL = every row): only the sample rows of block rows [row_first, row_end)
+ * are written, at their place in the plane -- a caller that holds a decode session (lep_gpu_decode_rows_*) turns each finished band
+ * into samples; the call uses no workspace of a session and may be made while one is open.  An empty range writes nothing.
+ * LEP_ASSERTION_FAILURE with a lep_gpu_last_error text, nothing launched: a scale other than 1 or 8, a pitch below the plane's width, a
+ * row range that is not inside the component, a missing or misaligned frame, a missing plane.  LEP_GPU_ERROR as everywhere. */
+int lep_gpu_samples_device(lep_gpu *g, const lep_image_desc *images, int nimg, int scale /* 1 or 8 */,
+                           const int32_t *row_first, const int32_t *row_end, /* [nimg*3] block rows per component, NULL = all */
+                           uint8_t *const *d_planes /* [nimg*3] */, const int32_t *pitch /* [nimg*3], bytes */, void *hip_stream);
 /* Progressive files that END INSIDE A SCAN (no EOI) in lep_compress_batch / lep_decompress_batch: on = 1 sends them to the scan kernels
  * (lep_jpeg_open_gpu_progressive_cut, lep_file_recode_plan_progressive_cut), on = 0 -- what a codec starts with, unless
  * LEP_CUT_PROGRESSIVE=1 was set when it was made -- keeps them with the host parser and re-coder, where every earlier release had them;
@@ -546,6 +577,18 @@ int lep_compress(lep_gpu *g, const uint8_t *jpg, size_t len, lep_bytes *out);
  * One file per call, on the host parser; lep_compress_batch_slices takes many slices through the batch pipeline and gives the same bytes. */
 int lep_compress_slice(lep_gpu *g, const uint8_t *jpg, size_t len, size_t start_byte, size_t trunc, lep_bytes *out);
 int lep_decompress(lep_gpu *g, const uint8_t *lepdata, size_t len, lep_bytes *out);
+/* .lep -> 8-bit sample planes: parse, decode on the device, lep_gpu_samples_device, the planes copied down -- no scan is written and no
+ * JPEG byte crosses PCIe.  Takes every file lep_decompress takes (baseline, progressive, truncated, -startbyte / -trunc slices, embedded
+ * files; of a chained stream the first file) and returns its codes for a file that does not parse or a stream that does not decode.
+ * Blocks the file never coded -- the tail of a truncated file, the rows in front of a slice -- are zero in the frame and come out as 128.
+ * scale: 1 or 8 (anything else: LEP_ASSERTION_FAILURE).  The planes are the components' block grids, not cropped to width x height. */
+typedef struct lep_planes {
+    int32_t width, height, ncomp, scale;          /* the image's size in pixels, as its frame header says */
+    int32_t h_samp[3], v_samp[3];                 /* sampling factors */
+    int32_t plane_width[3], plane_height[3], pitch[3];   /* samples stored: the block grid, not cropped */
+    uint8_t *plane[3];                            /* one allocation; lep_free(plane[0]) */
+} lep_planes;
+int lep_decompress_planes(lep_gpu *g, const uint8_t *lepdata, size_t len, int scale, lep_planes *out);
 /* lep_decompress with the JPEG's bytes handed to `sink` as they become final, in file order.  Every single file the split re-coder plans
  * (lep_file_recode_plan says gpu_ok: a baseline file or a -startbyte / -trunc slice of one, 'Z' or 'Y', one scan of one, two or three
  * components, cut inside that scan or not, with or without restart intervals; lep_file_streams_in_session answers for a file)

@@ -136,6 +136,12 @@ class RangeStats(C.Structure):
                 ("scan_bytes_down", C.c_uint64), ("frame_bytes_down", C.c_uint64), ("wall_s", C.c_double)]
 
 
+class Planes(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("scale", C.c_int32),
+                ("h_samp", C.c_int32 * 3), ("v_samp", C.c_int32 * 3), ("plane_width", C.c_int32 * 3), ("plane_height", C.c_int32 * 3),
+                ("pitch", C.c_int32 * 3), ("plane", C.c_void_p * 3)]
+
+
 class BatchOptions(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("verify", C.c_int32), ("chunk_frame_bytes", C.c_size_t), ("host_huffman", C.c_int32), ("chunk_images", C.c_int32), ("overlap_launches", C.c_int32)]
 
@@ -244,6 +250,9 @@ def lib():
             L.lep_file_recode_tail.argtypes = [vp, C.c_uint64, P(Bytes), P(C.c_uint64)]
             L.lep_decompress_batch_ranges.argtypes = [vp, P(Bytes), P(Range), C.c_int, C.c_int, P(Bytes), P(C.c_int32), P(BatchOptions), P(RangeStats)]
             L.lep_decompress_range.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint64, P(Bytes)]
+        if hasattr(L, "lep_gpu_samples_device"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_gpu_samples_device.argtypes = [vp, P(ImageDesc), C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), P(vp), P(C.c_int32), vp]
+            L.lep_decompress_planes.argtypes = [vp, vp, C.c_size_t, C.c_int, P(Planes)]
         L.lep_gpu_use_arena.argtypes = [vp, C.c_int]
         L.lep_gpu_sync.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
@@ -341,4 +350,5 @@ EXPORTS = [
     "lep_gpu_decode_rows_retire", "lep_gpu_pack_window_device", "lep_file_range_plan", "lep_file_recode_segment_end", "lep_file_recode_tail",
     "lep_decompress_batch_ranges", "lep_decompress_range",
     "lep_gpu_debug_write_bins", "lep_gpu_debug_wchunks",
+    "lep_gpu_samples_device", "lep_decompress_planes",
 ]

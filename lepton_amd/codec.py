@@ -306,6 +306,81 @@ class GpuCodec:
         self._L.lep_free(out.data)
         return data
 
+    def decompress_planes(self, lep, scale=1):
+        """lep_decompress_planes: a dict of the record's fields (width, height, ncomp, scale, h_samp, v_samp, plane_width, plane_height,
+        pitch) and "planes": one bytes object of pitch * plane_height bytes per component"""
+        out = abi.Planes()
+        rc = self._L.lep_decompress_planes(self.handle, bytes(lep), len(lep), scale, C.byref(out))
+        if rc:
+            raise LeptonError(rc, "lep_decompress_planes [%s]" % self.last_error())
+        n = out.ncomp
+        res = {k: getattr(out, k) for k in ("width", "height", "ncomp", "scale")}
+        for k in ("h_samp", "v_samp", "plane_width", "plane_height", "pitch"):
+            res[k] = list(getattr(out, k))[:n]
+        res["planes"] = [C.string_at(out.plane[c], out.pitch[c] * out.plane_height[c]) for c in range(n)]
+        self._L.lep_free(out.plane[0])
+        return res
+
+    SAMPLES_MARGIN = 256      # canary bytes in front of and behind every plane of samples()
+    SAMPLES_CANARY = 0xEE
+
+    def samples(self, descs, scale=1, rows=None, pitch=None):
+        """lep_gpu_samples_device on host frames: descs is a list of ImageDesc with HOST block pointers; the frames go up, the planes are
+        laid out in one device buffer filled with SAMPLES_CANARY -- SAMPLES_MARGIN bytes, the plane (pitch * height bytes), SAMPLES_MARGIN
+        bytes, for every plane -- and the launch runs.  rows: per image and component (first, end) block rows, None = all; pitch: per
+        image and component bytes, None = the plane's width.  Returns per image and component the plane's whole buffer with both
+        margins (bytes).  Raises LeptonError with the entry point's code; LeptonError.buffers then holds the buffers as they were left."""
+        L, h = self._L, self.handle
+        nimg = len(descs)
+        dev = (abi.ImageDesc * nimg)()
+        owned = []
+
+        def dmalloc(k):
+            p = C.c_void_p()
+            _check(L.lep_gpu_malloc(h, max(k, 16), C.byref(p)), "lep_gpu_malloc")
+            owned.append(p)
+            return p
+
+        try:
+            planes = (C.c_void_p * (nimg * 3))()
+            pitches = (C.c_int32 * (nimg * 3))()
+            first = (C.c_int32 * (nimg * 3))()
+            end = (C.c_int32 * (nimg * 3))()
+            sizes, offs, room = {}, {}, 0
+            per = scale if scale in (1, 8) else 1   # (a scale the entry point refuses: the buffers are laid out all the same)
+            for i, d in enumerate(descs):
+                C.memmove(C.byref(dev[i]), C.byref(d), C.sizeof(abi.ImageDesc))
+                for c in range(d.ncomp):
+                    k = i * 3 + c
+                    nbytes = d.nblocks(c) * 128
+                    p = dmalloc(nbytes)
+                    _check(L.lep_gpu_memcpy_h2d(h, p, d.blocks[c], nbytes), "h2d")
+                    dev[i].blocks[c] = p.value
+                    pitches[k] = pitch[i][c] if pitch is not None else d.width_blocks[c] * 8 // per
+                    first[k], end[k] = rows[i][c] if rows is not None else (0, d.height_blocks[c])
+                    sizes[k] = max(pitches[k], 0) * (d.height_blocks[c] * 8 // per)
+                    offs[k] = room + self.SAMPLES_MARGIN
+                    room = offs[k] + sizes[k] + self.SAMPLES_MARGIN
+            d_out = dmalloc(room)
+            _check(L.lep_gpu_memset(h, d_out, self.SAMPLES_CANARY, room), "memset")
+            for k, o in offs.items():
+                planes[k] = d_out.value + o
+            rc = L.lep_gpu_samples_device(h, dev, nimg, scale, first if rows is not None else None, end if rows is not None else None, planes, pitches, None)
+            if not rc:
+                rc = L.lep_gpu_sync(h)
+            host = C.create_string_buffer(room)
+            _check(L.lep_gpu_memcpy_d2h(h, host, d_out, room), "d2h")
+            raw = host.raw
+            bufs = [[raw[offs[i * 3 + c] - self.SAMPLES_MARGIN:offs[i * 3 + c] + sizes[i * 3 + c] + self.SAMPLES_MARGIN] for c in range(d.ncomp)] for i, d in enumerate(descs)]
+            if rc:
+                e = LeptonError(rc, "lep_gpu_samples_device [%s]" % self.last_error())
+                e.buffers = bufs
+                raise e
+            return bufs
+        finally:
+            for p in owned:
+                L.lep_gpu_free(h, p)
+
     def _batch(self, fn, blobs, verify, threads, chunk_bytes, chunk_images=0, host_huffman=False):
         n = len(blobs)
         ins = (abi.Bytes * n)()

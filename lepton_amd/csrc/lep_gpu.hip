@@ -32,6 +32,7 @@
 #include "lep_huffprogdec_rst.h"
 #include "lep_scan_decode_plan.h"
 #include "lep_pack.h"
+#include "lep_samples.h"
 
 using namespace lepdev;
 
@@ -369,6 +370,20 @@ __global__ __launch_bounds__(64) void lep_pack_copy_kernel(const uint8_t* __rest
     const int i = (int)blockIdx.x;
     leppack::copy_run(src + src_off[i], dst + dst_off[i], len[i], threadIdx.x & 63u);
 }
+// coefficient frames -> 8-bit sample planes (lep_samples.h): four wavefronts per workgroup, each with a unit and an LDS tile of its own
+__global__ __launch_bounds__(64 * lepsamples::kWavesPerGroup) void lep_samples_kernel(const lepsamples::PlaneRec* __restrict__ recs, const uint32_t* __restrict__ first, int nplanes) {
+    __shared__ uint32_t tiles[lepsamples::kWavesPerGroup][lepsamples::kTileWords];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = blockIdx.x * (uint32_t)lepsamples::kWavesPerGroup + (uint32_t)wave;
+    if (unit >= first[nplanes]) return;
+    lepsamples::wave_samples(recs, first, nplanes, unit, tiles[wave]);
+}
+__global__ __launch_bounds__(64 * lepsamples::kWavesPerGroup) void lep_samples_dc_kernel(const lepsamples::PlaneRec* __restrict__ recs, const uint32_t* __restrict__ first, int nplanes) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = blockIdx.x * (uint32_t)lepsamples::kWavesPerGroup + (uint32_t)wave;
+    if (unit >= first[nplanes]) return;
+    lepsamples::wave_samples_dc(recs, first, nplanes, unit);
+}
 // ... with a window per run (lep_gpu_pack_window_device): the clipped lengths are made here, from the device's lengths, summed, and left in wlen
 __global__ __launch_bounds__(leppack::kScanLanes) void lep_pack_window_offsets_kernel(const uint32_t* __restrict__ len, const uint32_t* __restrict__ skip,
                                                                                       const uint32_t* __restrict__ take, int n, uint32_t* __restrict__ wlen,
@@ -677,6 +692,7 @@ struct lep_gpu {
         W_HUFFDEC,                  // HuffDecImage[]
         W_HUFFPAR,                  // the lane-per-subsequence scan decoder's records (SimtImage | SimtWave | SimtSub x 2 | SimtPlace)
         W_PACK, W_PACK_1,           // lep_gpu_pack_device: the runs' source offsets (one per arena set, like W_HUFF)
+        W_SAMPLES, W_SAMPLES_1,     // lep_gpu_samples_device: PlaneRec[] | first[] (one per arena set)
         W_COUNT
     };
     lepbuf::DevBuf<> ws[W_COUNT];
@@ -1495,6 +1511,61 @@ int lep_gpu_pack_window_device(lep_gpu* g, const uint8_t* d_src, const uint64_t*
                        (const uint32_t*)ws.at<uint32_t>(o_wlen), n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
     HIPCHK(g, hipGetLastError());
     g->last_kernel = "lep_pack_window_{offsets,copy}_kernel";
+    return 0;
+}
+
+// Coefficient frames in device memory -> 8-bit sample planes (lep_samples.h).  Like the pack kernels its one workspace, W_SAMPLES of the
+// current arena set, is no decode session's: a caller that holds a session turns each finished band into samples with a row range.
+int lep_gpu_samples_device(lep_gpu* g, const lep_image_desc* images, int nimg, int scale, const int32_t* row_first, const int32_t* row_end,
+                           uint8_t* const* d_planes, const int32_t* pitch, void* hip_stream) {
+    if (!g) return LEP_GPU_ERROR;
+    auto refuse = [g](const std::string& what) { g->err = "lep_gpu_samples_device: " + what; return (int)LEP_ASSERTION_FAILURE; };
+    if (scale != 1 && scale != 8) return refuse("scale " + std::to_string(scale) + " (1 or 8)");
+    if (nimg < 0 || nimg > (1 << 20) || (nimg > 0 && (!images || !d_planes || !pitch)) || (!row_first != !row_end)) return refuse("images, planes and pitches, and both ends of the row ranges or neither");
+    std::vector<lepsamples::PlaneRec> recs;
+    std::vector<uint32_t> first(1, 0u);
+    for (int i = 0; i < nimg; ++i) {
+        const lep_image_desc& d = images[i];
+        if (d.ncomp < 1 || d.ncomp > LEP_MAX_COMPONENTS) return refuse("image " + std::to_string(i) + " has " + std::to_string(d.ncomp) + " components");
+        for (int c = 0; c < d.ncomp; ++c) {
+            const int k = i * 3 + c;
+            const std::string who = "image " + std::to_string(i) + " component " + std::to_string(c) + ": ";
+            const int wb = d.width_blocks[c], hb = d.height_blocks[c];
+            if (wb < 1 || hb < 1 || wb > (1 << 24) || hb > (1 << 24)) return refuse(who + std::to_string(wb) + " x " + std::to_string(hb) + " blocks");
+            if (!d.blocks[c] || ((uintptr_t)d.blocks[c] & 15u) || !d_planes[k]) return refuse(who + "a frame (16-byte aligned) and a plane");
+            if (pitch[k] < wb * 8 / scale) return refuse(who + "pitch " + std::to_string(pitch[k]) + " is less than the plane's width " + std::to_string(wb * 8 / scale));
+            const int r0 = row_first ? row_first[k] : 0, r1 = row_end ? row_end[k] : hb;
+            if (r0 < 0 || r1 < r0 || r1 > hb)
+                return refuse(who + "block rows [" + std::to_string(r0) + ", " + std::to_string(r1) + ") are not rows of its " + std::to_string(hb));
+            lepsamples::PlaneRec r;
+            const uint64_t units = lepsamples::fill_plane(&r, d.blocks[c], d_planes[k], wb, pitch[k], r0, r1, d.qtable_zigzag[c], scale);
+            if (units + first.back() > 0x7fffffffull) return refuse("more than 2^31 wavefront units in one call");
+            recs.push_back(r);
+            first.push_back(first.back() + (uint32_t)units);
+        }
+    }
+    const uint32_t total = first.back();
+    if (!total) return 0;   // nothing to write: empty row ranges
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
+    HIPCHK(g, hipSetDevice(g->device));
+    const int nplanes = (int)recs.size();
+    const size_t rec_bytes = recs.size() * sizeof(lepsamples::PlaneRec), first_bytes = first.size() * sizeof(uint32_t);
+    std::vector<char> table(rec_bytes + first_bytes);   // one upload: the records, the unit counts behind them
+    memcpy(table.data(), recs.data(), rec_bytes);
+    memcpy(table.data() + rec_bytes, first.data(), first_bytes);
+    Workspace& ws = g->ws[lep_gpu::W_SAMPLES + (g->cur & 1)];
+    if (int rc = ensure(g, ws, table.size())) return rc;
+    if (int rc = upload(g, ws.p, table.data(), table.size(), st)) return rc;
+    const lepsamples::PlaneRec* d_recs = ws.at<lepsamples::PlaneRec>(0);
+    const uint32_t* d_first = ws.at<uint32_t>(rec_bytes);
+    const unsigned groups = (total + lepsamples::kWavesPerGroup - 1) / lepsamples::kWavesPerGroup;
+    HIPCHK(g, hipEventRecord(g->ev0, st));
+    if (scale == 1) hipLaunchKernelGGL(lep_samples_kernel, dim3(groups), dim3(64 * lepsamples::kWavesPerGroup), 0, st, d_recs, d_first, nplanes);
+    else hipLaunchKernelGGL(lep_samples_dc_kernel, dim3(groups), dim3(64 * lepsamples::kWavesPerGroup), 0, st, d_recs, d_first, nplanes);
+    HIPCHK(g, hipGetLastError());
+    HIPCHK(g, hipEventRecord(g->ev1, st));
+    g->timed = true;
+    g->last_kernel = scale == 1 ? "lep_samples_kernel" : "lep_samples_dc_kernel";
     return 0;
 }
 
