@@ -764,6 +764,47 @@ void lep_batch_release(void);   /* frees the staging buffers the two calls above
 void lep_batch_footprint(size_t *pinned_bytes, size_t *device_bytes);
 /* test hook: overwrite the pinned staging buffers kept between batch calls with `value` (stale-staging regression tests) */
 void lep_batch_debug_poison(int value);
+/* Test hooks for the round-trip check of lep_compress_batch with verify = 1.  A .lep is released only after three things held on the
+ * device, one flag word per file: bit 0 (value 1) -- the streams decoded again into a scratch frame, and that frame differs from the
+ * input frame (lep_compare_kernel); bit 1 (value 2) -- the scan written again from the frame differs from the file's own bytes
+ * (lep_scan_check_bytes_kernel for a baseline file's thread segments, lep_scan_check_kernel for progressive scans); and every status
+ * of the verification decode was zero.  Bit 0 or a status is LEP_ROUNDTRIP_FAILURE; bit 1 alone sends the file through the per-file path.
+ * The two calls below run those kernels, with the pipeline's own launch geometry, on device buffers the caller gives (lep_gpu_malloc),
+ * on the default stream, and wait for the result.
+ * lep_batch_debug_compare: the first bytes / 16 units of 16 bytes of d_a and d_b (both 16-byte aligned); a difference ORs `value` into
+ * *d_flag.  LEP_ASSERTION_FAILURE: a pointer that is not aligned. */
+int lep_batch_debug_compare(lep_gpu *g, const void *d_a, const void *d_b, size_t bytes, uint32_t *d_flag, uint32_t value);
+/* One check item: ref_len bytes of the output arena at out_off against as many of the reference arena at ref_off; item i's written
+ * length is d_out_len[i].  `image` is the index of the flag word that gets bit 1.  LEP_SCAN_CHECK_PREFIX in `image` (the aligned form
+ * only: the scan a file ends in, written whole): the length may exceed ref_len, bit 31 of it is not looked at, the first ref_len bytes
+ * count.  Without it the length must equal ref_len, bit 31 (a writer that gave up) included. */
+typedef struct lep_scan_check { uint64_t out_off, ref_off; uint32_t ref_len, image; } lep_scan_check;
+#define LEP_SCAN_CHECK_PREFIX 0x80000000u
+/* lep_batch_debug_scan_check: `items` is a host array of n entries.  bytes_form != 0: lep_scan_check_bytes_kernel, any alignment, no
+ * prefix items; 0: lep_scan_check_kernel, d_out + out_off and d_ref + ref_off 16-byte aligned.  The call knows no buffer sizes: every
+ * item must lie inside the buffers given, every `image` inside d_flags.  LEP_ASSERTION_FAILURE: a misaligned item or a prefix item
+ * where the form takes none. */
+int lep_batch_debug_scan_check(lep_gpu *g, int bytes_form, const uint8_t *d_out, const uint32_t *d_out_len, const uint8_t *d_ref,
+                               const lep_scan_check *items, int n, uint32_t *d_flags);
+/* Test hook, of lep_batch_debug_poison's standing (process-global, not re-entrant): arms ONE alteration for the next lep_compress_batch /
+ * lep_compress_batch_slices call only -- one byte of a buffer the pipeline owns is XORed with xor_mask by a one-lane kernel, stream-
+ * ordered on the compute stream of the chunk that holds `file` (the index in that call's input array):
+ *   LEP_TAMPER_STREAM   the stream arena, `offset` into the file's first thread segment: behind the coder kernels, in front of the
+ *                       verification decode (applied without verify too: the byte then reaches the .lep)
+ *   LEP_TAMPER_SCRATCH  the file's scratch frame: behind the verification decode, in front of the frame comparison
+ *   LEP_TAMPER_VSCAN    a baseline file's first check segment as written again: in front of lep_scan_check_bytes_kernel
+ *   LEP_TAMPER_PSCAN    a progressive file's first check scan as written again: in front of lep_scan_check_kernel
+ * `offset` is held on the host against a size known before anything is queued -- the segment's reservation in the stream arena, the
+ * frame's exact bytes, the check segment's output cap -- and an offset outside, a file that is not in a chunk, or a buffer the call
+ * does not have (no verify, no check segment) leaves the alteration unapplied: it never writes outside the buffer it names.  It is
+ * disarmed when the call returns, applied or not; where = 0 disarms at once.  lep_batch_debug_tamper_applied: how often the last armed
+ * alteration was applied, 0 or 1. */
+enum { LEP_TAMPER_STREAM = 1, LEP_TAMPER_SCRATCH = 2, LEP_TAMPER_VSCAN = 3, LEP_TAMPER_PSCAN = 4 };
+void lep_batch_debug_tamper(int where, int file, uint64_t offset, int xor_mask);
+int lep_batch_debug_tamper_applied(void);
+/* ... and what the check then said of the altered file in a call with verify (both 0 when the file's coder had refused it, or without
+ * verify): its flag word, and the first status of its verification decode that was not zero.  Returns the applied count. */
+int lep_batch_debug_tamper_seen(uint32_t *flags, int32_t *decode_status);
 
 /* ---- serving surface ------------------------------------------------------------------------------
  * The `lepton -socket[=name] / -listen[=port]` protocol (src/lepton/socket_serve.cc:312-390, jpgcoder.cc:1162-1186):

@@ -136,6 +136,14 @@ class RangeStats(C.Structure):
                 ("scan_bytes_down", C.c_uint64), ("frame_bytes_down", C.c_uint64), ("wall_s", C.c_double)]
 
 
+class ScanCheck(C.Structure):
+    _fields_ = [("out_off", C.c_uint64), ("ref_off", C.c_uint64), ("ref_len", C.c_uint32), ("image", C.c_uint32)]
+
+
+SCAN_CHECK_PREFIX = 0x80000000
+TAMPER_STREAM, TAMPER_SCRATCH, TAMPER_VSCAN, TAMPER_PSCAN = 1, 2, 3, 4
+
+
 class Planes(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("scale", C.c_int32),
                 ("h_samp", C.c_int32 * 3), ("v_samp", C.c_int32 * 3), ("plane_width", C.c_int32 * 3), ("plane_height", C.c_int32 * 3),
@@ -320,6 +328,13 @@ def lib():
         L.lep_batch_scan_second_chances.restype = C.c_uint64
         L.lep_batch_debug_poison.argtypes = [C.c_int]
         L.lep_batch_debug_poison.restype = None
+        if hasattr(L, "lep_batch_debug_tamper"):   # (absent from an older build named by LEP_LIB_PATH)
+            L.lep_batch_debug_compare.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_uint32]
+            L.lep_batch_debug_scan_check.argtypes = [vp, C.c_int, vp, vp, vp, P(ScanCheck), C.c_int, vp]
+            L.lep_batch_debug_tamper.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int]
+            L.lep_batch_debug_tamper.restype = None
+            L.lep_batch_debug_tamper_applied.argtypes = []
+            L.lep_batch_debug_tamper_seen.argtypes = [P(C.c_uint32), P(C.c_int32)]
         L.lep_jpeg_plan_handoffs.argtypes = [vp, C.c_int, P(Handoff), C.c_int]
         L.lep_handoffs_serialize.argtypes = [P(Handoff), C.c_int, vp, C.c_size_t]
         L.lep_handoffs_parse.argtypes = [vp, C.c_size_t, P(Handoff), C.c_int]
@@ -351,4 +366,5 @@ EXPORTS = [
     "lep_decompress_batch_ranges", "lep_decompress_range",
     "lep_gpu_debug_write_bins", "lep_gpu_debug_wchunks",
     "lep_gpu_samples_device", "lep_decompress_planes",
+    "lep_batch_debug_compare", "lep_batch_debug_scan_check", "lep_batch_debug_tamper", "lep_batch_debug_tamper_applied", "lep_batch_debug_tamper_seen",
 ]

@@ -532,6 +532,87 @@ class GpuCodec:
             raise LeptonError(1, "lep_gpu_debug_wchunks [%s]" % self.last_error())
         return parts.value, chunks.value, recs
 
+    def _debug_device_arrays(self, arrays):
+        """device copies of numpy arrays (lep_gpu_malloc, 16 bytes of room at least) -> (pointers, release)"""
+        L, h = self._L, self.handle
+        owned = []
+
+        def release():
+            for p in owned:
+                L.lep_gpu_free(h, p)
+
+        try:
+            for a in arrays:
+                p = C.c_void_p()
+                _check(L.lep_gpu_malloc(h, max(a.nbytes, 16), C.byref(p)), "lep_gpu_malloc")
+                owned.append(p)
+                if a.nbytes:
+                    _check(L.lep_gpu_memcpy_h2d(h, p, a.ctypes.data_as(C.c_void_p), a.nbytes), "lep_gpu_memcpy_h2d")
+        except Exception:
+            release()
+            raise
+        return owned, release
+
+    def debug_compare(self, a, b, nbytes, flags, word, value):
+        """lep_batch_debug_compare (tests): lep_compare_kernel, as `verify` launches it, on the first nbytes of the uint8 arrays a and b;
+        a difference ORs `value` into flags[word].  -> the uint32 flag array as it stands on the device afterwards"""
+        import numpy as np
+
+        a, b = np.ascontiguousarray(a, dtype=np.uint8), np.ascontiguousarray(b, dtype=np.uint8)
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        if nbytes > min(a.size, b.size) or not 0 <= word < flags.size:
+            raise ValueError("debug_compare: the compared length or the flag word lies outside the arrays")
+        (d_a, d_b, d_f), release = self._debug_device_arrays([a, b, flags])
+        try:
+            rc = self._L.lep_batch_debug_compare(self.handle, d_a, d_b, nbytes, C.c_void_p(d_f.value + 4 * word), value)
+            if rc:
+                raise LeptonError(rc, "lep_batch_debug_compare [%s]" % self.last_error())
+            out = np.zeros_like(flags)
+            _check(self._L.lep_gpu_memcpy_d2h(self.handle, out.ctypes.data_as(C.c_void_p), d_f, out.nbytes), "lep_gpu_memcpy_d2h")
+            return out
+        finally:
+            release()
+
+    def debug_scan_check(self, bytes_form, out, out_len, ref, items, flags):
+        """lep_batch_debug_scan_check (tests): lep_scan_check_bytes_kernel (bytes_form) or lep_scan_check_kernel on the uint8 arenas
+        `out` and `ref`; items = [(out_off, ref_off, ref_len, image)], out_len[i] the written length of item i.  Every item is held
+        against the arrays' sizes here: the library call knows none.  -> the uint32 flag array as it stands on the device afterwards"""
+        import numpy as np
+
+        out, ref = np.ascontiguousarray(out, dtype=np.uint8), np.ascontiguousarray(ref, dtype=np.uint8)
+        out_len, flags = np.ascontiguousarray(out_len, dtype=np.uint32), np.ascontiguousarray(flags, dtype=np.uint32)
+        n = len(items)
+        if out_len.size != n:
+            raise ValueError("debug_scan_check: one written length per item")
+        for oo, ro, rl, image in items:
+            word = image & ~abi.SCAN_CHECK_PREFIX      # (a prefix item in the bytes form is the library's to refuse)
+            if min(oo, ro, rl) < 0 or oo + rl > out.size or ro + rl > ref.size or not 0 <= word < flags.size:
+                raise ValueError("debug_scan_check: an item lies outside the arrays")
+        arr = (abi.ScanCheck * max(1, n))(*[abi.ScanCheck(*it) for it in items])
+        (d_out, d_len, d_ref, d_f), release = self._debug_device_arrays([out, out_len, ref, flags])
+        try:
+            rc = self._L.lep_batch_debug_scan_check(self.handle, 1 if bytes_form else 0, d_out, d_len, d_ref, arr, n, d_f)
+            if rc:
+                raise LeptonError(rc, "lep_batch_debug_scan_check [%s]" % self.last_error())
+            got = np.zeros_like(flags)
+            _check(self._L.lep_gpu_memcpy_d2h(self.handle, got.ctypes.data_as(C.c_void_p), d_f, got.nbytes), "lep_gpu_memcpy_d2h")
+            return got
+        finally:
+            release()
+
+    def debug_tamper(self, where, file, offset, xor_mask):
+        """lep_batch_debug_tamper (tests): arms one altered byte for the next compress_batch call (abi.TAMPER_*)"""
+        self._L.lep_batch_debug_tamper(where, file, offset, xor_mask)
+
+    def debug_tamper_applied(self):
+        return int(self._L.lep_batch_debug_tamper_applied())
+
+    def debug_tamper_seen(self):
+        """(flag word, first non-zero status of the verification decode) of the file the last applied alteration was made in"""
+        flags, status = C.c_uint32(), C.c_int32()
+        self._L.lep_batch_debug_tamper_seen(C.byref(flags), C.byref(status))
+        return flags.value, status.value
+
     def close(self):
         if self.handle:
             self._L.lep_gpu_destroy(self.handle)

@@ -91,8 +91,8 @@ __global__ void lep_compare_kernel(const uint4* __restrict__ a, const uint4* __r
 // Round-trip check of progressive files: one workgroup per scan compares what the GPU scan encoder has just written
 // with the file's own bytes of that scan (uploaded beside the un-stuffed copy the decoder read); any difference -- the
 // length, a byte, an encoder that gave up (bit 31 of its length) -- sets bit 1 of the image's flag word.
-struct ScanCheck { uint64_t out_off, ref_off; uint32_t ref_len, image; };
-constexpr uint32_t kScanCheckPrefix = 0x80000000u;   // ScanCheck::image: the scan a file ends in -- written whole, its first ref_len bytes are the file's
+using ScanCheck = lep_scan_check;                           // { out_off, ref_off, ref_len, image }: public for the test hooks
+constexpr uint32_t kScanCheckPrefix = LEP_SCAN_CHECK_PREFIX;   // ScanCheck::image: the scan a file ends in -- written whole, its first ref_len bytes are the file's
 __global__ void lep_scan_check_kernel(const uint8_t* __restrict__ out, const uint32_t* __restrict__ out_len, const uint8_t* __restrict__ ref,
                                       const ScanCheck* __restrict__ items, uint32_t* flags) {
     ScanCheck it = items[blockIdx.x];
@@ -120,6 +120,24 @@ __global__ void lep_scan_check_bytes_kernel(const uint8_t* __restrict__ out, con
     if (!diff)
         for (uint32_t i = threadIdx.x; i < it.ref_len; i += blockDim.x) diff |= out[it.out_off + i] != ref[it.ref_off + i];
     if (diff) atomicOr(flags + it.image, 2u);
+}
+
+// The launches of the three check kernels, once: launch_compress_chunk and the test hooks (lep_batch_debug_compare, lep_batch_debug_scan_check)
+// both go through these, so a test runs the product's grid, block and arguments and not a copy of them.
+void launch_compare(const void* a, const void* b, size_t bytes, uint32_t* flag, uint32_t value, hipStream_t st) {
+    hipLaunchKernelGGL(lep_compare_kernel, dim3(256), dim3(256), 0, st, (const uint4*)a, (const uint4*)b, bytes / 16, flag, value);
+}
+// one workgroup of 256 per item (n > 0)
+void launch_scan_check_bytes(const uint8_t* out, const uint32_t* out_len, const uint8_t* ref, const ScanCheck* items, unsigned n, uint32_t* flags, hipStream_t st) {
+    hipLaunchKernelGGL(lep_scan_check_bytes_kernel, dim3(n), dim3(256), 0, st, out, out_len, ref, items, flags);
+}
+void launch_scan_check(const uint8_t* out, const uint32_t* out_len, const uint8_t* ref, const ScanCheck* items, unsigned n, uint32_t* flags, hipStream_t st) {
+    hipLaunchKernelGGL(lep_scan_check_kernel, dim3(n), dim3(256), 0, st, out, out_len, ref, items, flags);
+}
+
+// test hook (lep_batch_debug_tamper): one lane XORs one byte
+__global__ void lep_debug_xor_kernel(uint8_t* p, uint32_t mask) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *p = (uint8_t)(*p ^ mask);
 }
 
 // Hundreds of host threads each allocating and freeing MB-sized vectors (un-stuffed scan data, containers) serialise on
@@ -770,6 +788,66 @@ int parse_and_upload(CompressCall& x, Chunk* c, Slot* s) {
     return 0;
 }
 
+// Test hook (lep_batch_debug_tamper): one armed alteration, applied at most once, by the chunk that holds the file, at the stage it names.
+struct Tamper {
+    bool armed = false;
+    int where = 0, file = -1, mask = 0, applied = 0;
+    uint64_t offset = 0;
+    uint32_t seen_flags = 0;    // what the check then said of that file, as write_containers read it: its flag word ...
+    int32_t seen_status = 0;    // ... and the first status of its verification decode that was not zero
+};
+Tamper g_tamper;
+// Where the armed byte lies in the chunk's buffer of stage `where`, or false: another stage, the file is not in this chunk, the call
+// has no such buffer, or the offset lies outside what the layout gave that buffer (sizes known on the host before anything is queued).
+bool tamper_target(const Tamper& t, bool verify, const Chunk& c, int where, size_t* at) {
+    if (!t.armed || t.where != where) return false;
+    size_t k = 0;
+    while (k < c.live.size() && c.live[k] != t.file) ++k;
+    if (k == c.live.size()) return false;
+    if (where == LEP_TAMPER_STREAM) {
+        const size_t q = (size_t)c.seg_first[k];
+        if ((int)q >= c.seg_first[k + 1] || t.offset >= c.offs[q + 1] - c.offs[q]) return false;
+        *at = (size_t)(c.offs[q] + t.offset);
+        return true;
+    }
+    if (!verify) return false;
+    if (where == LEP_TAMPER_SCRATCH) {
+        if (t.offset >= frame_exact_bytes(c.host_desc[k])) return false;
+        *at = c.frame_off[k] + (size_t)t.offset;
+        return true;
+    }
+    if (where == LEP_TAMPER_VSCAN) {
+        for (size_t q = 0; q < c.vseg.size(); ++q) if (c.vcheck[q].image == (uint32_t)k) {
+            if (t.offset >= c.vseg[q].out_cap) return false;
+            *at = (size_t)(c.vseg[q].out_off + t.offset);
+            return true;
+        }
+        return false;
+    }
+    if (where == LEP_TAMPER_PSCAN) {
+        for (size_t q = 0; q < c.pscan.size(); ++q) if ((c.pcheck[q].image & ~kScanCheckPrefix) == (uint32_t)k) {
+            if (t.offset >= c.pscan[q].out_cap) return false;
+            *at = (size_t)(c.pscan[q].out_off + t.offset);
+            return true;
+        }
+        return false;
+    }
+    return false;
+}
+hipError_t tamper_chunk(CompressCall& x, Chunk* c, Slot* s, int where, hipStream_t st) {
+    size_t at = 0;
+    if (!tamper_target(g_tamper, x.verify, *c, where, &at)) return hipSuccess;
+    uint8_t* base = (uint8_t*)(where == LEP_TAMPER_STREAM ? s->d_streams.p : where == LEP_TAMPER_SCRATCH ? s->d_scratch.p
+                               : where == LEP_TAMPER_VSCAN ? s->d_vscan.p : s->d_pscan.p);
+    const size_t cap = where == LEP_TAMPER_STREAM ? s->d_streams.cap : where == LEP_TAMPER_SCRATCH ? s->d_scratch.cap
+                     : where == LEP_TAMPER_VSCAN ? s->d_vscan.cap : s->d_pscan.cap;
+    if (!base || at >= cap) return hipSuccess;   // (the layout's sizes lie inside the allocations: held once more against the allocation itself)
+    g_tamper.armed = false;
+    g_tamper.applied += 1;
+    hipLaunchKernelGGL(lep_debug_xor_kernel, dim3(1), dim3(64), 0, st, base + at, (uint32_t)(g_tamper.mask & 0xff));
+    return hipGetLastError();
+}
+
 // coder kernels of one chunk, stream-ordered behind the previous chunk's (the call returns once they are enqueued, i.e.
 // after the previous chunk's kernels have finished: the descriptor upload inside lep_gpu_encode_device is synchronous)
 int launch_compress_chunk(CompressCall& x, Chunk* c, Slot* s) {
@@ -779,31 +857,31 @@ int launch_compress_chunk(CompressCall& x, Chunk* c, Slot* s) {
     hipStream_t s_compute = x.s_compute[set];
     if (int rc0 = lep_gpu_use_arena(x.g, set)) return rc0;
     HIPOK(hipStreamWaitEvent(s_compute, s->up, 0));
+    const bool tamper = g_tamper.armed;   // (test hook: the one test an unarmed call pays per chunk)
     int rc = lep_gpu_encode_device(x.g, c->dev_desc.data(), nimg, c->segs.data(), nseg, s->d_streams, c->offs.data(), s->d_len, s->d_status, s_compute);
     if (rc) return rc;
+    if (tamper) HIPOK(tamper_chunk(x, c, s, LEP_TAMPER_STREAM, s_compute));
     if (x.verify) {
         HIPOK(hipMemsetAsync(s->d_scratch, 0, c->frame_bytes, s_compute));
         HIPOK(hipMemsetAsync(s->d_flags, 0, (size_t)nimg * 4, s_compute));
         rc = lep_gpu_decode_device(x.g, c->scratch_desc.data(), nimg, c->segs.data(), nseg, s->d_streams, c->offs.data(), s->d_len, s->d_status + nseg, s_compute);
         if (rc) return rc;
-        for (int k = 0; k < nimg; ++k) {
-            const size_t fb = frame_exact_bytes(c->host_desc[k]);   // the frame itself, not its rounded room in the slot
-            hipLaunchKernelGGL(lep_compare_kernel, dim3(256), dim3(256), 0, s_compute, (const uint4*)(s->d_frames + c->frame_off[k]),
-                               (const uint4*)(s->d_scratch + c->frame_off[k]), fb / 16, s->d_flags + k, 1u);
-        }
+        if (tamper) HIPOK(tamper_chunk(x, c, s, LEP_TAMPER_SCRATCH, s_compute));
+        for (int k = 0; k < nimg; ++k)   // the frame itself, not its rounded room in the slot
+            launch_compare(s->d_frames + c->frame_off[k], s->d_scratch + c->frame_off[k], frame_exact_bytes(c->host_desc[k]), s->d_flags + k, 1u, s_compute);
         x.st.gpu_verified_scans += (double)(c->vseg.size() + c->pscan.size());
         if (!c->vseg.empty()) {    // baseline files: the Huffman half, thread segment by thread segment against the file's bytes
             rc = lep_gpu_huffman_encode_device(x.g, c->vimg.data(), (int)c->vimg.size(), c->vseg.data(), (int)c->vseg.size(), s->d_vscan, s->d_vscanlen, nullptr, s_compute);
             if (rc) return rc;
-            hipLaunchKernelGGL(lep_scan_check_bytes_kernel, dim3((unsigned)c->vseg.size()), dim3(256), 0, s_compute, s->d_vscan, s->d_vscanlen, s->d_scan,
-                               s->d_vcheck, s->d_flags);
+            if (tamper) HIPOK(tamper_chunk(x, c, s, LEP_TAMPER_VSCAN, s_compute));
+            launch_scan_check_bytes(s->d_vscan, s->d_vscanlen, s->d_scan, s->d_vcheck, (unsigned)c->vseg.size(), s->d_flags, s_compute);
         }
         if (!c->pscan.empty()) {   // progressive files: the Huffman half, scan by scan against the file's bytes
             rc = lep_gpu_huffman_progressive_encode_device(x.g, c->pimg.data(), (int)c->pimg.size(), c->pscan.data(), (int)c->pscan.size(), s->d_pscan,
                                                            s->d_corr, s->d_pscanlen, s_compute);
             if (rc) return rc;
-            hipLaunchKernelGGL(lep_scan_check_kernel, dim3((unsigned)c->pscan.size()), dim3(256), 0, s_compute, s->d_pscan, s->d_pscanlen, s->d_scan,
-                               s->d_pcheck, s->d_flags);
+            if (tamper) HIPOK(tamper_chunk(x, c, s, LEP_TAMPER_PSCAN, s_compute));
+            launch_scan_check(s->d_pscan, s->d_pscanlen, s->d_scan, s->d_pcheck, (unsigned)c->pscan.size(), s->d_flags, s_compute);
         }
     }
     HIPOK(hipEventRecord(s->done, s_compute));
@@ -869,6 +947,10 @@ void write_containers(CompressCall& x, Chunk* c, Slot* s, const CompressResults&
         }
         if (!rc && x.verify) {
             for (int q = s0; q < s1; ++q) if (sts[c->segs.size() + (size_t)q]) rc = LEP_ROUNDTRIP_FAILURE;
+            if (g_tamper.applied && g_tamper.file == i) {   // (test hook: which signal the altered file raised)
+                g_tamper.seen_flags = r.flags[k];
+                for (int q = s1 - 1; q >= s0; --q) if (sts[c->segs.size() + (size_t)q]) g_tamper.seen_status = sts[c->segs.size() + (size_t)q];
+            }
             if (r.flags[k] & 1) rc = LEP_ROUNDTRIP_FAILURE;
             // a progressive scan the GPU encoder did not reproduce (trailing restart markers, which the host appends; a
             // non-canonical code choice): the per-file path decides (redo_overflowed)
@@ -976,6 +1058,52 @@ void lep_batch_debug_poison(int value) {
     }
 }
 
+// test hooks: the check kernels of `verify` on buffers the caller gives, through the launchers launch_compress_chunk uses
+int lep_batch_debug_compare(lep_gpu* g, const void* d_a, const void* d_b, size_t bytes, uint32_t* d_flag, uint32_t value) {
+    if (!g || !d_flag) return LEP_GPU_ERROR;
+    if (((uintptr_t)d_a | (uintptr_t)d_b) % 16 || (uintptr_t)d_flag % 4 || (bytes >= 16 && (!d_a || !d_b))) return LEP_ASSERTION_FAILURE;
+    HIPOK(hipSetDevice(lep_gpu_device(g)));
+    launch_compare(d_a, d_b, bytes, d_flag, value, nullptr);
+    HIPOK(hipGetLastError());
+    HIPOK(hipDeviceSynchronize());
+    return 0;
+}
+int lep_batch_debug_scan_check(lep_gpu* g, int bytes_form, const uint8_t* d_out, const uint32_t* d_out_len, const uint8_t* d_ref,
+                               const lep_scan_check* items, int n, uint32_t* d_flags) {
+    if (!g || n < 0) return LEP_GPU_ERROR;
+    if (n == 0) return 0;
+    if (!d_out || !d_out_len || !d_ref || !items || !d_flags) return LEP_GPU_ERROR;
+    for (int i = 0; i < n; ++i) {
+        if (bytes_form ? (items[i].image & kScanCheckPrefix) != 0
+                       : (((uintptr_t)d_out + items[i].out_off) | ((uintptr_t)d_ref + items[i].ref_off)) % 16 != 0) return LEP_ASSERTION_FAILURE;
+    }
+    HIPOK(hipSetDevice(lep_gpu_device(g)));
+    lepbuf::DevBuf<ScanCheck> d_items;
+    HIPOK(d_items.ensure((size_t)n * sizeof(ScanCheck)));
+    hipError_t e = hipMemcpy(d_items, items, (size_t)n * sizeof(ScanCheck), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        (bytes_form ? launch_scan_check_bytes : launch_scan_check)(d_out, d_out_len, d_ref, d_items, (unsigned)n, d_flags, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)d_items.release();
+    return e == hipSuccess ? 0 : LEP_GPU_ERROR;
+}
+
+// test hook: one alteration for the next compress call (see the header); a new arming forgets the last one's count
+void lep_batch_debug_tamper(int where, int file, uint64_t offset, int xor_mask) {
+    g_tamper = Tamper();
+    if (where < LEP_TAMPER_STREAM || where > LEP_TAMPER_PSCAN || file < 0) return;
+    g_tamper.armed = true;
+    g_tamper.where = where; g_tamper.file = file; g_tamper.offset = offset; g_tamper.mask = xor_mask;
+}
+int lep_batch_debug_tamper_applied(void) { return g_tamper.applied; }
+int lep_batch_debug_tamper_seen(uint32_t* flags, int32_t* decode_status) {
+    if (flags) *flags = g_tamper.seen_flags;
+    if (decode_status) *decode_status = g_tamper.seen_status;
+    return g_tamper.applied;
+}
+
 int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs, int32_t* status, const lep_batch_options* o,
                        lep_batch_stats* stats) {
     return lep_compress_batch_slices(g, jpgs, nullptr, n, outs, status, o, stats);
@@ -986,6 +1114,7 @@ int lep_compress_batch(lep_gpu* g, const lep_bytes* jpgs, int n, lep_bytes* outs
 // whatever holds the result against the input -- bytes [start_byte, len).
 int lep_compress_batch_slices(lep_gpu* g, const lep_bytes* files, const lep_slice* slices, int n, lep_bytes* outs, int32_t* status,
                               const lep_batch_options* o, lep_batch_stats* stats) {
+    struct Disarm { ~Disarm() { g_tamper.armed = false; } } disarm;   // (test hook: an armed alteration is this call's, applied or not)
     if (!g || n < 0) return LEP_GPU_ERROR;
     g_batch_gpu = g;
     std::vector<lep_bytes> bounded(files, files + n);

@@ -16,5 +16,6 @@ third=""
 grep -q LEP_HAVE_BROTLI_ENC $O/lep_container.cc.o.flags 2>/dev/null && third="$third $O/brotli/*.o"
 if grep -q LEP_PINNED_ZLIB $O/lep_container.cc.o.flags 2>/dev/null; then third="$third $O/zlib/*.o"; else third="$third -lz"; fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o lepton_amd/liblepton_$name.so $V/lep_gpu.o $V/lep_batch.o $O/lep_api.cc.o $O/jpeg_scan.cc.o \
-  $O/jpeg_progressive.cc.o $O/lep_container.cc.o $O/jpeg_recode.cc.o $O/lep_serve.cc.o $O/lep_stream.cc.o $third -ldl -lpthread
+  $O/jpeg_progressive.cc.o $O/lep_container.cc.o $O/jpeg_recode.cc.o $O/lep_serve.cc.o $O/lep_stream.cc.o \
+  $O/lep_batch_stream.cc.o $O/lep_batch_ranges.cc.o $O/lep_planes.cc.o $third -ldl -lpthread
 echo built lepton_amd/liblepton_$name.so

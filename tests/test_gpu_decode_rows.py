@@ -20,6 +20,7 @@ from lepton_amd import abi, corpus
 from lepton_amd.codec import JpegImage, LepFile, LeptonError
 from test_decode_rows_emulation import (FILL, check_failing_block, damaged_case, damaged_stream, fill_frame, frame_of, oracle_on_damaged,
                                         segment_mcu_rows, segment_rows)
+from test_decode_rows_emulation import emu  # noqa: F401  (the module-scoped fixture that builds tests/emu/libcore_emu_decrows.so)
 
 pytestmark = pytest.mark.gpu
 
@@ -167,6 +168,50 @@ def test_failing_block_on_the_gpu(gpu_codec):
         for c in range(good.desc.ncomp):
             assert np.array_equal(got[c], good_final[c])
     assert refused >= 8, refused   # so that the test cannot pass on nothing: the CPU test asks for 30 of 40, these are 10 of those 40
+
+
+@pytest.mark.parametrize("waves", ["4", "8"])
+def test_one_shot_decoder_on_damaged_streams(emu, monkeypatch, waves):
+    """lep_decode_v4_kernel, both register-budget forms, on the same ten damaged streams, an intact c444_96x80 beside them in the launch:
+    the status is the oracle's exit code, the frame (device frames start as FILL) is byte for byte the frame the same source leaves when
+    it is stepped on the CPU (emu_decode_segment_v4) -- which is the oracle's frame except, at most, for the block the oracle stopped
+    at -- and the neighbour is intact.  `verify` in lep_compress_batch rests on this answer."""
+    from lepton_amd.codec import GpuCodec
+
+    monkeypatch.setenv("LEP_DEC_WAVES", waves)
+    img, s, stream = damaged_case((203, 149))
+    d = img.desc
+    good, good_final = case("c444_96x80")
+    codec = GpuCodec(0)
+    try:
+        refused = 0
+        for seed in range(10):
+            data = damaged_stream(stream, seed)
+            oracle_rc, oracle_frame = oracle_on_damaged(d, s, data)
+            refused += oracle_rc != 0
+            fill_frame(d)
+            emu_rc = emu.emu_decode_segment_v4(C.byref(d), s.luma_y_start, s.luma_y_end, s.is_last, data, len(data), None)
+            emu_frame = frame_of(d)
+            assert emu_rc == oracle_rc, seed
+            differ = [(c,) + tuple(x) for c in range(d.ncomp) for x in np.argwhere((emu_frame[c] != oracle_frame[c]).any(axis=2))]
+            assert len(differ) <= (1 if oracle_rc else 0), (seed, differ[:4])
+            bad = SimpleNamespace(desc=d, segments=[s], streams=[data])
+            fill_frame(d)
+            fill_frame(good.desc)
+            rc, status = decode_device(codec, [bad, good])
+            assert rc == 0
+            assert abi.lib().lep_gpu_last_kernel_name(codec.handle).decode() == "lep_decode_v4_kernel<%s>" % waves
+            print("waves %s seed %d: oracle %d emulation %d gpu %s" % (waves, seed, oracle_rc, emu_rc, status))
+            assert status == [oracle_rc] + [0] * len(good.segments), seed
+            got = frame_of(d)
+            for c in range(d.ncomp):
+                assert np.array_equal(got[c], emu_frame[c]), (seed, c)
+            got = frame_of(good.desc)
+            for c in range(good.desc.ncomp):
+                assert np.array_equal(got[c], good_final[c]), seed
+        assert refused >= 8, refused   # so that the test cannot pass on nothing
+    finally:
+        codec.close()
 
 
 def test_session_owns_its_workspace_set(gpu_codec):

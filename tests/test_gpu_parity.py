@@ -118,14 +118,22 @@ def test_gpu_rejects_out_of_range_coefficient(gpu_codec):
 
 
 def test_gpu_decode_of_garbage_stream_is_contained(gpu_codec):
-    """a corrupt stream must come back as an error code or a (wrong) frame, never hang or crash"""
+    """a corrupt stream must come back as an error code or a (wrong) frame, never hang or crash -- and as the code the oracle's
+    decoder ends with on the same bytes (0: it decodes them to the end)"""
+    from test_decode_rows_emulation import oracle_on_damaged
+
     jpg, lep = golden("c420_160x120")
     f = LepFile(lep)
     f.streams[0] = bytes(len(f.streams[0]))
+    img = JpegImage(jpg)
+    oracle_rc, _ = oracle_on_damaged(img.desc, img.plan()[0], f.streams[0])
+    code = 0
     try:
         gpu_codec.decode([f])
     except LeptonError as e:
-        assert e.code in (6, 7, 43)
+        code = e.code
+    assert code in (0, 6, 7, 43)
+    assert code == oracle_rc
 
 
 def test_gpu_v3_encoder_many_bins_per_block(gpu_codec):
@@ -209,10 +217,13 @@ def test_gpu_decoder_register_budget_forms(env, kernel, monkeypatch):
         assert not any(st) and [C.string_at(d.blocks[c], d.nblocks(c) * 128) for c in range(d.ncomp)] == orig
         bad = list(want)
         bad[1] = bytes(np.random.default_rng(3).integers(0, 256, 300, dtype=np.uint8))
+        from test_decode_rows_emulation import oracle_on_damaged
+        oracle_rc, _ = oracle_on_damaged(d, segs[1], bad[1])    # (leaves its own frame in d: wiped below like the GPU's)
         for c in range(d.ncomp):
             C.memset(d.blocks[c], 0, d.nblocks(c) * 128)
         st = _gpu_decode_streams(codec, d, segs, bad)
         assert all(rc == 0 for i, rc in enumerate(st) if i != 1) and st[1] in (0, 6, 7, 43)
+        assert st[1] == oracle_rc
         w = d.width_blocks[0]
         got = C.string_at(d.blocks[0], d.nblocks(0) * 128)
         for i, s in enumerate(segs):
