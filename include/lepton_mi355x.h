@@ -151,7 +151,8 @@ double lep_gpu_last_kernel_ms(lep_gpu *g);          /* HIP-event duration of the
 int lep_gpu_last_stage_ms(lep_gpu *g, double *ms, int cap);
 const char *lep_gpu_last_kernel_name(lep_gpu *g);   /* which kernel generation / register-budget variant that launch used */
 /* Tests: the split-phase encoder's bool writer kernels on bin lists the caller gives -- one list per segment, `bins` holds them back to
- * back (entries probability | bit << 8), nbins[s] their lengths -- launched in the encoder's order in one of its three forms:
+ * back (entries probability | bit << 8), nbins[s] their lengths -- launched in the encoder's order, by the encoder's own launch function, in
+ * one of its three forms (csrc/lep_enc5_plan.h: which of them a launch of the encoder takes, and with which cut):
  *   LEP_DEBUG_WRITE_LANE         the lane-per-segment writer in `parts` parts (1..8; chunks is not read)
  *   LEP_DEBUG_WRITE_STITCHED     range / link / code / stitch over `chunks` chunks per segment (1..256; parts = 1)
  *   LEP_DEBUG_WRITE_PART_CHUNKS  range / link / code of `chunks` (1..32) chunks per part, part by part, then one stitch

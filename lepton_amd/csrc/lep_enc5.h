@@ -21,6 +21,7 @@
 // Reference citations are those of lep_core.h; the syntax walk below follows SegmentCoder<false>::code_block line by line.
 #pragma once
 #include "lep_v3.h"
+#include "lep_enc5_plan.h"   // kMaxParts
 #ifdef LEP5_DEBUG
 #include <cstdio>
 #endif
@@ -80,7 +81,6 @@ WDEV void key_classes(uint32_t key, int c[4]) {
 // gather and write run in PARTS (tile ranges of every segment): the writer is 128 wavefronts that take the same time whatever the
 // batch, so part k is written while part k + 1 is gathered.  emit leaves what both need to take a segment up at a part's first
 // tile: the walk's counters there.
-constexpr int kMaxParts = 8;
 struct Ckpt5 { uint32_t tile_no, ord0, sign_pos[2], nbins, tcur[16], pad[3]; };   // 96 bytes
 WDEV uint32_t part_first_tile(uint32_t ntiles, int part, int nparts) { return (uint32_t)(((uint64_t)ntiles * (uint32_t)part) / (uint32_t)nparts); }
 

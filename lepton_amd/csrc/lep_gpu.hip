@@ -21,6 +21,7 @@
 #include "lep_enc3.h"
 #include "lep_dec4.h"
 #include "lep_enc5.h"
+#include "lep_enc5_plan.h"
 #include "lep_huff.h"
 #include "lep_huffdec.h"
 #include "lep_huffdec_simt.h"
@@ -588,9 +589,7 @@ struct lep_gpu {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     bool released = false;   // device side already given back (by lep_gpu_destroy or by the exit handler)
-    int enc5_min = 8;        // launches of at least this many segments take the split-phase encoder (lep_enc5.h); LEP_ENC5_MIN (0 = never).  64 until
-                             // round 4: with the stitched writer a single 4K image (8 segments) takes 109 ms through it against 301 ms through the
-                             // two-wavefront single-kernel encoder (profiles/r05k_latency_stitched_writer_ab.json)
+    lep5::Enc5Options opt;   // the encoder knobs (lep_enc5_plan.h: defaults, environment, what was measured)
     hipStream_t stream2 = nullptr, stream3 = nullptr;   // the split-phase encoder folds its long chains beside its many short ones
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join3 = nullptr;
     int huffprog_pipeline = 1;          // LEP_HUFFPROG_PIPELINE=0: progressive scan decode level by level, whatever the launch size
@@ -607,32 +606,11 @@ struct lep_gpu {
     int simt_sub_bits = 0;              // LEP_HUFFDEC_SIMT_BITS: bits per subsequence of the lane-per-subsequence scan decoder (0 = from the launch's size)
     int huffprog_pipeline_max = 16384;  // LEP_HUFFPROG_PIPELINE_MAX: scans per launch up to which the levels go out as one pipelined launch (measured to 10240:
                                         // 1024 4K files, 798 -> 938 MB/s; a workgroup takes the scan of the ticket it draws when it starts, so a scan's predecessors are always running or done)
-    int enc5_waves = 2;      // LEP_ENC5_WAVES: wavefronts per segment in the split-phase walks (1 | 2)
-    int enc5_parts = 8;      // LEP_ENC5_PARTS: gather / write in this many parts (1..8), a part written while the next is gathered
-                             // (MI355X, 1024 x 4K: 1 part 569 ms per launch, 4 parts 481, 8 parts 475)
     hipEvent_t ev_part[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    long enc5_wlanes = 131072;  // LEP_ENC5_WLANES: chunk lanes a launch of the stitched writer may have (segments x chunks per segment)
-    int enc5_wmaxseg = 4096;    // LEP_ENC5_WMAXSEG: launches of more segments take the writer enc5_wsched names (up to it: stitched behind gather)
-    int enc5_wchunks = 64;   // LEP_ENC5_WCHUNKS: the stitched writer for launches that leave lanes free: up to this many chunks per segment (power of
-                             // two; 0 = always the lane-per-segment writer beside gather)
-    bool enc5_parts_given = false;   // LEP_ENC5_PARTS was set: it holds for every launch (else: one part where the writer runs behind gather)
-    int enc5_wsched = 1;     // LEP_ENC5_WSCHED: the writer of launches of more than enc5_wmaxseg segments (LEP_ENC5_WMAXSEG=0: of every launch) --
-                             // 0 | lane: lane per segment beside gather; 1 | after: stitched behind the last gather part, chunks as below
-                             // that size; 2 | beside: stitched, every part's chunks ranged / linked / coded beside the next part's gather
-                             // (MI355X, 1024 x 4K, profiles/r23_*: lane 434 ms per launch; after 423, with gather in one part 403;
-                             // beside 420 at 8 parts x 4 chunks, 402 at 2 parts x 8 -- gather loses more to parts and to company than the writer's tail costs)
-    int enc5_wpartchunks = 4;   // LEP_ENC5_WPARTCHUNKS: chunks per part and segment of the `beside` schedule (a power of two, 1 .. 32)
-    int enc5_gather_wgs = 0; // LEP_ENC5_GATHER_WGS: resident gather workgroups per CU held to this (through the LDS a launch asks for)
-    int enc5_fold_apart = 0; // LEP_ENC5_FOLD_APART: the fold launches one after the other, a launch per kind of chain (for the profiler)
-    size_t enc5_scratch_max = ~(size_t)0;   // LEP_ENC5_SCRATCH_MAX (bytes): a launch that needs more takes the single-kernel encoder (tests: the out-of-memory path)
     int wchunks_parts = 0, wchunks_per_part = 0;   // the stitched writer's cut in the most recent encode launch (0: it used none) and that launch's
     std::vector<uint32_t> wchunks_slots;           // segments in launch order, as the caller counts them (lep_gpu_debug_wchunks)
     hipEvent_t ev_stage[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // stage boundaries of the last split-phase launch
     int nstage = 0;
-    int enc_waves = 0;       // the same choice for the encoder (LEP_ENC_WAVES = 4 | 8; 2 = the two-wavefronts-per-segment kernel)
-    int enc_pair_max = 1280; // launches of up to this many segments take the two-wave encoder: its 128-thread workgroups are resident 6 per
-                             // CU (1536 on the chip), one pass; measured (profiles/r02d_latency_sweep.json, 4K images): 1 .. 128 images
-                             // 300-343 ms against 450-496 ms for one wavefront per segment, 256 images 650 against 510.  LEP_ENC_PAIR_MAX
     int dec_company = 0;     // lep_gpu_expect_company: decode launches will overlap with their neighbours on another stream
     int dec_waves = 0;       // register-budget build of the decoder: 0 = by batch size (8 waves per SIMD / 64 VGPRs once a launch can
                              // fill them, else 4 / 128 VGPRs, no spills); LEP_DEC_WAVES = 4 | 8 forces one
@@ -847,6 +825,29 @@ static int ensure(lep_gpu* g, Workspace& w, size_t need, bool may_release = true
 #include "lep_derive.h"
 
 
+// The bool writer of a split-phase launch, as its plan (lep_enc5_plan.h) says: the kernels of one of the three forms on `wst`, in the
+// encoder's order.  ready(p), p < gather_parts: part p's bins get to `binlist` and `wst` is put behind them; ready(gather_parts): every
+// part's kernels are queued (launch_enc5 marks the stage there).  Also what lep_gpu_debug_write_bins runs on a test's lists.
+template <class Ready>
+static int launch_enc5_writer(const lep5::Enc5WriterPlan& W, const lep5::SegPlan5* plans, const uint16_t* binlist, const SegDev* segs, int nseg, lep5::WChunk5* recs,
+                              uint8_t* arena, uint8_t* streams, uint32_t* stream_len, int32_t* status, uint32_t* bins, hipStream_t wst, Ready&& ready) {
+#define LEP_WCHUNK(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_kernel<PHASE>), dim3(GRID), dim3(64), 0, wst, plans, binlist, segs, nseg, W.records, recs, streams, stream_len, status, bins)
+#define LEP_WPART(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_part_kernel<PHASE>), dim3(GRID), dim3(64), 0, wst, plans, binlist, segs, nseg, \
+                                                  W.gather_parts, W.chunks, part, recs, streams, (const uint8_t*)arena, status, bins)
+    for (int part = 0; part < W.gather_parts; ++part) {
+        if (int rc = ready(part)) return rc;
+        if (W.form == LEP_DEBUG_WRITE_LANE)
+            hipLaunchKernelGGL(lep_enc5_write_kernel, dim3(W.groups), dim3(64), 0, wst, plans, binlist, segs, nseg, streams, stream_len, status, bins, arena, part, W.gather_parts);
+        if (W.form == LEP_DEBUG_WRITE_PART_CHUNKS) { LEP_WPART(0, W.lane_groups); LEP_WPART(1, W.groups); LEP_WPART(2, W.lane_groups); }
+    }
+    if (int rc = ready(W.gather_parts)) return rc;
+    if (W.form == LEP_DEBUG_WRITE_STITCHED) { LEP_WCHUNK(0, W.lane_groups); LEP_WCHUNK(1, W.groups); LEP_WCHUNK(2, W.lane_groups); }
+    if (W.form != LEP_DEBUG_WRITE_LANE) LEP_WCHUNK(3, W.groups);   // stitch: over all of a segment's records
+#undef LEP_WPART
+#undef LEP_WCHUNK
+    return 0;
+}
+
 // The split-phase encoder (lep_enc5.h): count -> plan -> emit -> fold -> gather -> write.  One host synchronisation in the
 // middle: the arena sizes come out of the count pass.  Stage boundaries are recorded as events (lep_gpu_last_stage_ms).
 constexpr int kEnc5NoMemory = -1000;   // launch_enc5: the scratch could not be allocated (nothing has been written for the caller yet)
@@ -875,19 +876,12 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     const int groups = (nseg + 63) / 64;
     g->nstage = 0;
     HIPCHK(g, hipEventRecord(g->ev_stage[0], st));
-    const bool two = g->enc5_waves == 2;
-    // The writer's schedule.  A launch that leaves the chip's lanes free takes the stitched writer behind gather: K chunks per segment (a
-    // power of two up to 64), as many as keep the launch under enc5_wlanes chunk lanes.  Round 4 capped the lanes at 4096 (K = 2 at 256
-    // images: two chains of 1.15 M bins per segment, 118 ms of writer on 64 wavefronts); round 6 measured the cap away (profiles/r6o_*:
-    // 256 images 253 -> 148 ms per launch with K = 32, 128 images 159 -> 107, 512 images -- which had kept the lane-per-segment writer
-    // -- 308 -> 260).  From 4097 segments on enc5_wsched says which (profiles/r23_*).
-    const int wsched = nseg <= g->enc5_wmaxseg ? 1 : g->enc5_wsched;
-    int K = 0;
-    if (g->enc5_wchunks >= 2 && wsched == 1) { K = 1; while (K * 2 <= g->enc5_wchunks && (long)nseg * K * 2 <= g->enc5_wlanes) K *= 2; }
-    int nparts = std::min(std::max(g->enc5_parts, 1), (int)lep5::kMaxParts);   // (emit and gather: settled below, once the records are there)
+    const bool two = g->opt.enc5_waves == 2;
+    lep5::Enc5WriterPlan W = lep5::enc5_writer_plan(nseg, g->opt);
+    int nparts = lep5::enc5_lane_plan(nseg, g->opt).gather_parts;   // (what count is told; emit and gather: the plan's, settled below, once the records are there)
     auto walk =[&](int mode, uint8_t* entries, uint16_t* binlist, int part = 0) {
         size_t lds = lep5::walk_lds_bytes(mode);
-        if (mode == lep5::kGather && g->enc5_gather_wgs > 0) lds = std::max(lds, (size_t)(160 * 1024 / g->enc5_gather_wgs) & ~(size_t)255);   // (measurement aid: fewer resident workgroups)
+        if (mode == lep5::kGather && g->opt.enc5_gather_wgs > 0) lds = std::max(lds, (size_t)(160 * 1024 / g->opt.enc5_gather_wgs) & ~(size_t)255);   // (measurement aid: fewer resident workgroups)
 #define LEP_WALK(MODE, NW) hipLaunchKernelGGL((lep_enc5_walk_kernel<MODE, NW>), dim3(nseg), dim3(64 * NW), lds, st, d_img, d_seg, (NSum*)ns.p, d_nsoff, plans, entries, binlist, counts, part, nparts)
         if (mode == lep5::kCount) { if (two) LEP_WALK(lep5::kCount, 2); else LEP_WALK(lep5::kCount, 1); }
         else if (mode == lep5::kEmit) { if (two) LEP_WALK(lep5::kEmit, 2); else LEP_WALK(lep5::kEmit, 1); }
@@ -903,25 +897,16 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     HIPCHK(g, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
     HIPCHK(g, hipStreamSynchronize(st));
     // no room for the scratch (~140 MB per 4K image): the single-kernel encoder takes the launch -- it needs none
-    if ((size_t)tot[0] + (size_t)tot[1] * 2 > g->enc5_scratch_max || ensure(g, ws_entries, (size_t)tot[0] + 256, false) || ensure(g, ws_binlist, (size_t)tot[1] * 2 + 256, false)) {
+    if ((size_t)tot[0] + (size_t)tot[1] * 2 > g->opt.enc5_scratch_max || ensure(g, ws_entries, (size_t)tot[0] + 256, false) || ensure(g, ws_binlist, (size_t)tot[1] * 2 + 256, false)) {
         (void)hipGetLastError();
         g->err.clear();
         static bool told = false;
         if (!told) { told = true; fprintf(stderr, "lepton-mi355x: no room for the split-phase encoder's scratch (%.1f GB for %d segments): single-kernel encoder\n", ((double)tot[0] + 2.0 * (double)tot[1]) / 1e9, nseg); }
         return kEnc5NoMemory;
     }
-    if (K >= 2 && ensure(g, wchunks, (size_t)nseg * K * sizeof(lep5::WChunk5) + 256, false)) { (void)hipGetLastError(); g->err.clear(); K = 0; }
-    // Parts exist for a writer that runs beside gather.  Behind gather there is nothing to hide, and gather in parts is the slower one
-    // (1024 x 4K, nothing beside it: 8 parts 133 ms, one part 115 -- every part steps through the segment's tiles to its first and ends on
-    // its slowest segment; 512 images 231 against 220 ms per launch, 256 images 142 against 137): a launch that writes behind gather
-    // gathers in ONE part unless LEP_ENC5_PARTS names a number.
-    if (K >= 2 && !g->enc5_parts_given) nparts = 1;
-    // `beside`: c chunks per part, cut at the parts' boundaries -- part p's range / link / code go out on the second stream when part p
-    // is gathered and run beside the gather of part p + 1; behind the last part only that part's phases and the stitch are left
-    const int c = wsched == 2 ? g->enc5_wpartchunks : 0;
-    const bool beside = c >= 1 && !ensure(g, wchunks, (size_t)nseg * nparts * c * sizeof(lep5::WChunk5) + 256, false);
-    if (c >= 1 && !beside) { (void)hipGetLastError(); g->err.clear(); }   // (no room for the records: the lane-per-segment writer)
-    const bool wrote_beside = beside;
+    // (no room for a chunked writer's records: the lane-per-segment writer)
+    if (W.records && ensure(g, wchunks, (size_t)nseg * W.records * sizeof(lep5::WChunk5) + 256, false)) { (void)hipGetLastError(); g->err.clear(); W = lep5::enc5_lane_plan(nseg, g->opt); }
+    nparts = W.gather_parts;
     // (Segment groups on streams of their own -- one group's writer and folds beside the next group's walks -- were measured
     // and dropped: MI355X, 1024 x 4K, profiles/r04l_*: 1 group 784 ms, 2: 875, 4: 1232; launches this large do not share the chip.)
     {
@@ -932,7 +917,7 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         HIPCHK(g, hipEventRecord(g->ev_fork, st));
         HIPCHK(g, hipStreamWaitEvent(g->stream2, g->ev_fork, 0));
         HIPCHK(g, hipStreamWaitEvent(g->stream3, g->ev_fork, 0));
-        if (g->enc5_fold_apart) {   // measurement aid (LEP_ENC5_FOLD_APART=1): every kind of chain as a launch of its own, one after the other
+        if (g->opt.enc5_fold_apart) {   // measurement aid (LEP_ENC5_FOLD_APART=1): every kind of chain as a launch of its own, one after the other
             const int small0[4] = {0, 2, 14, 46}, big0[3] = {0, 12, 32};   // sign | threshold | edge counts;  DC | 7x7 counts
             for (int i = 0; i < 3; ++i)
                 hipLaunchKernelGGL(lep_enc5_fold_small_kernel, dim3((unsigned)groups * (small0[i + 1] - small0[i])), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (uint8_t*)ws_entries.p,
@@ -950,56 +935,23 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
         HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0));
         HIPCHK(g, hipStreamWaitEvent(st, g->ev_join3, 0));
         HIPCHK(g, hipEventRecord(g->ev_stage[3], st));
-        if (beside) {
-            lep5::WChunk5* recs = (lep5::WChunk5*)wchunks.p;
-            const int lane_groups = (int)(((long)nseg * c + 63) / 64);
-#define LEP_WPART(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_part_kernel<PHASE>), dim3(GRID), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, \
-                                                  nparts, c, part, recs, d_streams, (const uint8_t*)ws_entries.p, d_status, g->d_bins)
-            for (int part = 0; part < nparts; ++part) {
-                walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
-                HIPCHK(g, hipEventRecord(g->ev_part[part], st));
-                HIPCHK(g, hipStreamWaitEvent(g->stream2, g->ev_part[part], 0));
-                LEP_WPART(0, lane_groups); LEP_WPART(1, groups); LEP_WPART(2, lane_groups);
-            }
-#undef LEP_WPART
-            HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
-            hipLaunchKernelGGL((lep_enc5_wchunk_kernel<3>), dim3(groups), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, nparts * c, recs,
-                               d_streams, d_stream_len, d_status, g->d_bins);
-            HIPCHK(g, hipEventRecord(g->ev_join, g->stream2));
-            HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0));
-            HIPCHK(g, hipEventRecord(g->ev_stage[5], st));
-            g->nstage = 5;
-        } else if (K >= 2) {
-            for (int part = 0; part < nparts; ++part) walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
-            HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
-            lep5::WChunk5* recs = (lep5::WChunk5*)wchunks.p;
-            const int lane_groups = (int)(((long)nseg * K + 63) / 64);
-#define LEP_WCHUNK(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, K, recs, d_streams, d_stream_len, d_status, g->d_bins)
-            LEP_WCHUNK(0, lane_groups); LEP_WCHUNK(1, groups); LEP_WCHUNK(2, lane_groups); LEP_WCHUNK(3, groups);
-#undef LEP_WCHUNK
-            HIPCHK(g, hipEventRecord(g->ev_stage[5], st));
-            g->nstage = 5;
-        } else {
-        // gather and write in parts (tile ranges of every segment): the writer is 128 wavefronts that take the same time whatever the
-        // batch -- part k is written (second stream) while part k + 1 is gathered
-        for (int part = 0; part < nparts; ++part) {
+        // behind gather the writer follows it on the launch's stream; beside it, it runs on the second one, behind every part's event
+        const hipStream_t wst = W.form == LEP_DEBUG_WRITE_STITCHED ? st : g->stream2;
+        auto gathered = [&](int part) -> int {
+            if (part == nparts) { HIPCHK(g, hipEventRecord(g->ev_stage[4], st)); return 0; }
             walk(lep5::kGather, (uint8_t*)ws_entries.p, (uint16_t*)ws_binlist.p, part);
-            HIPCHK(g, hipEventRecord(g->ev_part[part], st));
-            HIPCHK(g, hipStreamWaitEvent(g->stream2, g->ev_part[part], 0));
-            hipLaunchKernelGGL(lep_enc5_write_kernel, dim3(groups), dim3(64), 0, g->stream2, (const lep5::SegPlan5*)plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, d_streams,
-                               d_stream_len, d_status, g->d_bins, (uint8_t*)ws_entries.p, part, nparts);
-        }
-        HIPCHK(g, hipEventRecord(g->ev_stage[4], st));
-        HIPCHK(g, hipEventRecord(g->ev_join, g->stream2));
-        HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0));
+            if (wst != st) { HIPCHK(g, hipEventRecord(g->ev_part[part], st)); HIPCHK(g, hipStreamWaitEvent(wst, g->ev_part[part], 0)); }
+            return 0;
+        };
+        if (int rc = launch_enc5_writer(W, plans, (const uint16_t*)ws_binlist.p, d_seg, nseg, (lep5::WChunk5*)wchunks.p, (uint8_t*)ws_entries.p, d_streams, d_stream_len, d_status,
+                                        g->d_bins, wst, gathered)) return rc;
+        if (wst != st) { HIPCHK(g, hipEventRecord(g->ev_join, wst)); HIPCHK(g, hipStreamWaitEvent(st, g->ev_join, 0)); }
         HIPCHK(g, hipEventRecord(g->ev_stage[5], st));
         g->nstage = 5;
-        }
     }
     HIPCHK(g, hipEventRecord(g->ev_enc5_done, st));
     HIPCHK(g, hipGetLastError());
-    g->wchunks_parts = beside ? nparts : (K >= 2 ? 1 : 0); g->wchunks_per_part = beside ? c : (K >= 2 ? K : 0);
-    g->last_kernel = wrote_beside ? "lep_enc5 (count | emit | fold | gather | write: part chunks beside gather)" : "lep_enc5 (count | emit | fold | gather | write)";
+    g->wchunks_parts = W.report_parts; g->wchunks_per_part = W.chunks; g->last_kernel = W.name;
     return 0;
 }
 
@@ -1163,27 +1115,17 @@ static int launch(lep_gpu* g, const lep_image_desc* images, int nimg, const lep_
         else { g->last_kernel = "lep_decode_v4_kernel<4>"; LEP_LAUNCH_DEC4(4); }
 #undef LEP_LAUNCH_DEC4
     } else {
-#define LEP_LAUNCH_ENC3(W)                                                                                                     \
-    hipLaunchKernelGGL((lep_encode_v3_kernel<W>), dim3(nseg), dim3(64), 0, st, F.d_img, F.d_seg, (uint32_t*)models.p, (NSum*)ns.p, \
-                       F.d_nsoff, d_streams, d_stream_len, d_status, g->d_bins)
-        // like the decoder: a launch that cannot fill 8 wavefronts per SIMD takes the 4-wave build (128 VGPRs, no spills)
-        int waves = g->enc_waves;
-        if (!waves) waves = nseg > 4608 ? 8 : (nseg <= g->enc_pair_max ? 2 : 4);
-        bool done = false;
+#define LEP_LAUNCH_ENC3(KERNEL, THREADS)                                                                                       \
+    hipLaunchKernelGGL(KERNEL, dim3(nseg), dim3(THREADS), 0, st, F.d_img, F.d_seg, (uint32_t*)models.p, (NSum*)ns.p, F.d_nsoff, \
+                       d_streams, d_stream_len, d_status, g->d_bins)
+        const lep5::EncChoice enc = lep5::enc_choice(nseg, g->opt);   // (lep_enc5_plan.h)
         g->wchunks_parts = g->wchunks_per_part = 0;
-        if (g->enc5_min > 0 && !g->enc_waves && nseg >= g->enc5_min) {   // (LEP_ENC_WAVES asks for one of the single-kernel forms)
-            const int rc = launch_enc5(g, F.d_img, F.d_seg, F.d_nsoff, nseg, d_streams, d_stream_len, d_status, st);
-            if (rc && rc != kEnc5NoMemory) return rc;
-            done = rc == 0;
-        }
-        if (done) {}
-        else if (waves == 2) {   // few segments: two wavefronts per segment (producer / bool coder), half the serial chain
-            g->last_kernel = "lep_encode_v3x2_kernel";
-            hipLaunchKernelGGL(lep_encode_v3x2_kernel, dim3(nseg), dim3(128), 0, st, F.d_img, F.d_seg, (uint32_t*)models.p, (NSum*)ns.p, F.d_nsoff,
-                               d_streams, d_stream_len, d_status, g->d_bins);
-        }
-        else if (waves >= 8) { g->last_kernel = "lep_encode_v3_kernel<8>"; LEP_LAUNCH_ENC3(8); }
-        else { g->last_kernel = "lep_encode_v3_kernel<4>"; LEP_LAUNCH_ENC3(4); }
+        const int rc = enc.split_phase ? launch_enc5(g, F.d_img, F.d_seg, F.d_nsoff, nseg, d_streams, d_stream_len, d_status, st) : kEnc5NoMemory;
+        if (rc && rc != kEnc5NoMemory) return rc;
+        if (!rc) {}
+        else if (enc.waves == 2) { g->last_kernel = "lep_encode_v3x2_kernel"; LEP_LAUNCH_ENC3(lep_encode_v3x2_kernel, 128); }
+        else if (enc.waves >= 8) { g->last_kernel = "lep_encode_v3_kernel<8>"; LEP_LAUNCH_ENC3((lep_encode_v3_kernel<8>), 64); }
+        else { g->last_kernel = "lep_encode_v3_kernel<4>"; LEP_LAUNCH_ENC3((lep_encode_v3_kernel<4>), 64); }
 #undef LEP_LAUNCH_ENC3
     }
     HIPCHK(g, hipGetLastError());
@@ -1223,9 +1165,7 @@ int lep_gpu_create(int device, lep_gpu** out) {
     lep_gpu* g = new lep_gpu;
     g->device = device;
     if (const char* e = getenv("LEP_DEC_WAVES")) g->dec_waves = atoi(e) == 4 ? 4 : (atoi(e) == 8 ? 8 : 0);
-    if (const char* e = getenv("LEP_ENC_WAVES")) g->enc_waves = atoi(e) == 4 ? 4 : (atoi(e) == 8 ? 8 : (atoi(e) == 2 ? 2 : 0));
-    if (const char* e = getenv("LEP_ENC_PAIR_MAX")) g->enc_pair_max = atoi(e);
-    if (const char* e = getenv("LEP_ENC5_MIN")) g->enc5_min = atoi(e);
+    lep5::enc5_options_from_env(&g->opt);
     if (const char* e = getenv("LEP_HUFFPROG_PIPELINE")) g->huffprog_pipeline = atoi(e);
     if (const char* e = getenv("LEP_HUFFPROG_PIPELINE_MAX")) g->huffprog_pipeline_max = atoi(e);
     if (const char* e = getenv("LEP_HUFFDEC_SIMT_BITS")) g->simt_sub_bits = std::max(0, atoi(e));
@@ -1238,16 +1178,6 @@ int lep_gpu_create(int device, lep_gpu** out) {
     if (const char* e = getenv("LEP_HUFFPROGDEC_RST")) g->huffprogdec_rst = atoi(e) != 0;
     if (const char* e = getenv("LEP_HUFFPROGDEC_RST_FLOOR")) g->huffprogdec_rst_floor = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("LEP_HUFFPROG_SPLIT")) g->huffprog_split = atoi(e) != 0;
-    if (const char* e = getenv("LEP_ENC5_WAVES")) g->enc5_waves = atoi(e) == 1 ? 1 : 2;
-    if (const char* e = getenv("LEP_ENC5_FOLD_APART")) g->enc5_fold_apart = atoi(e);
-    if (const char* e = getenv("LEP_ENC5_GATHER_WGS")) g->enc5_gather_wgs = atoi(e);
-    if (const char* e = getenv("LEP_ENC5_PARTS")) { g->enc5_parts = atoi(e); g->enc5_parts_given = true; }
-    if (const char* e = getenv("LEP_ENC5_WCHUNKS")) g->enc5_wchunks = atoi(e);
-    if (const char* e = getenv("LEP_ENC5_WLANES")) g->enc5_wlanes = atol(e);
-    if (const char* e = getenv("LEP_ENC5_WMAXSEG")) g->enc5_wmaxseg = atoi(e);
-    if (const char* e = getenv("LEP_ENC5_WSCHED")) g->enc5_wsched = !strcmp(e, "lane") ? 0 : !strcmp(e, "after") ? 1 : !strcmp(e, "beside") ? 2 : std::min(std::max(atoi(e), 0), 2);
-    if (const char* e = getenv("LEP_ENC5_WPARTCHUNKS")) { const int c = atoi(e); g->enc5_wpartchunks = 1; while (g->enc5_wpartchunks * 2 <= std::min(c, 32)) g->enc5_wpartchunks *= 2; }
-    if (const char* e = getenv("LEP_ENC5_SCRATCH_MAX")) g->enc5_scratch_max = (size_t)strtoull(e, nullptr, 10);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= device) { delete g; return LEP_GPU_ERROR; }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&g->stream) != hipSuccess ||
@@ -1975,7 +1905,7 @@ int lep_gpu_debug_write_bins(lep_gpu* g, int form, int parts, int chunks, int ns
     }
     if (!ok) { g->err = "lep_gpu_debug_write_bins: arguments out of range"; return LEP_ASSERTION_FAILURE; }
     HIPCHK(g, hipSetDevice(g->device));
-    const int K = form == LEP_DEBUG_WRITE_STITCHED ? chunks : form == LEP_DEBUG_WRITE_PART_CHUNKS ? parts * chunks : 0;
+    const lep5::Enc5WriterPlan W = lep5::enc5_writer_form(form, nseg, parts, chunks);
     constexpr uint32_t kSegArena = 1024;   // [kMaxParts] Ckpt5 | WriterState5
     static_assert(lep5::kMaxParts * sizeof(lep5::Ckpt5) + sizeof(lep5::WriterState5) <= kSegArena, "a segment's checkpoints and writer state");
     std::vector<lep5::SegPlan5> plans((size_t)nseg);
@@ -2005,7 +1935,7 @@ int lep_gpu_debug_write_bins(lep_gpu* g, int form, int parts, int chunks, int ns
         if (nbins[s]) memcpy(h_bins.data() + plans[(size_t)s].bins_off, bins + first[(size_t)s], (size_t)nbins[s] * 2);
     DebugDev dev;
     lep5::SegPlan5* d_plans; SegDev* d_segs; uint8_t *d_arena, *d_out; uint16_t* d_list; lep5::WChunk5* d_recs; uint32_t *d_len, *d_nb; int32_t* d_status;
-    const size_t list_bytes = (size_t)total * 2 + 256, rec_bytes = (size_t)nseg * (size_t)std::max(K, 1) * sizeof(lep5::WChunk5);
+    const size_t list_bytes = (size_t)total * 2 + 256, rec_bytes = (size_t)nseg * (size_t)std::max(W.records, 1) * sizeof(lep5::WChunk5);
     HIPCHK(g, dev.get((void**)&d_plans, plans.size() * sizeof(lep5::SegPlan5)));
     HIPCHK(g, dev.get((void**)&d_segs, segs.size() * sizeof(SegDev)));
     HIPCHK(g, dev.get((void**)&d_arena, h_arena.size()));
@@ -2026,6 +1956,7 @@ int lep_gpu_debug_write_bins(lep_gpu* g, int form, int parts, int chunks, int ns
     HIPCHK(g, hipMemsetAsync(d_status, 0x7f, (size_t)nseg * 4, st));
     // part p's bins of every segment (all of them where the form has no parts)
     auto send_part = [&](int p) -> int {
+        if (p == parts) return 0;
         if (!in_parts || parts == 1) { HIPCHK(g, hipMemcpyAsync(d_list, h_bins.data(), (size_t)total * 2, hipMemcpyHostToDevice, st)); return 0; }
         for (int s = 0; s < nseg; ++s) {
             const uint32_t b0 = part_first[(size_t)s * parts + p], b1 = p + 1 < parts ? part_first[(size_t)s * parts + p + 1] : nbins[s];
@@ -2035,36 +1966,12 @@ int lep_gpu_debug_write_bins(lep_gpu* g, int form, int parts, int chunks, int ns
         if (p + 1 == parts) HIPCHK(g, hipMemcpyAsync(d_plans, plans_last.data(), plans_last.size() * sizeof(lep5::SegPlan5), hipMemcpyHostToDevice, st));
         return 0;
     };
-    const int groups = (nseg + 63) / 64;
-    if (form == LEP_DEBUG_WRITE_LANE) {
-        for (int part = 0; part < parts; ++part) {
-            if (int rc = send_part(part)) return rc;
-            hipLaunchKernelGGL(lep_enc5_write_kernel, dim3(groups), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, d_out,
-                               d_len, d_status, d_nb, d_arena, part, parts);
-        }
-    } else if (form == LEP_DEBUG_WRITE_STITCHED) {
-        if (int rc = send_part(0)) return rc;
-        const int lane_groups = (int)(((long)nseg * K + 63) / 64);
-#define LEP_WCHUNK(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, K, d_recs, d_out, d_len, d_status, d_nb)
-        LEP_WCHUNK(0, lane_groups); LEP_WCHUNK(1, groups); LEP_WCHUNK(2, lane_groups); LEP_WCHUNK(3, groups);
-#undef LEP_WCHUNK
-    } else {
-        const int c = chunks, lane_groups = (int)(((long)nseg * c + 63) / 64);
-#define LEP_WPART(PHASE, GRID) hipLaunchKernelGGL((lep_enc5_wchunk_part_kernel<PHASE>), dim3(GRID), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, \
-                                                  parts, c, part, d_recs, d_out, (const uint8_t*)d_arena, d_status, d_nb)
-        for (int part = 0; part < parts; ++part) {
-            if (int rc = send_part(part)) return rc;
-            LEP_WPART(0, lane_groups); LEP_WPART(1, groups); LEP_WPART(2, lane_groups);
-        }
-#undef LEP_WPART
-        hipLaunchKernelGGL((lep_enc5_wchunk_kernel<3>), dim3(groups), dim3(64), 0, st, (const lep5::SegPlan5*)d_plans, (const uint16_t*)d_list, (const SegDev*)d_segs, nseg, K, d_recs,
-                           d_out, d_len, d_status, d_nb);
-    }
+    if (int rc = launch_enc5_writer(W, d_plans, d_list, d_segs, nseg, d_recs, d_arena, d_out, d_len, d_status, d_nb, st, send_part)) return rc;
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipMemcpyAsync(arena_out, d_out, arena_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(g, hipMemcpyAsync(stream_len, d_len, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(g, hipMemcpyAsync(status, d_status, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
-    if (wchunks && K) HIPCHK(g, hipMemcpyAsync(wchunks, d_recs, rec_bytes, hipMemcpyDeviceToHost, st));
+    if (wchunks && W.records) HIPCHK(g, hipMemcpyAsync(wchunks, d_recs, rec_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(g, hipStreamSynchronize(st));
     return 0;
 }

@@ -29,7 +29,8 @@ def asm(src, out):
             kernels[cur] = "\n".join(body)
             cur = None
         elif t and not t.startswith(";") and not t.startswith("."):
-            body.append(re.sub(r"\s*;.*$", "", t))
+            # (a block label carries the function's number in the file, .LBB<function>_<block>: it moves when host code instantiates the kernels in another order)
+            body.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*$", "", t)))
     return kernels
 
 
