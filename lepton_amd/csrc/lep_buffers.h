@@ -1,14 +1,14 @@
-// lep_buffers.h -- what the host runtime (lep_gpu.hip, lep_batch.hip) keeps its memory in: a grow-only device buffer, a grow-only
-// pinned host buffer, and the layout of a packed descriptor block.  A buffer owns its pointer and its capacity together: both change
-// in set() and nowhere else, so a capacity never outlives its allocation (the next allocation may fail).
+// lep_buffers.h -- what the host runtime (lep_gpu.hip, lep_batch.hip) keeps its memory in: a grow-only device buffer and a grow-only
+// pinned host buffer (the layout of a packed descriptor block, and the block: lep_block.h).  A buffer owns its pointer and its capacity
+// together: both change in set() and nowhere else, so a capacity never outlives its allocation (the next allocation may fail).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
-namespace lepbuf {
+#include "lep_block.h"
 
-inline size_t round_up(size_t v, size_t align = 256) { return (v + align - 1) & ~(align - 1); }   // (align: a power of two)
+namespace lepbuf {
 
 // An owned virtual address range with physical chunks mapped into its front (lep_gpu.hip "workspaces": the codec object's large
 // buffers; the chunks come from and go back to that object's pool).  Empty for every other buffer.
@@ -68,19 +68,6 @@ struct PinBuf {
         if (e == hipSuccess) set(q, need + head);
         return e;
     }
-};
-
-// A packed block of arrays: add<T>(n) appends n elements at the next multiple of `align` and returns their offset; bytes() is where
-// the last part ends, padded() that rounded up to 256.
-struct Layout {
-    size_t end = 0;
-    template <class T> size_t add(size_t n, size_t align = 256) {
-        const size_t off = round_up(end, align);
-        end = off + n * sizeof(T);
-        return off;
-    }
-    size_t bytes() const { return end; }
-    size_t padded() const { return round_up(end); }
 };
 
 }  // namespace lepbuf

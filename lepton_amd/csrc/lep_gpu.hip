@@ -689,10 +689,9 @@ struct lep_gpu {
     uint32_t* d_bins = nullptr;
     std::vector<uint32_t> h_bins;
     struct Staging { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
-    Staging staging[16];                // pinned ring for descriptor uploads (upload()): nothing on a launch path waits for its stream
-    int staging_next = 0;
+    Staging staging[16];                // pinned ring of staged descriptor blocks (stage()): a slot per block, at most five blocks per call (a
+    int staging_next = 0;               // progressive write or decode that holds every kind of scan); nothing on a launch path waits for its stream
     std::vector<void*> staging_retired;
-    lepbuf::PinBuf<char> h_huffprog[2];   // pinned staging of W_HUFFPROG: the upload does not wait for the stream
     int huffprog_turn = 0;   // the two sets are used in turn: at most two launches are ever in flight (lep_batch.hip queues chunk k+1 before it fetches chunk k)
 };
 
@@ -770,7 +769,7 @@ static int vmm_ensure(lep_gpu* g, Workspace& w, size_t need, bool may_release) {
     lepbuf::VRange& b = w.v;
     const size_t want = ((need + V.chunk - 1) / V.chunk) * V.chunk;
     if (want > b.reserved) {   // a longer address range (what the workspace held is not kept: every launch fills it anew)
-        // The old range is unmapped and freed here, and launches do not wait for their streams any more (upload() ring; lep_batch.hip
+        // The old range is unmapped and freed here, and launches do not wait for their streams any more (stage() ring; lep_batch.hip
         // queues chunk k + 1 while chunk k's kernels run): a kernel still in flight would lose its mapping under its feet.  hipFree
         // used to synchronise implicitly; this path has to ask.  Rare: growth inside the reservation maps behind.
         if (b.mapped) (void)hipDeviceSynchronize();
@@ -955,13 +954,24 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
     return 0;
 }
 
-// Descriptor bytes to the device, ordered on `st`, WITHOUT waiting for what is queued on it: the bytes are copied into a pinned buffer
-// of the codec's own (the caller's arrays may go away) and go up from there.  A launch function that waited for its stream here --
-// hipMemcpyAsync from pageable memory, then hipStreamSynchronize -- waited for every kernel queued in front of it: in the batch
-// decompressor that was the decode kernel of the chunk being launched (1 s), during which the host could have staged the next chunk
-// (kernel trace of round 4: the decoder idle ~0.1 s per chunk).  A ring slot is reused sixteen uploads later; its event says when its
-// copy has run.
-static int upload(lep_gpu* g, void* dst, const void* src, size_t n, hipStream_t st) {
+// The sizes of the descriptor types that are staged, as tests/test_stage_block.py walks them: a type that changes size stops the build here.
+#define LEP_STAGED(T, N) static_assert(sizeof(T) == N, "a staged descriptor changed size: tests/test_stage_block.py WORKSPACES and tests/emu/stage_block_probe.cc ELEM_SIZES name it")
+LEP_STAGED(ImageDev, 2208); LEP_STAGED(SegDev, 32); LEP_STAGED(lep_huff_image, 4272); LEP_STAGED(lep_huff_segment, 40); LEP_STAGED(lephuff::SimtEncSeg, 40);
+LEP_STAGED(lephuff::SimtEncWave, 8); LEP_STAGED(lepsamples::PlaneRec, 176); LEP_STAGED(lep_huffprog_image, 168); LEP_STAGED(lep_huffprog_scan, 4184);
+LEP_STAGED(lephuff::ProgSimtScan, 48); LEP_STAGED(lephuff::ProgSimtWave, 8); LEP_STAGED(lephuff::ProgSimtRegion, 24); LEP_STAGED(lep_huffprogdec_scan, 5696);
+LEP_STAGED(lephuff::ProgDeps, 16); LEP_STAGED(lephuff::ProgRstScan, 16); LEP_STAGED(lephuff::ProgRstOut, 24); LEP_STAGED(lep_huffdec_image, 5552);
+LEP_STAGED(lephuff::SimtImage, 36); LEP_STAGED(lephuff::SimtWave, 8); LEP_STAGED(lephuff::SimtSub, 20); LEP_STAGED(lephuff::SimtPlace, 12); LEP_STAGED(lephuff::SimtSlots, 32);
+
+// The one way descriptors get to the device: a block (lep_block.h: these arrays, at these offsets) into workspace `ws`, ordered on `st`,
+// WITHOUT waiting for what is queued on it.  The workspace is ensured for the whole block; the block's image is packed into a pinned
+// slot of the codec's own ring (the caller's arrays, and the launch function's vectors, may go away) and goes up from there as ONE
+// copy.  A launch function that waited for its stream here -- hipMemcpyAsync from pageable memory, then hipStreamSynchronize -- waited
+// for every kernel queued in front of it: in the batch decompressor that was the decode kernel of the chunk being launched (1 s),
+// during which the host could have staged the next chunk (kernel trace of round 4: the decoder idle ~0.1 s per chunk).  A slot is
+// reused sixteen blocks later -- a call stages at most five -- and its event says when its copy has run.
+static int stage(lep_gpu* g, Workspace& ws, const lepbuf::Block& B, hipStream_t st) {
+    if (int rc = ensure(g, ws, B.padded())) return rc;
+    const size_t n = B.upload_bytes();
     if (!n) return 0;
     lep_gpu::Staging& sl = g->staging[g->staging_next];
     g->staging_next = (g->staging_next + 1) % 16;
@@ -976,8 +986,8 @@ static int upload(lep_gpu* g, void* dst, const void* src, size_t n, hipStream_t 
         HIPCHK(g, hipHostMalloc(&sl.host, want, hipHostMallocDefault));
         sl.cap = want;
     }
-    memcpy(sl.host, src, n);
-    HIPCHK(g, hipMemcpyAsync(dst, sl.host, n, hipMemcpyHostToDevice, st));
+    B.pack((char*)sl.host);
+    HIPCHK(g, hipMemcpyAsync(ws.p, sl.host, n, hipMemcpyHostToDevice, st));
     HIPCHK(g, hipEventRecord(sl.ev, st));
     sl.used = true;
     return 0;
@@ -1069,17 +1079,14 @@ static int launch_front(lep_gpu* g, bool dec, const lep_image_desc* images, int 
     Workspace &models = g->ws[lep_gpu::W_MODELS + g->cur], &ns = g->ws[lep_gpu::W_NS + g->cur];
     if (int rc = ensure(g, models, (size_t)nseg * kModelStride * 4)) return rc;
     if (int rc = ensure(g, ns, (size_t)ns_total * sizeof(NSum) + 16)) return rc;
-    lepbuf::Layout L;
-    const size_t o_img = L.add<ImageDev>((size_t)nimg), o_seg = L.add<SegDev>((size_t)nseg), o_ns = L.add<uint64_t>((size_t)nseg), o_bins = L.add<uint32_t>((size_t)nseg);
-    if (int rc = ensure(g, g->ws[lep_gpu::W_META + g->cur], L.bytes())) return rc;
-    char* meta = g->ws[lep_gpu::W_META + g->cur].at<char>(0);
-    if (int rc = upload(g, meta + o_img, himg.data(), nimg * sizeof(ImageDev), st)) return rc;      // (the host vectors above go out of scope:
-    if (int rc = upload(g, meta + o_seg, hseg.data(), nseg * sizeof(SegDev), st)) return rc;        //  upload() keeps a copy)
-    if (int rc = upload(g, meta + o_ns, hns.data(), nseg * sizeof(uint64_t), st)) return rc;
-    g->d_bins = (uint32_t*)(meta + o_bins);
+    lepbuf::Block B;
+    const size_t o_img = B.add(himg.data(), (size_t)nimg), o_seg = B.add(hseg.data(), (size_t)nseg), o_ns = B.add(hns.data(), (size_t)nseg), o_bins = B.add<uint32_t>((size_t)nseg);
+    Workspace& meta = g->ws[lep_gpu::W_META + g->cur];
+    if (int rc = stage(g, meta, B, st)) return rc;
+    g->d_bins = meta.at<uint32_t>(o_bins);
     g->h_bins.assign(nseg, 0);
     g->nstage = 0;
-    out->d_img = (const ImageDev*)(meta + o_img); out->d_seg = (const SegDev*)(meta + o_seg); out->d_nsoff = (const uint64_t*)(meta + o_ns);
+    out->d_img = meta.at<const ImageDev>(o_img); out->d_seg = meta.at<const SegDev>(o_seg); out->d_nsoff = meta.at<const uint64_t>(o_ns);
     out->d_models = (uint32_t*)models.p; out->d_ns = (NSum*)ns.p;
     return 0;
 }
@@ -1210,7 +1217,6 @@ static void release_device_side(lep_gpu* g) {
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    for (auto& h : g->h_huffprog) (void)h.release();
     for (lep_gpu::Staging& sl : g->staging) { if (sl.host) (void)hipHostFree(sl.host); if (sl.ev) (void)hipEventDestroy(sl.ev); sl = lep_gpu::Staging(); }
     for (void* p : g->staging_retired) (void)hipHostFree(p);
     g->staging_retired.clear();
@@ -1346,38 +1352,31 @@ int lep_gpu_huffman_encode_device(lep_gpu* g, const lep_huff_image* images, int 
     if (nseg <= 0) return 0;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    lepbuf::Layout D;
-    D.add<lep_huff_image>((size_t)nimg);
-    const size_t o_seg = D.add<lep_huff_segment>((size_t)nseg);
     const int set = g->cur & 1;                            // (the arena set the caller chose: two launches on two streams never share descriptors or scratch)
     Workspace &huff = g->ws[lep_gpu::W_HUFF + set], &huffenc = g->ws[lep_gpu::W_HUFFENC + set];
-    if (int rc = ensure(g, huff, D.bytes())) return rc;
     // which segments the lane-per-unit kernels take, and what they need: lep_huff_simt.h's plan; the wavefront-per-segment kernel keeps the others
     std::vector<lep_huff_segment> sv(segs, segs + nseg);
     lephuff::SimtEncPlan plan;
     lephuff::simt_enc_plan(reinterpret_cast<const lephuff::HuffImage*>(images), nimg, reinterpret_cast<lephuff::HuffSegment*>(sv.data()), nseg, g->huffenc_simt != 0, &plan);
     const auto& es = plan.es; const auto& waves = plan.waves;
-    lepbuf::Layout L;
-    const size_t o_es = L.add<lephuff::SimtEncSeg>(es.size()), o_wv = L.add<lephuff::SimtEncWave>(waves.size()),
-                 o_ub = L.add<uint32_t>(plan.nunits * 2),   // (units: bit counts / positions, and the plain prefix sum of scans with restart intervals)
-                 o_sc = L.add<uint8_t>(plan.scratch_bytes);
-    if (!es.empty()) { if (int rc = ensure(g, huffenc, L.padded())) return rc; }
-    if (int rc = upload(g, huff, images, nimg * sizeof(lep_huff_image), st)) return rc;           // (the caller's arrays and ours may go away)
-    if (int rc = upload(g, huff.at<char>(o_seg), sv.data(), nseg * sizeof(lep_huff_segment), st)) return rc;
-    char* eb = huffenc.at<char>(0);
+    lepbuf::Block D, E;
+    const size_t o_img = D.add(images, (size_t)nimg), o_seg = D.add(sv.data(), (size_t)nseg);
+    const size_t o_es = E.add(es.data(), es.size()), o_wv = E.add(waves.data(), waves.size()),
+                 o_ub = E.add<uint32_t>(plan.nunits * 2),   // (units: bit counts / positions, and the plain prefix sum of scans with restart intervals)
+                 o_sc = E.add<uint8_t>(plan.scratch_bytes);
+    if (int rc = stage(g, huff, D, st)) return rc;
     if (!es.empty()) {
-        if (int rc = upload(g, eb + o_es, es.data(), es.size() * sizeof(lephuff::SimtEncSeg), st)) return rc;
-        if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::SimtEncWave), st)) return rc;
-        hipLaunchKernelGGL(lep_zero_kernel, dim3(8192), dim3(256), 0, st, (uint4*)(eb + o_sc), plan.scratch_bytes / 16);   // (buf_bytes are multiples of 16)
+        if (int rc = stage(g, huffenc, E, st)) return rc;
+        hipLaunchKernelGGL(lep_zero_kernel, dim3(8192), dim3(256), 0, st, huffenc.at<uint4>(o_sc), plan.scratch_bytes / 16);   // (buf_bytes are multiples of 16)
     }
-    const lephuff::HuffImage* di = huff.at<lephuff::HuffImage>(0);
-    const lephuff::HuffSegment* ds = huff.at<lephuff::HuffSegment>(o_seg);
+    const lephuff::HuffImage* di = huff.at<const lephuff::HuffImage>(o_img);
+    const lephuff::HuffSegment* ds = huff.at<const lephuff::HuffSegment>(o_seg);
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (!es.empty()) {
-        lephuff::SimtEncSeg* des = (lephuff::SimtEncSeg*)(eb + o_es);
-        const lephuff::SimtEncWave* dwv = (const lephuff::SimtEncWave*)(eb + o_wv);
-        uint32_t* dub = (uint32_t*)(eb + o_ub);
-        uint8_t* dsc = (uint8_t*)(eb + o_sc);
+        lephuff::SimtEncSeg* des = huffenc.at<lephuff::SimtEncSeg>(o_es);
+        const lephuff::SimtEncWave* dwv = huffenc.at<const lephuff::SimtEncWave>(o_wv);
+        uint32_t* dub = huffenc.at<uint32_t>(o_ub);
+        uint8_t* dsc = huffenc.at<uint8_t>(o_sc);
         hipLaunchKernelGGL((lep_huffman_simt_encode_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, des, dwv, dub, dsc);
         hipLaunchKernelGGL(lep_huffman_simt_encode_place_kernel, dim3((unsigned)es.size()), dim3(64), 0, st, di, ds, des, dub, dub + plan.nunits);
         hipLaunchKernelGGL((lep_huffman_simt_encode_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, des, dwv, dub, dsc);
@@ -1406,10 +1405,11 @@ int lep_gpu_pack_device(lep_gpu* g, const uint8_t* d_src, const uint64_t* src_of
     HIPCHK(g, hipSetDevice(g->device));
     if (n == 0) { HIPCHK(g, hipMemsetAsync(d_dst_off, 0, sizeof(uint64_t), st)); return 0; }
     Workspace& ws = g->ws[lep_gpu::W_PACK + (g->cur & 1)];
-    if (int rc = ensure(g, ws, (size_t)n * sizeof(uint64_t))) return rc;
-    if (int rc = upload(g, ws.p, src_off, (size_t)n * sizeof(uint64_t), st)) return rc;
+    lepbuf::Block B;
+    const size_t o_src = B.add(src_off, (size_t)n);
+    if (int rc = stage(g, ws, B, st)) return rc;
     hipLaunchKernelGGL(lep_pack_offsets_kernel, dim3(1), dim3(leppack::kScanLanes), 0, st, d_len, n, d_dst_off);
-    hipLaunchKernelGGL(lep_pack_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, ws.at<uint64_t>(0), d_len, n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
+    hipLaunchKernelGGL(lep_pack_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, ws.at<const uint64_t>(o_src), d_len, n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
     HIPCHK(g, hipGetLastError());
     g->last_kernel = "lep_pack_{offsets,copy}_kernel";
     return 0;
@@ -1428,17 +1428,13 @@ int lep_gpu_pack_window_device(lep_gpu* g, const uint8_t* d_src, const uint64_t*
     HIPCHK(g, hipSetDevice(g->device));
     if (n == 0) { HIPCHK(g, hipMemsetAsync(d_dst_off, 0, sizeof(uint64_t), st)); return 0; }
     Workspace& ws = g->ws[lep_gpu::W_PACK + (g->cur & 1)];
-    lepbuf::Layout L;
-    L.add<uint64_t>((size_t)n);
-    const size_t o_skip = L.add<uint32_t>((size_t)n), o_take = L.add<uint32_t>((size_t)n), o_wlen = L.add<uint32_t>((size_t)n);
-    if (int rc = ensure(g, ws, L.bytes())) return rc;
-    if (int rc = upload(g, ws.p, src_off, (size_t)n * sizeof(uint64_t), st)) return rc;
-    if (int rc = upload(g, ws.at<char>(o_skip), win_skip, (size_t)n * sizeof(uint32_t), st)) return rc;
-    if (int rc = upload(g, ws.at<char>(o_take), win_take, (size_t)n * sizeof(uint32_t), st)) return rc;
-    hipLaunchKernelGGL(lep_pack_window_offsets_kernel, dim3(1), dim3(leppack::kScanLanes), 0, st, d_len, (const uint32_t*)ws.at<uint32_t>(o_skip),
-                       (const uint32_t*)ws.at<uint32_t>(o_take), n, ws.at<uint32_t>(o_wlen), d_dst_off);
-    hipLaunchKernelGGL(lep_pack_window_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, (const uint64_t*)ws.at<uint64_t>(0), (const uint32_t*)ws.at<uint32_t>(o_skip),
-                       (const uint32_t*)ws.at<uint32_t>(o_wlen), n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
+    lepbuf::Block B;
+    const size_t o_src = B.add(src_off, (size_t)n), o_skip = B.add(win_skip, (size_t)n), o_take = B.add(win_take, (size_t)n), o_wlen = B.add<uint32_t>((size_t)n);
+    if (int rc = stage(g, ws, B, st)) return rc;
+    hipLaunchKernelGGL(lep_pack_window_offsets_kernel, dim3(1), dim3(leppack::kScanLanes), 0, st, d_len, ws.at<const uint32_t>(o_skip),
+                       ws.at<const uint32_t>(o_take), n, ws.at<uint32_t>(o_wlen), d_dst_off);
+    hipLaunchKernelGGL(lep_pack_window_copy_kernel, dim3((unsigned)n), dim3(64), 0, st, d_src, ws.at<const uint64_t>(o_src), ws.at<const uint32_t>(o_skip),
+                       ws.at<const uint32_t>(o_wlen), n, d_dst, d_dst_cap, (const uint64_t*)d_dst_off);
     HIPCHK(g, hipGetLastError());
     g->last_kernel = "lep_pack_window_{offsets,copy}_kernel";
     return 0;
@@ -1479,15 +1475,12 @@ int lep_gpu_samples_device(lep_gpu* g, const lep_image_desc* images, int nimg, i
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
     const int nplanes = (int)recs.size();
-    const size_t rec_bytes = recs.size() * sizeof(lepsamples::PlaneRec), first_bytes = first.size() * sizeof(uint32_t);
-    std::vector<char> table(rec_bytes + first_bytes);   // one upload: the records, the unit counts behind them
-    memcpy(table.data(), recs.data(), rec_bytes);
-    memcpy(table.data() + rec_bytes, first.data(), first_bytes);
     Workspace& ws = g->ws[lep_gpu::W_SAMPLES + (g->cur & 1)];
-    if (int rc = ensure(g, ws, table.size())) return rc;
-    if (int rc = upload(g, ws.p, table.data(), table.size(), st)) return rc;
-    const lepsamples::PlaneRec* d_recs = ws.at<lepsamples::PlaneRec>(0);
-    const uint32_t* d_first = ws.at<uint32_t>(rec_bytes);
+    lepbuf::Block B;   // the records, the unit counts behind them
+    const size_t o_recs = B.add(recs.data(), recs.size()), o_first = B.add(first.data(), first.size(), 4);
+    if (int rc = stage(g, ws, B, st)) return rc;
+    const lepsamples::PlaneRec* d_recs = ws.at<const lepsamples::PlaneRec>(o_recs);
+    const uint32_t* d_first = ws.at<const uint32_t>(o_first);
     const unsigned groups = (total + lepsamples::kWavesPerGroup - 1) / lepsamples::kWavesPerGroup;
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (scale == 1) hipLaunchKernelGGL(lep_samples_kernel, dim3(groups), dim3(64 * lepsamples::kWavesPerGroup), 0, st, d_recs, d_first, nplanes);
@@ -1530,20 +1523,16 @@ int lep_gpu_huffman_progressive_decode_device(lep_gpu* g, const lep_huffprogdec_
 // the scans of files that have a scan of lep_huffprogdec_rst.h's: dependency level after dependency level on the stream -- the pieces of
 // the scans of that form, one launch of the window form's level-by-level kernel for the others -- and the reduce step behind the last
 static int progdec_launch_by_level(lep_gpu* g, const lephuff::ProgDecPlan::Pieces& c, lep_huffdec_row* d_rows, hipStream_t st, bool time_from_here) {
-    lepbuf::Layout L;
-    L.add<lep_huffprogdec_scan>(c.plain.size());
-    const size_t o_rst = L.add<lep_huffprogdec_scan>(c.rst.size()), o_plan = L.add<lephuff::ProgRstScan>(c.plans.size()), o_out = L.add<lephuff::ProgRstOut>((size_t)c.pieces);
-    if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGRST], L.padded())) return rc;
-    char* base = g->ws[lep_gpu::W_HUFFPROGRST].at<char>(0);
-    if (!c.plain.empty()) HIPCHK(g, hipMemcpyAsync(base, c.plain.data(), c.plain.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_rst, c.rst.data(), c.rst.size() * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_plan, c.plans.data(), c.plans.size() * sizeof(lephuff::ProgRstScan), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipStreamSynchronize(st));   // (the plan's vectors are the copies' sources)
+    lepbuf::Block B;
+    const size_t o_plain = B.add(c.plain.data(), c.plain.size()), o_rst = B.add(c.rst.data(), c.rst.size()), o_plan = B.add(c.plans.data(), c.plans.size()),
+                 o_out = B.add<lephuff::ProgRstOut>((size_t)c.pieces);
+    Workspace& ws = g->ws[lep_gpu::W_HUFFPROGRST];
+    if (int rc = stage(g, ws, B, st)) return rc;
     if (time_from_here) HIPCHK(g, hipEventRecord(g->ev0, st));
-    const lephuff::ProgDecScan* d_plain = (const lephuff::ProgDecScan*)base;
-    const lephuff::ProgDecScan* d_rst = (const lephuff::ProgDecScan*)(base + o_rst);
-    const lephuff::ProgRstScan* d_plan = (const lephuff::ProgRstScan*)(base + o_plan);
-    lephuff::ProgRstOut* d_out = (lephuff::ProgRstOut*)(base + o_out);
+    const lephuff::ProgDecScan* d_plain = ws.at<const lephuff::ProgDecScan>(o_plain);
+    const lephuff::ProgDecScan* d_rst = ws.at<const lephuff::ProgDecScan>(o_rst);
+    const lephuff::ProgRstScan* d_plan = ws.at<const lephuff::ProgRstScan>(o_plan);
+    lephuff::ProgRstOut* d_out = ws.at<lephuff::ProgRstOut>(o_out);
     for (int lv = 0; lv < 64; ++lv) {
         const int np = c.pcut[lv + 1] - c.pcut[lv], nr = c.rcut[lv + 1] - c.rcut[lv];
         if (np > 0)
@@ -1562,21 +1551,16 @@ static int progdec_launch_by_level(lep_gpu* g, const lephuff::ProgDecPlan::Piece
 // progressive scans of files without that form: all levels as ONE pipelined launch, or level after level (stream order is the dependency)
 static int progdec_launch_scans(lep_gpu* g, const lephuff::ProgDecPlan::Levels& b, lep_huffdec_row* d_rows, hipStream_t st) {
     const int nscan = (int)b.sorted.size();
-    lepbuf::Layout L;
-    L.add<lep_huffprogdec_scan>((size_t)nscan);
-    const size_t o_deps = L.add<lephuff::ProgDeps>((size_t)nscan), o_prog = L.add<uint32_t>((size_t)nscan + 1);   // (+ the ticket counter behind the progress words)
+    lepbuf::Block B;   // (the dependencies are read by the pipelined launch alone)
+    const size_t o_scan = B.add(b.sorted.data(), (size_t)nscan), o_deps = b.pipelined ? B.add(b.deps.data(), (size_t)nscan) : B.add<lephuff::ProgDeps>((size_t)nscan),
+                 o_prog = B.add<uint32_t>((size_t)nscan + 1);   // (+ the ticket counter behind the progress words)
     Workspace& progdec = g->ws[lep_gpu::W_HUFFPROGDEC];
-    if (int rc = ensure(g, progdec, L.bytes())) return rc;
-    HIPCHK(g, hipMemcpyAsync(progdec, b.sorted.data(), (size_t)nscan * sizeof(lep_huffprogdec_scan), hipMemcpyHostToDevice, st));
-    if (b.pipelined) {
-        HIPCHK(g, hipMemcpyAsync(progdec.at<char>(o_deps), b.deps.data(), (size_t)nscan * sizeof(lephuff::ProgDeps), hipMemcpyHostToDevice, st));
-        HIPCHK(g, hipMemsetAsync(progdec.at<char>(o_prog), 0, (size_t)nscan * 4 + 4, st));
-    }
-    HIPCHK(g, hipStreamSynchronize(st));
+    if (int rc = stage(g, progdec, B, st)) return rc;
+    if (b.pipelined) HIPCHK(g, hipMemsetAsync(progdec.at<char>(o_prog), 0, (size_t)nscan * 4 + 4, st));
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (b.pipelined) {
         hipLaunchKernelGGL(b.any_win ? lep_huffprogdec_win_pipelined_kernel : lep_huffman_progressive_pipelined_kernel, dim3(nscan), dim3(64), 0, st,
-                           progdec.at<const lephuff::ProgDecScan>(0), (lephuff::HuffDecRow*)d_rows,
+                           progdec.at<const lephuff::ProgDecScan>(o_scan), (lephuff::HuffDecRow*)d_rows,
                            progdec.at<const lephuff::ProgDeps>(o_deps), progdec.at<uint32_t>(o_prog), progdec.at<uint32_t>(o_prog) + nscan);
         HIPCHK(g, hipGetLastError());
         HIPCHK(g, hipEventRecord(g->ev1, st));
@@ -1588,7 +1572,7 @@ static int progdec_launch_scans(lep_gpu* g, const lephuff::ProgDecPlan::Levels& 
         const int n = b.cut[q + 1] - b.cut[q];
         if (n <= 0) continue;
         hipLaunchKernelGGL(b.any_win ? lep_huffprogdec_win_kernel : lep_huffman_progressive_decode_kernel, dim3(n), dim3(64), 0, st,
-                           progdec.at<const lephuff::ProgDecScan>(0) + b.cut[q], (lephuff::HuffDecRow*)d_rows);
+                           progdec.at<const lephuff::ProgDecScan>(o_scan) + b.cut[q], (lephuff::HuffDecRow*)d_rows);
     }
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
@@ -1605,19 +1589,11 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     if (nscan <= 0) return 0;
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
-    lepbuf::Layout D;
-    D.add<lep_huffprog_image>((size_t)nimg);
-    const size_t o_scan = D.add<lep_huffprog_scan>((size_t)nscan), total = D.bytes();
     const int turn = (g->huffprog_turn ^= 1);
-    if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROG + turn], total)) return rc;
-    char* const d_desc = g->ws[lep_gpu::W_HUFFPROG + turn].at<char>(0);
-    // descriptors through a pinned copy of this set (its previous user, two launches ago, has been waited for by then): the
-    // caller's arrays may go away, and nothing here waits for the kernels already queued on the stream
-    HIPCHK(g, g->h_huffprog[turn].ensure(total, total / 8));
-    char* const h_desc = g->h_huffprog[turn];
-    memcpy(h_desc, images, nimg * sizeof(lep_huffprog_image));
-    memcpy(h_desc + o_scan, scans, nscan * sizeof(lep_huffprog_scan));
-    lephuff::ProgScan* hs = reinterpret_cast<lephuff::ProgScan*>(h_desc + o_scan);
+    Workspace &prog = g->ws[lep_gpu::W_HUFFPROG + turn], &seq = g->ws[lep_gpu::W_HUFFSEQ + turn], &simt = g->ws[lep_gpu::W_HUFFPROGSIMT + turn];
+    std::vector<lephuff::ProgScan> hscan((size_t)nscan);   // the scans as the device gets them: `pad` is edited below, before the block is staged
+    memcpy(hscan.data(), scans, (size_t)nscan * sizeof(lep_huffprog_scan));
+    lephuff::ProgScan* hs = hscan.data();
     for (uint32_t& c : g->huffprog_forms) c = 0;
     std::vector<uint32_t> file_bound((size_t)nscan);
     for (int i = 0; i < nscan; ++i) { file_bound[(size_t)i] = hs[i].pad; hs[i].pad = 0; }   // (the caller's field; on the device it says which kernel owns the scan)
@@ -1640,16 +1616,12 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     }
     if (!seq_seg.empty()) {
         const size_t n = seq_seg.size();
-        lepbuf::Layout S;   // which | caps | byte counts | (16-byte aligned) end states
-        S.add<uint32_t>(n, 4);
-        const size_t o_cap = S.add<uint32_t>(n, 4), o_len = S.add<uint32_t>(n, 4), o_end = S.add<lep_huff_end>(n, 16);
-        if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFSEQ + turn], S.bytes())) return rc;
-        char* b = g->ws[lep_gpu::W_HUFFSEQ + turn].at<char>(0);
-        if (int rc = upload(g, b, seq_which.data(), n * 4, st)) return rc;
-        if (int rc = upload(g, b + o_cap, seq_cap.data(), n * 4, st)) return rc;
-        if (int rc = lep_gpu_huffman_encode_device(g, seq_img.data(), (int)n, seq_seg.data(), (int)n, d_out, (uint32_t*)(b + o_len), (lep_huff_end*)(b + o_end), st)) return rc;
-        hipLaunchKernelGGL(lep_huffprog_seq_lens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)b, (const uint32_t*)(b + o_cap), (const uint32_t*)(b + o_len),
-                           (const lephuff::HuffEnd*)(b + o_end), (int)n, d_out_len);
+        lepbuf::Block S;   // which | caps | byte counts | (16-byte aligned) end states
+        const size_t o_which = S.add(seq_which.data(), n, 4), o_cap = S.add(seq_cap.data(), n, 4), o_len = S.add<uint32_t>(n, 4), o_end = S.add<lep_huff_end>(n, 16);
+        if (int rc = stage(g, seq, S, st)) return rc;
+        if (int rc = lep_gpu_huffman_encode_device(g, seq_img.data(), (int)n, seq_seg.data(), (int)n, d_out, seq.at<uint32_t>(o_len), seq.at<lep_huff_end>(o_end), st)) return rc;
+        hipLaunchKernelGGL(lep_huffprog_seq_lens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, seq.at<const uint32_t>(o_which), seq.at<const uint32_t>(o_cap),
+                           seq.at<const uint32_t>(o_len), seq.at<const lephuff::HuffEnd>(o_end), (int)n, d_out_len);
         g->huffprog_forms[3] = (uint32_t)n;
         if ((int)n == nscan) { HIPCHK(g, hipGetLastError()); return 0; }
     }
@@ -1658,32 +1630,27 @@ int lep_gpu_huffman_progressive_encode_device(lep_gpu* g, const lep_huffprog_ima
     lephuff::prog_simt_plan(reinterpret_cast<const lephuff::ProgImage*>(images), nimg, hs, nscan, file_bound.data(), g->huffprog_simt != 0, g->huffprog_simt_rst != 0, &plan);
     const auto& ps = plan.ps; const auto& waves = plan.waves; const auto& regions = plan.regions;
     g->huffprog_forms[0] = plan.forms[0]; g->huffprog_forms[1] = plan.forms[1];
-    lepbuf::Layout L;
-    const size_t o_ps = L.add<lephuff::ProgSimtScan>(ps.size()), o_wv = L.add<lephuff::ProgSimtWave>(waves.size()), o_rg = L.add<lephuff::ProgSimtRegion>(regions.size()),
-                 o_un = L.add<uint32_t>(plan.nunits * lephuff::prog_simt_unit_words(plan.intervals)), o_sc = L.add<uint8_t>(plan.scratch_bytes);
+    lepbuf::Block D, E;
+    const size_t o_img = D.add(images, (size_t)nimg), o_scan = D.add(hs, (size_t)nscan);
+    const size_t o_ps = E.add(ps.data(), ps.size()), o_wv = E.add(waves.data(), waves.size()), o_rg = E.add(regions.data(), regions.size()),
+                 o_un = E.add<uint32_t>(plan.nunits * lephuff::prog_simt_unit_words(plan.intervals)), o_sc = E.add<uint8_t>(plan.scratch_bytes);
     g->huffprog_forms[2] = (uint32_t)((size_t)nscan - ps.size() - seq_seg.size());
-    if (!ps.empty()) { if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPROGSIMT + turn], L.padded())) return rc; }
-    HIPCHK(g, hipMemcpyAsync(d_desc, h_desc, total, hipMemcpyHostToDevice, st));
-    char* eb = g->ws[lep_gpu::W_HUFFPROGSIMT + turn].at<char>(0);
-    if (!ps.empty()) {
-        if (int rc = upload(g, eb + o_ps, ps.data(), ps.size() * sizeof(lephuff::ProgSimtScan), st)) return rc;
-        if (int rc = upload(g, eb + o_wv, waves.data(), waves.size() * sizeof(lephuff::ProgSimtWave), st)) return rc;
-        if (int rc = upload(g, eb + o_rg, regions.data(), regions.size() * sizeof(lephuff::ProgSimtRegion), st)) return rc;
-    }
-    const lephuff::ProgImage* di = (const lephuff::ProgImage*)d_desc;
-    const lephuff::ProgScan* ds = (const lephuff::ProgScan*)(d_desc + o_scan);
+    if (int rc = stage(g, prog, D, st)) return rc;
+    if (!ps.empty()) { if (int rc = stage(g, simt, E, st)) return rc; }
+    const lephuff::ProgImage* di = prog.at<const lephuff::ProgImage>(o_img);
+    const lephuff::ProgScan* ds = prog.at<const lephuff::ProgScan>(o_scan);
     HIPCHK(g, hipEventRecord(g->ev0, st));
     if (!ps.empty()) {
-        lephuff::ProgSimtScan* dps = (lephuff::ProgSimtScan*)(eb + o_ps);
-        const lephuff::ProgSimtWave* dwv = (const lephuff::ProgSimtWave*)(eb + o_wv);
-        uint32_t* dun = (uint32_t*)(eb + o_un);
-        uint8_t* dsc = (uint8_t*)(eb + o_sc);
+        lephuff::ProgSimtScan* dps = simt.at<lephuff::ProgSimtScan>(o_ps);
+        const lephuff::ProgSimtWave* dwv = simt.at<const lephuff::ProgSimtWave>(o_wv);
+        uint32_t* dun = simt.at<uint32_t>(o_un);
+        uint8_t* dsc = simt.at<uint8_t>(o_sc);
         uint32_t longest = 0;
         for (const lephuff::ProgSimtRegion& r : regions) longest = (uint32_t)std::max<uint64_t>(longest, r.bytes);
         const uint32_t chunk16 = 4096;   // 64 KB of a bit buffer per workgroup of the clearing kernel
         hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<false>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, plan.nunits, dsc);
         hipLaunchKernelGGL(lep_huffprog_simt_place_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, ds, dps, dun, plan.nunits);
-        hipLaunchKernelGGL(lep_huffprog_simt_assign_kernel, dim3((unsigned)(regions.size() + 63) / 64), dim3(64), 0, st, (const lephuff::ProgSimtRegion*)(eb + o_rg), (int)regions.size(), dps);
+        hipLaunchKernelGGL(lep_huffprog_simt_assign_kernel, dim3((unsigned)(regions.size() + 63) / 64), dim3(64), 0, st, simt.at<const lephuff::ProgSimtRegion>(o_rg), (int)regions.size(), dps);
         hipLaunchKernelGGL(lep_huffprog_simt_zero_kernel, dim3((unsigned)ps.size(), (longest / 16 + chunk16 - 1) / chunk16 + 1), dim3(256), 0, st, (const lephuff::ProgSimtScan*)dps, dsc, chunk16);
         hipLaunchKernelGGL((lep_huffprog_simt_units_kernel<true>), dim3((unsigned)waves.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dwv, dun, plan.nunits, dsc);
         hipLaunchKernelGGL(lep_huffprog_simt_stuff_kernel, dim3((unsigned)ps.size()), dim3(64), 0, st, di, ds, (const lephuff::ProgSimtScan*)dps, dsc, d_out, d_out_len);
@@ -1705,12 +1672,11 @@ int lep_gpu_huffman_decode_device(lep_gpu* g, const lep_huffdec_image* images, i
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
     Workspace& huffdec = g->ws[lep_gpu::W_HUFFDEC];
-    if (int rc = ensure(g, huffdec, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
-    HIPCHK(g, hipMemcpyAsync(huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipStreamSynchronize(st));   // the caller's array may go away
+    lepbuf::Block B;
+    const size_t o_img = B.add(images, (size_t)nimg);
+    if (int rc = stage(g, huffdec, B, st)) return rc;
     HIPCHK(g, hipEventRecord(g->ev0, st));
-    hipLaunchKernelGGL(lep_huffman_decode_kernel, dim3(nimg), dim3(64), 0, st, (const lephuff::HuffDecImage*)huffdec.p,
-                       (lephuff::HuffDecRow*)d_rows);
+    hipLaunchKernelGGL(lep_huffman_decode_kernel, dim3(nimg), dim3(64), 0, st, huffdec.at<const lephuff::HuffDecImage>(o_img), (lephuff::HuffDecRow*)d_rows);
     HIPCHK(g, hipGetLastError());
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
@@ -1728,23 +1694,19 @@ int lep_gpu_huffman_decode_simt_device(lep_gpu* g, const lep_huffdec_image* imag
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
     HIPCHK(g, hipSetDevice(g->device));
     const size_t nsub_all = plan.nsub_all;
-    lepbuf::Layout P;
-    const size_t o_si = P.add<lephuff::SimtImage>(plan.si.size()), o_wv = P.add<lephuff::SimtWave>(plan.waves.size()), o_s0 = P.add<lephuff::SimtSub>(nsub_all),
+    lepbuf::Block D, P;
+    const size_t o_img = D.add(images, (size_t)nimg);
+    const size_t o_si = P.add(plan.si.data(), plan.si.size()), o_wv = P.add(plan.waves.data(), plan.waves.size()), o_s0 = P.add<lephuff::SimtSub>(nsub_all),
                  o_s1 = P.add<lephuff::SimtSub>(nsub_all), o_pl = P.add<lephuff::SimtPlace>(nsub_all), o_sl = P.add<lephuff::SimtSlots>(plan.nslots);
-    Workspace& huffdec = g->ws[lep_gpu::W_HUFFDEC];
-    if (int rc = ensure(g, huffdec, (size_t)nimg * sizeof(lep_huffdec_image))) return rc;
-    if (int rc = ensure(g, g->ws[lep_gpu::W_HUFFPAR], P.padded())) return rc;
-    char* base = g->ws[lep_gpu::W_HUFFPAR].at<char>(0);
-    HIPCHK(g, hipMemcpyAsync(huffdec, images, (size_t)nimg * sizeof(lep_huffdec_image), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_si, plan.si.data(), plan.si.size() * sizeof(lephuff::SimtImage), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipMemcpyAsync(base + o_wv, plan.waves.data(), plan.waves.size() * sizeof(lephuff::SimtWave), hipMemcpyHostToDevice, st));
-    HIPCHK(g, hipStreamSynchronize(st));   // the caller's array (and ours) may go away
-    const lephuff::HuffDecImage* di = (const lephuff::HuffDecImage*)huffdec.p;
-    lephuff::SimtImage* dsi = (lephuff::SimtImage*)(base + o_si);
-    const lephuff::SimtWave* dwv = (const lephuff::SimtWave*)(base + o_wv);
-    lephuff::SimtSub* buf[2] = {(lephuff::SimtSub*)(base + o_s0), (lephuff::SimtSub*)(base + o_s1)};
-    lephuff::SimtPlace* dpl = (lephuff::SimtPlace*)(base + o_pl);
-    lephuff::SimtSlots* dsl = (lephuff::SimtSlots*)(base + o_sl);
+    Workspace &huffdec = g->ws[lep_gpu::W_HUFFDEC], &par = g->ws[lep_gpu::W_HUFFPAR];
+    if (int rc = stage(g, huffdec, D, st)) return rc;
+    if (int rc = stage(g, par, P, st)) return rc;
+    const lephuff::HuffDecImage* di = huffdec.at<const lephuff::HuffDecImage>(o_img);
+    lephuff::SimtImage* dsi = par.at<lephuff::SimtImage>(o_si);
+    const lephuff::SimtWave* dwv = par.at<const lephuff::SimtWave>(o_wv);
+    lephuff::SimtSub* buf[2] = {par.at<lephuff::SimtSub>(o_s0), par.at<lephuff::SimtSub>(o_s1)};
+    lephuff::SimtPlace* dpl = par.at<lephuff::SimtPlace>(o_pl);
+    lephuff::SimtSlots* dsl = par.at<lephuff::SimtSlots>(o_sl);
     const int nw = (int)plan.waves.size(), nw_plain = plan.nw_plain, nw_wide = nw - nw_plain;
     HIPCHK(g, hipEventRecord(g->ev0, st));
     for (int k = 0; k <= lephuff::kSimtSettle; ++k) {       // pass A (k = 0: nothing is read), then the settle passes
