@@ -262,6 +262,44 @@ int lep_gpu_pack_window_device(lep_gpu *g, const uint8_t *d_src, const uint64_t 
 int lep_gpu_samples_device(lep_gpu *g, const lep_image_desc *images, int nimg, int scale /* 1 or 8 */,
                            const int32_t *row_first, const int32_t *row_end, /* [nimg*3] block rows per component, NULL = all */
                            uint8_t *const *d_planes /* [nimg*3] */, const int32_t *pitch /* [nimg*3], bytes */, void *hip_stream);
+/* 8-bit sample planes in device memory (what lep_gpu_samples_device writes at scale 1) -> pixels: interleaved R,G,B, 3 bytes per pixel,
+ * or 1 byte per pixel for a one-component image, cropped to width x height (lep_rgb.h; nimg images of whatever geometry in one launch;
+ * enqueues on hip_stream and returns; lep_gpu_last_kernel_ms times it).  Equal byte for byte to libjpeg's default full-scale output
+ * (fancy upsampling, no merged upsampling, jdcolor's table arithmetic) when the planes are lep_gpu_samples_device's.
+ * The definition.
+ *   Geometry.  hmax = max h_samp, vmax = max v_samp.  Component c: dw = ceil(width * h_c / hmax), dh = ceil(height * v_c / vmax); only
+ *   the top-left dw x dh samples of its plane are used, x[r][k]; the rest of the block grid is ignored.  fh = hmax / h_c, fv = vmax / v_c
+ *   must be integers.  A one-component image has fh = fv = 1 whatever its factors say.
+ *   Upsampling.  Neighbours out of range are the edge sample itself: up(r) = x[max(r-1, 0)], dn(r) = x[min(r+1, dh-1)], columns alike
+ *   with dw; division is an arithmetic right shift; the result is cropped to width x height.
+ *     (fh, fv) = (1, 1)   out = x
+ *     (2, 1), dw > 2      out[y][2k] = (3 x[y][k] + x[y][k-1] + 1) >> 2;   out[y][2k+1] = (3 x[y][k] + x[y][k+1] + 2) >> 2
+ *     (1, 2), any width   out[2r][k] = (3 x[r][k] + up(r)[k] + 1) >> 2;    out[2r+1][k] = (3 x[r][k] + dn(r)[k] + 2) >> 2
+ *     (2, 2), dw > 2      s[2r][k] = 3 x[r][k] + up(r)[k];  s[2r+1][k] = 3 x[r][k] + dn(r)[k]   (not rounded)
+ *                         out[y][2k] = (3 s[y][k] + s[y][k-1] + 8) >> 4;   out[y][2k+1] = (3 s[y][k] + s[y][k+1] + 7) >> 4
+ *     (2, 1) or (2, 2) with dw <= 2, and every other integral pair (a factor of 3 or 4, (2, 4), (4, 2), ...): replication,
+ *                         out[y][x] = x[y / fv][x / fh]
+ *   Colour (convert != 0).  FIX(f) = (int)(f * 65536 + 0.5), cb' = Cb - 128, cr' = Cr - 128, clamp to 0..255:
+ *     R = clamp(Y + ((FIX(1.40200) cr' + 32768) >> 16));   B = clamp(Y + ((FIX(1.77200) cb' + 32768) >> 16))
+ *     G = clamp(Y + ((-FIX(0.34414) cb' + 32768 - FIX(0.71414) cr') >> 16))
+ *   convert == 0: the components are R, G, B as they are -- upsampled all the same, not converted.
+ * Only output rows [y_first, y_end) are written, at their place; the call reads source rows up to one above and one below the rows the
+ * range maps to, inside [0, dh), and the caller guarantees that those are in the planes: a holder of a decode session colours the
+ * bands that are finished.  An empty range writes nothing.  Uses no workspace of a session.
+ * LEP_ASSERTION_FAILURE with a lep_gpu_last_error text, nothing launched: a missing plane or output, a plane pitch below dw, an rgb_pitch
+ * below the row's bytes, a row range that is not inside the image, ncomp other than 1 or 3, sampling factors outside 1..4 or not
+ * integral multiples, a size outside 1..65535.  LEP_GPU_ERROR as everywhere. */
+typedef struct lep_rgb_image {
+    int32_t width, height, ncomp;                 /* pixels; 1 or 3 components */
+    int32_t h_samp[3], v_samp[3];                 /* sampling factors */
+    int32_t convert;                              /* 1: the components are Y, Cb, Cr; 0: they are R, G, B as they are */
+    const uint8_t *d_plane[3];                    /* device memory: sample (0, 0) of each component */
+    int32_t plane_pitch[3];                       /* bytes from row to row, >= dw */
+    int32_t rgb_pitch;                            /* bytes from pixel row to pixel row, >= width * (ncomp == 1 ? 1 : 3) */
+    uint8_t *d_rgb;                               /* device memory: pixel (0, 0) */
+    int32_t y_first, y_end;                       /* output rows written, 0 <= y_first <= y_end <= height */
+} lep_rgb_image;
+int lep_gpu_rgb_device(lep_gpu *g, const lep_rgb_image *images, int nimg, void *hip_stream);
 /* Progressive files that END INSIDE A SCAN (no EOI) in lep_compress_batch / lep_decompress_batch: on = 1 sends them to the scan kernels
  * (lep_jpeg_open_gpu_progressive_cut, lep_file_recode_plan_progressive_cut), on = 0 -- what a codec starts with, unless
  * LEP_CUT_PROGRESSIVE=1 was set when it was made -- keeps them with the host parser and re-coder, where every earlier release had them;
@@ -590,6 +628,18 @@ typedef struct lep_planes {
     uint8_t *plane[3];                            /* one allocation; lep_free(plane[0]) */
 } lep_planes;
 int lep_decompress_planes(lep_gpu *g, const uint8_t *lepdata, size_t len, int scale, lep_planes *out);
+/* .lep -> pixels: lep_decompress_planes's front at scale 1 (the same files, the same codes for a file that does not parse or a stream
+ * that does not decode), then lep_gpu_rgb_device on the planes where they lie; only the pixels are copied down.  Blocks the file never
+ * coded come out as the definition makes of 128-valued samples.  Which three-component files are converted from YCbCr is libjpeg's
+ * rule, read from the file's header segments and component ids: a JFIF APP0 ("JFIF\0", 14 bytes of data or more) means YCbCr; else an
+ * Adobe APP14 ("Adobe", 12 bytes or more) with transform byte 0 means R, G, B as they are, any other transform YCbCr; else the
+ * component ids 'R', 'G', 'B' mean as they are; else YCbCr.  One component gives one byte per pixel.  LEP_UNSUPPORTED_JPEG with a
+ * lep_gpu_last_error text, nothing launched for the pixels: two components, sampling factors that are no integral multiples. */
+typedef struct lep_rgb {
+    int32_t width, height, channels, pitch;       /* channels: 1 or 3; pitch = width * channels */
+    uint8_t *pixels;                              /* one allocation; lep_free(pixels) */
+} lep_rgb;
+int lep_decompress_rgb(lep_gpu *g, const uint8_t *lepdata, size_t len, lep_rgb *out);
 /* lep_decompress with the JPEG's bytes handed to `sink` as they become final, in file order.  Every single file the split re-coder plans
  * (lep_file_recode_plan says gpu_ok: a baseline file or a -startbyte / -trunc slice of one, 'Z' or 'Y', one scan of one, two or three
  * components, cut inside that scan or not, with or without restart intervals; lep_file_streams_in_session answers for a file)

@@ -150,6 +150,16 @@ class Planes(C.Structure):
                 ("pitch", C.c_int32 * 3), ("plane", C.c_void_p * 3)]
 
 
+class RgbImage(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("h_samp", C.c_int32 * 3), ("v_samp", C.c_int32 * 3),
+                ("convert", C.c_int32), ("d_plane", C.c_void_p * 3), ("plane_pitch", C.c_int32 * 3), ("rgb_pitch", C.c_int32),
+                ("d_rgb", C.c_void_p), ("y_first", C.c_int32), ("y_end", C.c_int32)]
+
+
+class Rgb(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("pitch", C.c_int32), ("pixels", C.c_void_p)]
+
+
 class BatchOptions(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("verify", C.c_int32), ("chunk_frame_bytes", C.c_size_t), ("host_huffman", C.c_int32), ("chunk_images", C.c_int32), ("overlap_launches", C.c_int32)]
 
@@ -261,6 +271,9 @@ def lib():
         if hasattr(L, "lep_gpu_samples_device"):   # (absent from an older build named by LEP_LIB_PATH)
             L.lep_gpu_samples_device.argtypes = [vp, P(ImageDesc), C.c_int, C.c_int, P(C.c_int32), P(C.c_int32), P(vp), P(C.c_int32), vp]
             L.lep_decompress_planes.argtypes = [vp, vp, C.c_size_t, C.c_int, P(Planes)]
+        if hasattr(L, "lep_gpu_rgb_device"):
+            L.lep_gpu_rgb_device.argtypes = [vp, P(RgbImage), C.c_int, vp]
+            L.lep_decompress_rgb.argtypes = [vp, vp, C.c_size_t, P(Rgb)]
         L.lep_gpu_use_arena.argtypes = [vp, C.c_int]
         L.lep_gpu_sync.argtypes = [vp]
         L.lep_gpu_last_kernel_ms.argtypes = [vp]
@@ -366,5 +379,6 @@ EXPORTS = [
     "lep_decompress_batch_ranges", "lep_decompress_range",
     "lep_gpu_debug_write_bins", "lep_gpu_debug_wchunks",
     "lep_gpu_samples_device", "lep_decompress_planes",
+    "lep_gpu_rgb_device", "lep_decompress_rgb",
     "lep_batch_debug_compare", "lep_batch_debug_scan_check", "lep_batch_debug_tamper", "lep_batch_debug_tamper_applied", "lep_batch_debug_tamper_seen",
 ]

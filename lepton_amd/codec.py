@@ -381,6 +381,73 @@ class GpuCodec:
             for p in owned:
                 L.lep_gpu_free(h, p)
 
+    def decompress_rgb(self, lep):
+        """lep_decompress_rgb: a dict of width, height, channels (1 or 3), pitch and "pixels": pitch * height bytes, R,G,B interleaved or
+        one byte per pixel"""
+        out = abi.Rgb()
+        rc = self._L.lep_decompress_rgb(self.handle, bytes(lep), len(lep), C.byref(out))
+        if rc:
+            raise LeptonError(rc, "lep_decompress_rgb [%s]" % self.last_error())
+        res = {k: getattr(out, k) for k in ("width", "height", "channels", "pitch")}
+        res["pixels"] = C.string_at(out.pixels, out.pitch * out.height)
+        self._L.lep_free(out.pixels)
+        return res
+
+    def rgb(self, images):
+        """lep_gpu_rgb_device on host planes.  images: a list of dicts with width, height, h_samp, v_samp (lists, one entry per component),
+        convert, planes (per component the plane's bytes exactly as they go up, None = no plane), plane_pitch (per component), rgb_pitch and
+        optionally rows = (y_first, y_end) (default: every row) and no_output = True (a null output pointer).  The planes go up, the
+        outputs are laid out in one device buffer filled with SAMPLES_CANARY -- SAMPLES_MARGIN bytes, the output (rgb_pitch * height bytes),
+        SAMPLES_MARGIN bytes, for every image -- and the launch runs.  Returns per image the output's whole buffer with both margins
+        (bytes).  Raises LeptonError with the entry point's code; LeptonError.buffers then holds the buffers as they were left."""
+        L, h = self._L, self.handle
+        nimg = len(images)
+        recs = (abi.RgbImage * max(nimg, 1))()
+        owned = []
+
+        def dmalloc(k):
+            p = C.c_void_p()
+            _check(L.lep_gpu_malloc(h, max(k, 16), C.byref(p)), "lep_gpu_malloc")
+            owned.append(p)
+            return p
+
+        try:
+            sizes, offs, room = [], [], 0
+            for i, m in enumerate(images):
+                r = recs[i]
+                r.width, r.height, r.ncomp, r.convert = m["width"], m["height"], m.get("ncomp", len(m["planes"])), 1 if m.get("convert", True) else 0
+                for c, plane in enumerate(m["planes"][:3]):
+                    r.h_samp[c], r.v_samp[c], r.plane_pitch[c] = m["h_samp"][c], m["v_samp"][c], m["plane_pitch"][c]
+                    if plane is not None:
+                        raw = bytes(plane)
+                        p = dmalloc(len(raw))
+                        _check(L.lep_gpu_memcpy_h2d(h, p, raw, len(raw)), "h2d")
+                        r.d_plane[c] = p.value
+                r.rgb_pitch = m["rgb_pitch"]
+                r.y_first, r.y_end = m.get("rows") or (0, m["height"])
+                sizes.append(max(r.rgb_pitch, 0) * max(r.height, 0))
+                offs.append(room + self.SAMPLES_MARGIN)
+                room = offs[i] + sizes[i] + self.SAMPLES_MARGIN
+            d_out = dmalloc(room)
+            _check(L.lep_gpu_memset(h, d_out, self.SAMPLES_CANARY, room), "memset")
+            for i, m in enumerate(images):
+                recs[i].d_rgb = None if m.get("no_output") else d_out.value + offs[i]
+            rc = L.lep_gpu_rgb_device(h, recs, nimg, None)
+            if not rc:
+                rc = L.lep_gpu_sync(h)
+            host = C.create_string_buffer(max(room, 1))
+            _check(L.lep_gpu_memcpy_d2h(h, host, d_out, room), "d2h")
+            raw = host.raw
+            bufs = [raw[offs[i] - self.SAMPLES_MARGIN:offs[i] + sizes[i] + self.SAMPLES_MARGIN] for i in range(nimg)]
+            if rc:
+                e = LeptonError(rc, "lep_gpu_rgb_device [%s]" % self.last_error())
+                e.buffers = bufs
+                raise e
+            return bufs
+        finally:
+            for p in owned:
+                L.lep_gpu_free(h, p)
+
     def _batch(self, fn, blobs, verify, threads, chunk_bytes, chunk_images=0, host_huffman=False):
         n = len(blobs)
         ins = (abi.Bytes * n)()

@@ -33,6 +33,7 @@
 #include "lep_huffprogdec_rst.h"
 #include "lep_scan_decode_plan.h"
 #include "lep_pack.h"
+#include "lep_rgb.h"
 #include "lep_samples.h"
 
 using namespace lepdev;
@@ -385,6 +386,13 @@ __global__ __launch_bounds__(64 * lepsamples::kWavesPerGroup) void lep_samples_d
     if (unit >= first[nplanes]) return;
     lepsamples::wave_samples_dc(recs, first, nplanes, unit);
 }
+// sample planes -> pixels (lep_rgb.h): four wavefronts per workgroup, each with a unit of its own
+__global__ __launch_bounds__(64 * leprgb::kWavesPerGroup) void lep_rgb_kernel(const leprgb::RgbRec* __restrict__ recs, const uint32_t* __restrict__ first, int nimg) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = blockIdx.x * (uint32_t)leprgb::kWavesPerGroup + (uint32_t)wave;
+    if (unit >= first[nimg]) return;
+    leprgb::wave_rgb(recs, first, nimg, unit);
+}
 // ... with a window per run (lep_gpu_pack_window_device): the clipped lengths are made here, from the device's lengths, summed, and left in wlen
 __global__ __launch_bounds__(leppack::kScanLanes) void lep_pack_window_offsets_kernel(const uint32_t* __restrict__ len, const uint32_t* __restrict__ skip,
                                                                                       const uint32_t* __restrict__ take, int n, uint32_t* __restrict__ wlen,
@@ -671,6 +679,7 @@ struct lep_gpu {
         W_HUFFPAR,                  // the lane-per-subsequence scan decoder's records (SimtImage | SimtWave | SimtSub x 2 | SimtPlace)
         W_PACK, W_PACK_1,           // lep_gpu_pack_device: the runs' source offsets (one per arena set, like W_HUFF)
         W_SAMPLES, W_SAMPLES_1,     // lep_gpu_samples_device: PlaneRec[] | first[] (one per arena set)
+        W_RGB, W_RGB_1,             // lep_gpu_rgb_device: RgbRec[] | first[] (one per arena set)
         W_COUNT
     };
     lepbuf::DevBuf<> ws[W_COUNT];
@@ -957,7 +966,7 @@ static int launch_enc5(lep_gpu* g, const ImageDev* d_img, const SegDev* d_seg, c
 // The sizes of the descriptor types that are staged, as tests/test_stage_block.py walks them: a type that changes size stops the build here.
 #define LEP_STAGED(T, N) static_assert(sizeof(T) == N, "a staged descriptor changed size: tests/test_stage_block.py WORKSPACES and tests/emu/stage_block_probe.cc ELEM_SIZES name it")
 LEP_STAGED(ImageDev, 2208); LEP_STAGED(SegDev, 32); LEP_STAGED(lep_huff_image, 4272); LEP_STAGED(lep_huff_segment, 40); LEP_STAGED(lephuff::SimtEncSeg, 40);
-LEP_STAGED(lephuff::SimtEncWave, 8); LEP_STAGED(lepsamples::PlaneRec, 176); LEP_STAGED(lep_huffprog_image, 168); LEP_STAGED(lep_huffprog_scan, 4184);
+LEP_STAGED(lephuff::SimtEncWave, 8); LEP_STAGED(lepsamples::PlaneRec, 176); LEP_STAGED(leprgb::RgbRec, 112); LEP_STAGED(lep_huffprog_image, 168); LEP_STAGED(lep_huffprog_scan, 4184);
 LEP_STAGED(lephuff::ProgSimtScan, 48); LEP_STAGED(lephuff::ProgSimtWave, 8); LEP_STAGED(lephuff::ProgSimtRegion, 24); LEP_STAGED(lep_huffprogdec_scan, 5696);
 LEP_STAGED(lephuff::ProgDeps, 16); LEP_STAGED(lephuff::ProgRstScan, 16); LEP_STAGED(lephuff::ProgRstOut, 24); LEP_STAGED(lep_huffdec_image, 5552);
 LEP_STAGED(lephuff::SimtImage, 36); LEP_STAGED(lephuff::SimtWave, 8); LEP_STAGED(lephuff::SimtSub, 20); LEP_STAGED(lephuff::SimtPlace, 12); LEP_STAGED(lephuff::SimtSlots, 32);
@@ -1489,6 +1498,54 @@ int lep_gpu_samples_device(lep_gpu* g, const lep_image_desc* images, int nimg, i
     HIPCHK(g, hipEventRecord(g->ev1, st));
     g->timed = true;
     g->last_kernel = scale == 1 ? "lep_samples_kernel" : "lep_samples_dc_kernel";
+    return 0;
+}
+
+// Sample planes in device memory -> pixels (lep_rgb.h).  Like lep_gpu_samples_device its one workspace, W_RGB of the current arena set, is
+// no decode session's: a caller that holds a session colours each finished band with a row range.
+int lep_gpu_rgb_device(lep_gpu* g, const lep_rgb_image* images, int nimg, void* hip_stream) {
+    if (!g) return LEP_GPU_ERROR;
+    auto refuse = [g](const std::string& what) { g->err = "lep_gpu_rgb_device: " + what; return (int)LEP_ASSERTION_FAILURE; };
+    if (nimg < 0 || nimg > (1 << 20) || (nimg > 0 && !images)) return refuse("images");
+    std::vector<leprgb::RgbRec> recs;
+    std::vector<uint32_t> first(1, 0u);
+    for (int i = 0; i < nimg; ++i) {
+        const lep_rgb_image& m = images[i];
+        const std::string who = "image " + std::to_string(i) + ": ";
+        if (m.ncomp != 1 && m.ncomp != 3) return refuse(who + std::to_string(m.ncomp) + " components (1 or 3)");
+        if (m.width < 1 || m.height < 1 || m.width > 65535 || m.height > 65535) return refuse(who + std::to_string(m.width) + " x " + std::to_string(m.height) + " pixels");
+        leprgb::RgbRec r;
+        const int64_t units = leprgb::fill_image(&r, m.width, m.height, m.ncomp, m.h_samp, m.v_samp, m.convert, m.d_plane, m.plane_pitch, m.d_rgb, m.rgb_pitch, m.y_first, m.y_end);
+        if (units < 0) return refuse(who + "sampling factors that are not 1..4 or no integral multiples of one another");
+        if (!m.d_rgb) return refuse(who + "no output");
+        const int row_bytes = m.width * (m.ncomp == 1 ? 1 : 3);
+        if (m.rgb_pitch < row_bytes) return refuse(who + "rgb_pitch " + std::to_string(m.rgb_pitch) + " is less than a row's " + std::to_string(row_bytes) + " bytes");
+        if (m.y_first < 0 || m.y_end < m.y_first || m.y_end > m.height)
+            return refuse(who + "rows [" + std::to_string(m.y_first) + ", " + std::to_string(m.y_end) + ") are not rows of its " + std::to_string(m.height));
+        for (int c = 0; c < m.ncomp; ++c) {
+            if (!m.d_plane[c]) return refuse(who + "component " + std::to_string(c) + " has no plane");
+            if (m.plane_pitch[c] < r.dw[c])
+                return refuse(who + "component " + std::to_string(c) + ": pitch " + std::to_string(m.plane_pitch[c]) + " is less than its " + std::to_string(r.dw[c]) + " samples");
+        }
+        if ((uint64_t)units + first.back() > 0x7fffffffull) return refuse("more than 2^31 wavefront units in one call");
+        recs.push_back(r);
+        first.push_back(first.back() + (uint32_t)units);
+    }
+    const uint32_t total = first.back();
+    if (!total) return 0;   // nothing to write: empty row ranges
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : g->stream;
+    HIPCHK(g, hipSetDevice(g->device));
+    Workspace& ws = g->ws[lep_gpu::W_RGB + (g->cur & 1)];
+    lepbuf::Block B;   // the records, the unit counts behind them
+    const size_t o_recs = B.add(recs.data(), recs.size()), o_first = B.add(first.data(), first.size(), 4);
+    if (int rc = stage(g, ws, B, st)) return rc;
+    const unsigned groups = (total + leprgb::kWavesPerGroup - 1) / leprgb::kWavesPerGroup;
+    HIPCHK(g, hipEventRecord(g->ev0, st));
+    hipLaunchKernelGGL(lep_rgb_kernel, dim3(groups), dim3(64 * leprgb::kWavesPerGroup), 0, st, ws.at<const leprgb::RgbRec>(o_recs), ws.at<const uint32_t>(o_first), nimg);
+    HIPCHK(g, hipGetLastError());
+    HIPCHK(g, hipEventRecord(g->ev1, st));
+    g->timed = true;
+    g->last_kernel = "lep_rgb_kernel";
     return 0;
 }
 
@@ -2094,3 +2151,11 @@ int lep_gpu_decode_host(lep_gpu* g, const lep_image_desc* images, int nimg, cons
 }
 
 }  // extern "C"
+
+// a refusal made outside this file in the object's name (lep_planes.cc; declared in lep_handles.h): the text lep_gpu_last_error returns
+namespace lep {
+int gpu_refuse(lep_gpu* g, int code, const std::string& what) {
+    if (g) g->err = what;
+    return code;
+}
+}  // namespace lep
